@@ -24,6 +24,10 @@ Timing: W untimed steps, then exactly K steps between barrier + torch.cuda.synch
 `ms_per_step`, `roofline` (launch duration by HIP events on the launch stream).  The same window is then repeated after
 CLOCK_RAMP_MS of untimed steps and reported beside it as `clock_ramp.steady_state` (information: a short window straight after
 start-up runs at the board's idle clock).  `cpu_baseline` and `extras` (Fri.prove, LDE, census, Merkle, ...) follow, rank 0, N = 1.
+
+--dump-outputs DIR (N = 1, ntt): after the timed windows, the last step's forward and inverse outputs go to DIR/ntt_forward.npy
+and DIR/ntt_inverse.npy (a fixed, seeded sample of 2^19 elements each, as 32-bit limbs in float64; positions in
+DIR/element_index.npy).  The inputs depend on the arguments alone, so two builds can be compared output for output.
 """
 import argparse
 import itertools
@@ -164,7 +168,17 @@ def main():
                          "0.7 -- so they are dropped in that order, and the line says which were (config.legs); 0 = no limit")
     ap.add_argument("--allow-replicas", action="store_true",
                     help="N > 1: if the sharded path cannot be set up, time N independent single-GPU transforms instead of exiting non-zero")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="single-GPU ntt workload: after the timed steps write what the last step computed (forward and inverse outputs) "
+                         "as DIR/<name>.npy for output-for-output comparison of two builds; see dump_outputs()")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or args.force_sharded or args.workload != "ntt"):
+        ap.error("--dump-outputs is supported for the single-GPU ntt workload only")
+    if (args.steps is not None and args.steps < 1) or (args.warmup is not None and args.warmup < 0):
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    # an explicit --steps / --warmup is what runs; the per-workload caps of run_census_workload / run_stark_prove_workload apply to
+    # the defaults only
+    args.steps_given, args.warmup_given = args.steps is not None, args.warmup is not None
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args))            # bare `python bench.py --gpus N`: become N ranks under torch.distributed.run
@@ -320,6 +334,7 @@ def main():
     for _ in range(ramp_steps):
         step()
     steady_elapsed, steady_ev_ms = timed_window()
+    dumped = dump_outputs(args.dump_outputs, {"ntt_forward": y, "ntt_inverse": z}) if args.dump_outputs else None
 
     # correctness guard inside the bench: the round trip must reproduce the input bit for bit
     ok = bool(torch.equal(z, x))
@@ -501,7 +516,7 @@ def main():
             "scaling": scaling_label, "vs_baseline": None, "dtype": "u128", "data": "synthetic",
             "config": {"workload": workload, "log2n": log2n, "columns_per_step": (cols if not sharded else 1), "elements_per_step": 2 * total_n, "parallelism": parallelism,
                        "passes_per_transform": passes, "roundtrip_bit_exact": ok, "forward_sha256_equals_reference_output": reference_sha,
-                       **({"tune": args.tune} if args.tune else {})},
+                       **({"tune": args.tune} if args.tune else {}), **({"dumped_outputs": dumped} if dumped else {})},
             "clock_ramp": {"untimed_steps_between_windows": ramp_steps, "target_ms": CLOCK_RAMP_MS,
                            "steady_state": {"value": 2.0 * total_n * args.steps / steady_elapsed, "ms_per_step": 1e3 * steady_elapsed / args.steps,
                                             "avg_launch_us": steady_ev_ms * 1e3 / (args.steps * launches_per_step),
@@ -589,7 +604,8 @@ def run_census_workload(args, rank, world, dev, stream, dist, backend, shared_gp
     import torch
     ngpu = torch.cuda.device_count()
     log_fri = args.log2n or (16 if shared_gpus else 20 + (world.bit_length() - 1) + 1)
-    steps, warmup = min(args.steps, 20), max(1, min(args.warmup, 2))
+    steps = args.steps if args.steps_given else min(args.steps, 20)
+    warmup = args.warmup if args.warmup_given else max(1, min(args.warmup, 2))
     for _ in range(warmup):
         sharded_census(log_fri, rank, world, dev, stream)
     dist.barrier()
@@ -625,7 +641,8 @@ def run_stark_prove_workload(args, rank, world, dev, stream, dist, backend, shar
     import torch
     ngpu = torch.cuda.device_count()
     log_fri = args.log2n or (16 if shared_gpus else 24)
-    steps, warmup = max(1, min(args.steps, 5)), max(1, min(args.warmup, 1))
+    steps = args.steps if args.steps_given else max(1, min(args.steps, 5))
+    warmup = args.warmup if args.warmup_given else max(1, min(args.warmup, 1))
     elapsed, same_everywhere, rec = stark_prove_measure(log_fri, steps, warmup, rank, world, dev, dist, backend, phases=True)
     if rank == 0:
         rec["collective_backend"] = collective_label(backend, world, ngpu, shared_gpus)
@@ -882,6 +899,37 @@ def extras(sc, lib, stream=None):
     except Exception as e:
         res["stark_prove_2p24_1gpu"] = {"error": repr(e)}
     return res
+
+
+DUMP_ELEMENTS = 1 << 19      # per output: 2^19 elements x 4 limbs x 8 B = 16 MiB, so two outputs and the index stay under 64 MiB
+DUMP_SEED = 20240601
+
+
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs: write each device vector of u128 field elements (int64 tensor of (lo, hi) pairs) as out_dir/<name>.npy,
+    shape (k, 4) float64: the element's four 32-bit limbs, least significant first (exact in float64).  A vector of more than
+    DUMP_ELEMENTS elements is sampled: one element from each of DUMP_ELEMENTS equal strides, its offset in the stride drawn from
+    a generator seeded with DUMP_SEED, so the positions depend on the vector's length alone; they are written as
+    element_index.npy (float64).  Every output of a call has the same length.  Returns what was written, for the JSON line."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    total = next(iter(outputs.values())).numel() // 2
+    assert all(t.numel() == 2 * total for t in outputs.values())
+    if total <= DUMP_ELEMENTS:
+        idx = np.arange(total, dtype=np.int64)
+    else:
+        stride = total // DUMP_ELEMENTS
+        idx = np.arange(DUMP_ELEMENTS, dtype=np.int64) * stride + np.random.default_rng(DUMP_SEED).integers(0, stride, DUMP_ELEMENTS)
+    np.save(os.path.join(out_dir, "element_index.npy"), idx.astype(np.float64))
+    idx_dev = None
+    for name, t in outputs.items():
+        if idx_dev is None:
+            idx_dev = torch.from_numpy(idx).to(t.device)
+        pairs = t.view(-1, 2).index_select(0, idx_dev).cpu().numpy()          # (k, 2) int64: lo, hi
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(pairs).view(np.uint32).astype(np.float64))
+    return {"dir": out_dir, "files": sorted(list(outputs) + ["element_index"]), "elements_per_output": int(idx.size), "of": total,
+            "format": "float64 (k, 4): 32-bit limbs of each element, least significant first"}
 
 
 def ctypes_void(v):
