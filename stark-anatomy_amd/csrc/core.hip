@@ -72,8 +72,9 @@ __global__ void __launch_bounds__(1 << (GLR + GLC - LOGE)) ntt_pass_kernel_fixed
 }
 
 // The 2^12-element shapes with EIGHT elements per thread, for the batches of columns (NttTuning::loge_cols): 512 threads, three stages per
-// round, and the register budget of four waves per SIMD (128 VGPRs, one spilled), so that two workgroups share a CU and one computes
-// while the other loads or drains.  No trace, no second destination (those launches take the generic kernel).
+// round, and the register budget of four waves per SIMD (122 of 128 VGPRs, no scratch), so that two workgroups share a CU and one computes
+// while the other loads or drains.  Global accesses are  s[base] + 32-bit lane offset  (Round::SPLIT_ADDR), so the launch needs every
+// per-thread offset below 4 GiB (fixed_offsets_fit).  No trace, no second destination (those launches take the generic kernel).
 template <int GLR, int GLC>
 __global__ void __launch_bounds__(1 << (GLR + GLC - 3)) __attribute__((amdgpu_waves_per_eu(4)))
 ntt_pass_kernel_fixed8(const PassParams P, uint32_t ntiles, int xcd_remap, int wave_local) {
@@ -626,7 +627,7 @@ void launch_pass(const NttPassDesc& pd, hipStream_t st) {
         }
     }
     if constexpr (LOGE == 3) {
-        if (g.fixed_shapes && !pd.p.trace && !pd.p.blk_enable) {
+        if (g.fixed_shapes && !pd.p.trace && !pd.p.blk_enable && fixed_offsets_fit(pd.p)) {
             const int lr = pd.p.logR, lc = pd.p.logC;
 #define SC_FIXED8(LR, LC) if (lr == LR && lc == LC) { hipLaunchKernelGGL((ntt_pass_kernel_fixed8<LR, LC>), dim3(pd.ntiles * pd.cols), dim3(pd.threads), pd.lds_bytes, st, pd.p, pd.ntiles, remap, g.wave_local); return; }
             SC_FIXED8(10, 2) SC_FIXED8(9, 3) SC_FIXED8(8, 4)

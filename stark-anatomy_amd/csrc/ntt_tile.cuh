@@ -163,6 +163,7 @@ struct Round {
     uint32_t t_lo, t_mid, t_hi;
     uint64_t col_off, col_off_in;  // first element of this workgroup's column in `out` / `in` (0 unless the launch covers several transforms)
     int logR, logC;
+    bool rfast;       // (SPLIT_ADDR) this round's lanes run along rows: first round of a transposing pass
 
     SC_HD void setup(const PassParams& P, bool first, uint32_t tile, uint32_t tid) {
         logR = (GLR >= 0) ? GLR : P.logR;
@@ -191,12 +192,56 @@ struct Round {
             rr[g] = rrem;
             cc[g] = c;
         }
+        if constexpr (SPLIT_ADDR) rfast = first && P.rfast_load;
     }
-    SC_HD uint32_t row(int i, int sh) const {
-        const int g = i >> S, fi = i & (F - 1);
-        const uint32_t rrem = rr[g];
-        return ((rrem >> sh) << (sh + S)) | ((uint32_t)fi << sh) | (rrem & ((1u << sh) - 1u));
+    struct Uc { uint32_t rrem, c; };
+    // group element rem -> (row bits outside the field, column), as setup() splits it; by value and with selects (outputs through
+    // references picked by the runtime `rfast` put the pair on the stack)
+    SC_HD Uc split(uint32_t rem) const {
+        const uint32_t rs = logR - S;
+        return Uc{rfast ? (rem & ((1u << rs) - 1u)) : (rem >> logC), rfast ? (rem >> rs) : (rem & ((1u << logC) - 1u))};
     }
+    SC_HD static uint32_t row_of(uint32_t rrem, uint32_t fi, int sh) {
+        return ((rrem >> sh) << (sh + S)) | (fi << sh) | (rrem & ((1u << sh) - 1u));
+    }
+    SC_HD uint32_t row(int i, int sh) const { return row_of(rr[i >> S], (uint32_t)(i & (F - 1)), sh); }
+
+    // Geometry-specialised addressing (the eight-element FixedRounds kernels and their CPU emulation).  With T threads a power of
+    // two, group element rem = g * T + tid is the disjoint OR of g * T and tid, and split(), row_of() and bitrev32() only move bit
+    // fields, so every row / column / output-row index of element i is  (part of tid) | (part of i)  -- a SUM of a per-thread value
+    // and a compile-time-shaped uniform one.  Memory index = uniform(i) + lane: the uniform part (tile, column, the element's own
+    // rows and columns times the runtime strides) is scalar work, the lane part is computed once per thread as a 32-bit byte offset,
+    // and each access is  global_load/store v, v_lane, s[base(i)]  instead of a 64-bit index product and address add per element.
+    // The launch keeps the lane byte offsets below 2^32 (fixed_offsets_fit); other launches take the generic kernel.
+    // Eight-element kernels only (the batches): built into the four-element ones too, it cost 3-4.5 % on their launches (one 2^20
+    // column at a time, 2^22, 2^24; same-box A/B, profiles/fixed8_addressing), so those keep the per-element form.
+    static constexpr bool SPLIT_ADDR = GLR >= 0 && GLC >= 0 && LOGE == 3;
+    SC_HD Uc group_part(int g) const { return split((uint32_t)g * (1u << (logR + logC - LOGE))); }     // the uniform part of rr[g] / cc[g]
+    // Element at  base + lane_bytes  with `base` uniform: the base is pinned in SGPRs (an empty asm the compiler may not look
+    // through -- otherwise it folds the lane offset into the base ONCE, as a 64-bit VGPR pointer, and pays a 64-bit VGPR add per
+    // access) and the access goes through a global (address space 1) pointer, so that it is  global_load/store v, v_off, s[base].
+    template <class T> SC_HD static T sgpr_pin(T v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm("" : "+s"(v));
+#endif
+        return v;
+    }
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef __attribute__((address_space(1))) char gchar;
+    typedef __attribute__((address_space(1))) Fe gfe;
+    // (the offset is pinned too, in the access's own block: a zero-extension the compiler hoisted out of a branch would arrive as a
+    // 64-bit register and miss the s[base] + v_offset form)
+    SC_HD static uint32_t vgpr_pin(uint32_t v) { asm("" : "+v"(v)); return v; }
+    SC_HD static Fe load_at(const Fe* base, uint32_t lane_bytes) {
+        return *reinterpret_cast<const gfe*>(reinterpret_cast<const gchar*>(sgpr_pin(reinterpret_cast<uint64_t>(base))) + vgpr_pin(lane_bytes));
+    }
+    SC_HD static void store_at(Fe* base, uint32_t lane_bytes, Fe v) {
+        *reinterpret_cast<gfe*>(reinterpret_cast<gchar*>(sgpr_pin(reinterpret_cast<uint64_t>(base))) + vgpr_pin(lane_bytes)) = v;
+    }
+#else
+    static Fe load_at(const Fe* base, uint32_t lane_bytes) { return *reinterpret_cast<const Fe*>(reinterpret_cast<const char*>(base) + lane_bytes); }
+    static void store_at(Fe* base, uint32_t lane_bytes, Fe v) { *reinterpret_cast<Fe*>(reinterpret_cast<char*>(base) + lane_bytes) = v; }
+#endif
     // memory index of element i of the first round
     SC_HD uint64_t in_index(const PassParams& P, int i, int sh) const {
         const uint32_t r = row(i, sh), c = cc[i >> S];
@@ -207,6 +252,14 @@ struct Round {
     }
     // first round: issue the global loads (data, and the previous pass's four-step twiddles when they are applied on load)
     SC_HD void gather_global(const PassParams& P, int sh, Fe* x, Fe* tin) const {
+        if constexpr (SPLIT_ADDR) {
+            if (!P.in_split) {
+                // the zero-padding test only where the launch pads (in_limit < ~0: the first pass of an LDE)
+                if (P.in_limit == ~0ull) gather_split<false>(P, sh, x, tin);
+                else gather_split<true>(P, sh, x, tin);
+                return;
+            }
+        }
 #pragma unroll
         for (int i = 0; i < E; ++i) {
             const uint64_t j = in_index(P, i, sh);
@@ -214,6 +267,26 @@ struct Round {
             if (j < P.in_limit) v = P.in[col_off_in + j];
             x[i] = v;
             if (P.twd_in) tin[i] = P.twd_in[j & P.twd_in_mask];
+        }
+    }
+    template <bool LIMIT>
+    SC_HD void gather_split(const PassParams& P, int sh, Fe* x, Fe* tin) const {
+        const uint64_t tile_j = (uint64_t)t_hi * P.in_hi + (uint64_t)t_mid * P.in_mid + (uint64_t)t_lo * P.in_lo;
+        const uint32_t lane = row_of(rr[0], 0, sh) * (uint32_t)P.in_rs + cc[0] * (uint32_t)P.in_cs;
+        const Fe* src = P.in + col_off_in;
+#pragma unroll
+        for (int i = 0; i < E; ++i) {
+            const Uc u = group_part(i >> S);
+            const uint64_t ju = tile_j + (uint64_t)row_of(u.rrem, (uint32_t)(i & (F - 1)), sh) * P.in_rs + (uint64_t)u.c * P.in_cs;
+            if constexpr (LIMIT) {
+                // j = ju + lane < in_limit, as a 32-bit compare against the (uniform) room left above ju
+                const uint64_t room = P.in_limit > ju ? P.in_limit - ju : 0;
+                const uint32_t room32 = sgpr_pin(room > 0xffffffffull ? 0xffffffffu : (uint32_t)room);
+                x[i] = lane < room32 ? load_at(src + ju, lane << 4) : fe_zero();
+            } else {
+                x[i] = load_at(src + ju, lane << 4);
+            }
+            if (P.twd_in) tin[i] = P.twd_in[(ju + lane) & P.twd_in_mask];
         }
     }
     // first round: the multiplications that belong to the load (coset scaling, twiddle-on-load)
@@ -339,6 +412,22 @@ struct Round {
     // the direct four-step twiddles of this thread's E output elements (PassParams::twd): issued early by the fixed-shape kernel,
     // at the top of the last round, so that their latency hides behind that round's butterflies
     SC_HD void load_twd(const PassParams& P, Fe* t) const {
+        if constexpr (SPLIT_ADDR) {
+            const uint32_t lane = bitrev32(row_of(rr[0], 0, 0), logR) * (uint32_t)(P.tw_row_k * P.twd_stride) + (cc[0] >> P.tw_col_shift);
+#pragma unroll
+            for (int i = 0; i < E; ++i) {
+                const Uc u = group_part(i >> S);
+                const uint32_t k = bitrev32(row_of(u.rrem, (uint32_t)(i & (F - 1)), 0), logR);
+                const uint64_t colidx = ((((uint64_t)t_lo << logC) | u.c) >> P.tw_col_shift) + P.tw_col_base;
+                const uint64_t ju = ((uint64_t)k * P.tw_row_k + (uint64_t)t_mid * P.tw_row_mid) * P.twd_stride + colidx;
+#if SC_TWD_NT
+                t[i] = load_stream(P.twd + ju + lane);
+#else
+                t[i] = load_at(P.twd + ju, lane << 4);
+#endif
+            }
+            return;
+        }
 #pragma unroll
         for (int i = 0; i < E; ++i) {
             const uint32_t k = bitrev32(row(i, 0), logR);
@@ -393,6 +482,19 @@ struct Round {
         if (P.scale_enable) {
 #pragma unroll
             for (int i = 0; i < E; ++i) v[i] = mont_mul(v[i], P.scale);
+        }
+        if constexpr (SPLIT_ADDR && !ALT) {
+            const uint64_t tile_j = (uint64_t)t_hi * P.out_hi + (uint64_t)t_mid * P.out_mid + (uint64_t)t_lo * P.out_lo;
+            const uint32_t lane = bitrev32(row_of(rr[0], 0, 0), logR) * (uint32_t)P.out_rs + cc[0] * (uint32_t)P.out_cs;
+            Fe* dst = P.out + col_off;
+#pragma unroll
+            for (int i = 0; i < E; ++i) {
+                const Uc u = group_part(i >> S);
+                const uint32_t k = bitrev32(row_of(u.rrem, (uint32_t)(i & (F - 1)), 0), logR);
+                const uint64_t ju = tile_j + (uint64_t)k * P.out_rs + (uint64_t)u.c * P.out_cs;
+                store_at(dst + ju, lane << 4, v[i]);
+            }
+            return;
         }
 #pragma unroll
         for (int i = 0; i < E; ++i) {
@@ -511,6 +613,17 @@ struct FixedRounds {
         }
     }
 };
+
+// Launch condition of the eight-element geometry-specialised kernels (Round::SPLIT_ADDR): every per-thread byte offset of the pass -- a row below R
+// times its stride plus a column below C times its stride -- fits in 32 bits.
+inline bool fixed_offsets_fit(const PassParams& P) {
+    typedef unsigned __int128 u128;
+    const u128 lim = (u128)1 << 32, r1 = (1u << P.logR) - 1u, c1 = (1u << P.logC) - 1u;
+    if (!P.in_split && (r1 * P.in_rs + c1 * P.in_cs) * sizeof(Fe) >= lim) return false;
+    if (!P.blk_enable && (r1 * P.out_rs + c1 * P.out_cs) * sizeof(Fe) >= lim) return false;
+    if (P.tw_enable && P.twd && (r1 * P.tw_row_k * P.twd_stride + (c1 >> P.tw_col_shift)) * sizeof(Fe) >= lim) return false;
+    return true;
+}
 
 // Round schedule shared by the kernel and the CPU emulation: the short round (if any) goes first.
 struct RoundSched {
