@@ -219,7 +219,10 @@ int sc_coset_divide_dev(const void* d_a, uint64_t na, const void* d_b, uint64_t 
  * words_out[1]: the highest index, counted from n_out, of a non-zero coefficient of the interpolant above the quotient, -1 iff the
  * division is exact (always -1 for the pointwise form).  A prover collects its checks where it has to wait anyway (before the next
  * Fiat-Shamir challenge) instead of idling the GPU at every division.  sc_later_wait frees the handle (it is also how one is abandoned).
- * SC_ERR_UNSUPPORTED: no pinned slot free -- use the waiting forms. */
+ * SC_ERR_UNSUPPORTED: no pinned slot free (they are shared with the asynchronous Merkle roots); NOTHING was enqueued, so d_out -- and a
+ * numerator divided in place -- is as it was: use the waiting forms.  Each check has device words of its own, so checks in flight on
+ * any number of streams do not disturb one another; but the coset form, like sc_coset_divide_dev, runs its transforms in the
+ * library's shared scratch, so coset divisions (deferred or not) must be ordered on one stream.  The pointwise form has no such limit. */
 int sc_coset_divide_later_dev(const void* d_a, uint64_t na, const void* d_b, uint64_t nb, const uint64_t offset[2], const uint64_t root[2], uint64_t order,
                               void* d_out, uint64_t n_out, sc_later_t** later, void* stream);
 int sc_pointwise_div_later_dev(const void* d_a, const void* d_b, void* d_out, uint64_t n, sc_later_t** later, void* stream);

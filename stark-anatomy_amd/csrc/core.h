@@ -130,11 +130,13 @@ struct Ctx {
     int fri_tail = -1;       // the persistent tail kernel of Fri.commit (csrc/fri_tail.cuh): -1 = environment STARKCORE_FRI_TAIL (default on), 0 / 1
     int fri_tail_stall = -1; // tests: the host withholds the challenge of this round of the tail kernel (its wait then times out: the abort path)
     uint8_t* root_slots = nullptr;        // pinned host memory: roots of asynchronously built Merkle trees in flight
+    uint8_t* later_words = nullptr;       // device memory: the flag and degree words of each deferred check, LATER_WORD_BYTES per pinned slot
     uint64_t root_seq = 0;
     std::vector<int> free_root_slots;
 };
 constexpr int ROOT_SLOTS = 256;
 constexpr size_t ROOT_SLOT_BYTES = 128;   // 64-byte root, then the 8-byte sequence number that says it has landed
+constexpr size_t LATER_WORD_BYTES = 128;  // a deferred check's device words: DEGREE_SLOTS degree words (64 bytes), then the zero-divisor flag
 constexpr long SPIN_POLLS = 40000000;     // ~ tens of milliseconds of polling before the blocking wait
 
 // Frees never wait.  A buffer handed back while a stream may still be using it (the *_dev entries take raw device pointers on
@@ -210,7 +212,7 @@ int ntt_any(const Fe* d_in, Fe* d_out, uint64_t n, Fe root, bool inverse, const 
 int upload(void* d, const void* h, size_t bytes, hipStream_t st);
 int download(void* h, const void* d, size_t bytes, hipStream_t st);
 int pointwise_div_device(const Fe* a, const Fe* b, Fe* out, uint64_t n, hipStream_t st);
-int pointwise_div_enqueue(const Fe* a, const Fe* b, Fe* out, uint64_t n, hipStream_t st, uint32_t** flag_dev);
+int pointwise_div_enqueue(const Fe* a, const Fe* b, Fe* out, uint64_t n, hipStream_t st, uint32_t* flag);
 int gather_device(const Fe* v, const uint64_t* d_idx, uint64_t k, Fe* d_out, hipStream_t st);
 int read_small_polled(const void* d_src, size_t bytes, hipStream_t st, void* host_out);
 

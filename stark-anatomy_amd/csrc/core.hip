@@ -456,7 +456,9 @@ int scratch(int slot, size_t bytes, void** out) {
 
 // The intermediate vector of a multi-pass transform.  One per STREAM: calls on one stream reuse it in stream order (as the shared
 // scratch slot did), calls on different streams -- two independent columns transformed side by side, tools/two_stream_ntt.py -- each
-// have their own, so that sc_ntt_dev / sc_coset_evaluate_dev / sc_coset_divide_dev's transforms may be in flight on several streams at once.
+// have their own, so that sc_ntt_dev / sc_coset_evaluate_dev's transforms may be in flight on several streams at once.  (The coset
+// divisions, sc_coset_divide_dev and sc_coset_divide_later_dev, still keep their operands in the shared scratch slots 1-3: calls of
+// them are ordered on one stream.)
 int ntt_work_buffer(hipStream_t st, size_t bytes, void** out) {
     DevBuf& b = g.ntt_work[st];
     if (b.bytes < bytes) {
@@ -737,26 +739,24 @@ int download(void* h, const void* d, size_t bytes, hipStream_t st) {
     return SC_OK;
 }
 
-// the division only enqueued: *flag_dev (a word of this stream's scratch, valid until the next division on the stream clears it)
-// becomes non-zero if a divisor is zero
-int pointwise_div_enqueue(const Fe* a, const Fe* b, Fe* out, uint64_t n, hipStream_t st, uint32_t** flag_dev) {
-    void* fl;
-    SCCHK(scratch(4, 256, &fl));
-    HIPCHK(hipMemsetAsync(fl, 0, 8, st));
+// the division only enqueued: the caller's word *flag (cleared here, in stream order) becomes non-zero if a divisor is zero
+int pointwise_div_enqueue(const Fe* a, const Fe* b, Fe* out, uint64_t n, hipStream_t st, uint32_t* flag) {
+    HIPCHK(hipMemsetAsync(flag, 0, 8, st));
     static const int K = [] { const char* e = getenv("STARKCORE_DIV_K"); return e && atoi(e) == 8 ? 8 : 16; }();      // (A/B knob)
     const uint64_t threads = (n + K - 1) / K;
     const unsigned blocks = (unsigned)((threads + 255) / 256);
-    if (K == 8) hipLaunchKernelGGL(pointwise_div_kernel<8>, dim3(blocks), dim3(256), 0, st, a, b, out, n, (uint32_t*)fl);
-    else hipLaunchKernelGGL(pointwise_div_kernel<16>, dim3(blocks), dim3(256), 0, st, a, b, out, n, (uint32_t*)fl);
+    if (K == 8) hipLaunchKernelGGL(pointwise_div_kernel<8>, dim3(blocks), dim3(256), 0, st, a, b, out, n, flag);
+    else hipLaunchKernelGGL(pointwise_div_kernel<16>, dim3(blocks), dim3(256), 0, st, a, b, out, n, flag);
     HIPCHK(hipGetLastError());
-    *flag_dev = (uint32_t*)fl;
     return SC_OK;
 }
+// synchronous: the flag is a word of the process-wide scratch slot 4, read back before the call returns
 int pointwise_div_device(const Fe* a, const Fe* b, Fe* out, uint64_t n, hipStream_t st) {
-    uint32_t* fl;
-    SCCHK(pointwise_div_enqueue(a, b, out, n, st, &fl));
+    void* fl;
+    SCCHK(scratch(4, 256, &fl));
+    SCCHK(pointwise_div_enqueue(a, b, out, n, st, (uint32_t*)fl));
     uint64_t hflag = 0;
-    SCCHK(read_small_polled(fl, 8, st, &hflag));                  // (the flag is the low 32 bits of a word of the scratch buffer)
+    SCCHK(read_small_polled(fl, 8, st, &hflag));                  // (the flag is the low 32 bits of the word)
     if ((uint32_t)hflag) return fail(SC_ERR_DIV_ZERO, "divide by zero");
     return SC_OK;
 }
@@ -811,6 +811,16 @@ int read_small_polled(const void* d_src, size_t bytes, hipStream_t st, void* hos
 // (tools/sync_points.py).  The flags travel like the roots of asynchronously built trees -- a one-wave kernel behind the work writes
 // them to a pinned slot, then a sequence number -- and the caller collects them where it has to wait anyway.
 //   words[0] != 0 : a divisor value was zero      words[1] : highest index of a non-zero coefficient above the quotient, -1 if none
+// The pinned slot is reserved BEFORE anything is enqueued (SC_ERR_UNSUPPORTED then leaves every operand as it was: a caller may
+// fall back to the waiting form, in place), and the device words the division and the degree scan write are the slot's own
+// (later_words): a check in flight shares no word with any other call, on any stream.
+static int later_words(int slot, uint32_t** zero_flag, long long** degree_slots) {
+    if (!g.later_words) HIPCHK(hipMalloc((void**)&g.later_words, LATER_WORD_BYTES * ROOT_SLOTS));
+    uint8_t* w = g.later_words + LATER_WORD_BYTES * slot;
+    *degree_slots = (long long*)w;
+    *zero_flag = (uint32_t*)(w + DEGREE_SLOTS * sizeof(long long));
+    return SC_OK;
+}
 __global__ void __launch_bounds__(64) divide_flags_publish_kernel(const uint32_t* __restrict__ zero_flag, const long long* __restrict__ degree_slots,
                                                                  volatile uint64_t* host, uint64_t seq) {
     if (threadIdx.x == 0) {
@@ -822,16 +832,20 @@ __global__ void __launch_bounds__(64) divide_flags_publish_kernel(const uint32_t
         host[8] = seq;
     }
 }
-int divide_flags_later(const uint32_t* zero_flag, const long long* degree_slots, hipStream_t st, sc_later** out) {
-    const int slot = root_slot_get();
-    if (slot < 0) return fail(SC_ERR_UNSUPPORTED, "no pinned slot free for a deferred check");
-    sc_later* h = new sc_later{slot, ++g.root_seq, st};
+// behind the work on `st`: publish the words of the reserved `slot` to its pinned host slot.  Does not free the slot on failure.
+static int divide_flags_later(int slot, const uint32_t* zero_flag, const long long* degree_slots, hipStream_t st, sc_later** out) {
+    const uint64_t seq = ++g.root_seq;
     volatile uint64_t* host = (volatile uint64_t*)(g.root_slots + ROOT_SLOT_BYTES * slot);
-    hipLaunchKernelGGL(divide_flags_publish_kernel, dim3(1), dim3(64), 0, st, zero_flag, degree_slots, host, h->seq);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g.free_root_slots.push_back(slot); delete h; return fail(SC_ERR_HIP, hipGetErrorString(e)); }
-    *out = h;
+    hipLaunchKernelGGL(divide_flags_publish_kernel, dim3(1), dim3(64), 0, st, zero_flag, degree_slots, host, seq);
+    HIPCHK(hipGetLastError());
+    *out = new sc_later{slot, seq, st};
     return SC_OK;
+}
+// a deferred entry that failed after reserving its slot: nothing enqueued may still write the slot's words when it is reused
+static int later_abandon(int slot, hipStream_t st, int rc) {
+    (void)hipStreamSynchronize(st);
+    g.free_root_slots.push_back(slot);
+    return rc;
 }
 int later_wait(sc_later* h, uint64_t words[8]) {
     volatile uint64_t* host = (volatile uint64_t*)(g.root_slots + ROOT_SLOT_BYTES * h->slot);
@@ -900,6 +914,8 @@ int sc_shutdown(void) {
     for (auto& b : g.scratch) { if (b.p) hipFree(b.p); b = DevBuf{}; }
     for (auto& kv : g.ntt_work) if (kv.second.p) hipFree(kv.second.p);
     g.ntt_work.clear();
+    if (g.later_words) hipFree(g.later_words);     // (no check is in flight after the device-wide wait above; re-allocated on the next)
+    g.later_words = nullptr;
     if (g.stream) hipStreamDestroy(g.stream);
     g.stream = nullptr;
     g.seen_streams.clear();
@@ -1435,8 +1451,8 @@ int sc_poly_mul(const void* a, uint64_t na, const void* b, uint64_t nb, const ui
 // ---- coset divide
 // core of fast_coset_divide (code/ntt.py:159-176) on device operands: ALL `order` coefficients of the unscaled interpolant of
 // ntt(scale(a)) / ntt(scale(b)) land in scratch slot 2 (returned in *full)
-// zero_flag_dev != nullptr: the pointwise division is only enqueued and *zero_flag_dev names its "divide by zero" word (deferred check)
-static int coset_divide_core(const Fe* d_a, uint64_t na, const Fe* d_b, uint64_t nb, Fe off, Fe rt, uint64_t order, Fe** full, hipStream_t st, uint32_t** zero_flag_dev = nullptr) {
+// zero_flag != nullptr: the pointwise division is only enqueued, with zero_flag as its "divide by zero" word (deferred check)
+static int coset_divide_core(const Fe* d_a, uint64_t na, const Fe* d_b, uint64_t nb, Fe off, Fe rt, uint64_t order, Fe** full, hipStream_t st, uint32_t* zero_flag = nullptr) {
     void *da, *db, *dc;
     SCCHK(scratch(1, order * sizeof(Fe), &da));
     SCCHK(scratch(2, order * sizeof(Fe), &db));
@@ -1457,7 +1473,7 @@ static int coset_divide_core(const Fe* d_a, uint64_t na, const Fe* d_b, uint64_t
         o.in_limit = nb;
         SCCHK(ntt_device(d_b, (Fe*)db, logn, rt, false, o, st));
     }
-    if (zero_flag_dev) SCCHK(pointwise_div_enqueue((const Fe*)da, (const Fe*)db, (Fe*)dc, order, st, zero_flag_dev));
+    if (zero_flag) SCCHK(pointwise_div_enqueue((const Fe*)da, (const Fe*)db, (Fe*)dc, order, st, zero_flag));
     else SCCHK(pointwise_div_device((const Fe*)da, (const Fe*)db, (Fe*)dc, order, st));
     SCCHK(ntt_device((const Fe*)dc, (Fe*)da, logn, root_inverse(rt, order), true, NttOpts{}, st));
     // unscale by offset^-1 (ntt.py:176)
@@ -1532,28 +1548,40 @@ int sc_coset_divide_later_dev(const void* d_a, uint64_t na, const void* d_b, uin
     Fe rt, off;
     SCCHK(coset_divide_args(na, nb, n_out, offset, root, order, &rt, &off));
     hipStream_t st = pick_stream(stream);
-    Fe* full;
-    uint32_t* zero_flag = nullptr;
-    SCCHK(coset_divide_core((const Fe*)d_a, na, (const Fe*)d_b, nb, off, rt, order, &full, st, &zero_flag));
-    if (n_out) HIPCHK(hipMemcpyAsync(d_out, full, n_out * sizeof(Fe), hipMemcpyDeviceToDevice, st));
-    void* fl;
-    SCCHK(scratch(7, 256, &fl));
-    HIPCHK(hipMemsetAsync(fl, 0xFF, DEGREE_SLOTS * sizeof(long long), st));
-    if (order > n_out) {
-        const uint64_t cnt = order - n_out;
-        hipLaunchKernelGGL(vec_degree_kernel, dim3(degree_blocks(cnt)), dim3(256), 0, st, (const Fe*)full + n_out, cnt, (long long*)fl);
-        HIPCHK(hipGetLastError());
-    }
-    return divide_flags_later(zero_flag, (const long long*)fl, st, later);
+    const int slot = root_slot_get();
+    if (slot < 0) return fail(SC_ERR_UNSUPPORTED, "no pinned slot free for a deferred check (nothing enqueued)");
+    const int rc = [&]() -> int {
+        uint32_t* zero_flag;
+        long long* deg;
+        SCCHK(later_words(slot, &zero_flag, &deg));
+        Fe* full;
+        SCCHK(coset_divide_core((const Fe*)d_a, na, (const Fe*)d_b, nb, off, rt, order, &full, st, zero_flag));
+        if (n_out) HIPCHK(hipMemcpyAsync(d_out, full, n_out * sizeof(Fe), hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemsetAsync(deg, 0xFF, DEGREE_SLOTS * sizeof(long long), st));
+        if (order > n_out) {
+            const uint64_t cnt = order - n_out;
+            hipLaunchKernelGGL(vec_degree_kernel, dim3(degree_blocks(cnt)), dim3(256), 0, st, (const Fe*)full + n_out, cnt, deg);
+            HIPCHK(hipGetLastError());
+        }
+        return divide_flags_later(slot, zero_flag, deg, st, later);
+    }();
+    return rc == SC_OK ? SC_OK : later_abandon(slot, st, rc);
 }
 int sc_pointwise_div_later_dev(const void* d_a, const void* d_b, void* d_out, uint64_t n, sc_later_t** later, void* stream) {
     std::lock_guard<std::mutex> lk(g_mu);
     SCCHK(ensure_init());
     if (!later || !n) return fail(SC_ERR_BAD_ARG, "null argument");
     hipStream_t st = pick_stream(stream);
-    uint32_t* zero_flag = nullptr;
-    SCCHK(pointwise_div_enqueue((const Fe*)d_a, (const Fe*)d_b, (Fe*)d_out, n, st, &zero_flag));
-    return divide_flags_later(zero_flag, nullptr, st, later);
+    const int slot = root_slot_get();
+    if (slot < 0) return fail(SC_ERR_UNSUPPORTED, "no pinned slot free for a deferred check (nothing enqueued)");
+    const int rc = [&]() -> int {
+        uint32_t* zero_flag;
+        long long* deg;
+        SCCHK(later_words(slot, &zero_flag, &deg));
+        SCCHK(pointwise_div_enqueue((const Fe*)d_a, (const Fe*)d_b, (Fe*)d_out, n, st, zero_flag));
+        return divide_flags_later(slot, zero_flag, nullptr, st, later);
+    }();
+    return rc == SC_OK ? SC_OK : later_abandon(slot, st, rc);
 }
 int sc_later_wait(sc_later_t* later, int64_t words_out[8]) {
     std::lock_guard<std::mutex> lk(g_mu);

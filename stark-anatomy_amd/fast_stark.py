@@ -89,6 +89,21 @@ def prefetch_random_polynomial(count, width=17):
         _sc._check(_sc.lib().sc_urandom_prefetch(count, width))
 
 
+def _collect_verdicts(pending):
+    """run every collected check, then raise what the first failing one raised: a check left unread would keep its pinned slot
+    (shared with the asynchronous Merkle roots) for as long as the exception's traceback lives"""
+    checks = iter(pending)
+    try:
+        for verdict in checks:
+            verdict()
+    finally:
+        for verdict in checks:                 # only after a failure: the rest are still waited for, their own verdicts dropped
+            try:
+                verdict()
+            except Exception:                  # noqa: BLE001
+                pass
+
+
 def device_powers(base, count):
     """base^i, i < count, as a DeviceVector (Polynomial.scale of the all-ones vector: no host loop)"""
     ones = DeviceVector.from_bytes((1).to_bytes(16, "little") * count)
@@ -338,8 +353,7 @@ class FastStark:
         commit(randomizer_codeword)
         self._mark("randomizer polynomial: LDE, commitment")
 
-        for verdict in pending or ():                    # the collected checks: the device has long decided them
-            verdict()
+        _collect_verdicts(pending or ())                 # the collected checks: the device has long decided them
         # Fiat-Shamir weights: 1 randomizer + 2 per transition quotient + 2 per boundary quotient
         weights = self.sample_weights(1 + 2 * len(transition_quotients) + 2 * len(boundary_quotients), proof_stream.prover_fiat_shamir())
         tq_bounds = self.transition_quotient_degree_bounds(transition_constraints)
