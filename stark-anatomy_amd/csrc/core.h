@@ -77,13 +77,10 @@ struct PlanTables {      // power tables of one root of order n = 2^logn
     Fe* tl = nullptr;
     Fe* th = nullptr;
     Fe* th_ninv = nullptr;   // th * n^-1 (built on first inverse use)
-    // direct four-step twiddle tables per column pass for the plan's digit split, [0]: plain, [1]: first pass scaled by n^-1
-    Fe* twd[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};
-    int twd_digits[4] = {0, 0, 0, 0};
-    int twd_passes = 0;
-    // direct inter-pass table of the two-pass BATCHED plans of this length (first digit twd_b_digit0)
-    Fe* twd_b = nullptr;
-    int twd_b_digit0 = 0;
+    // direct four-step twiddle tables built so far (direct_twiddles), one per (logA, logR, scaled) of ntt_plan.h's DirectTable:
+    // the column passes of plain and batched plans of every digit split share them
+    struct Direct { int logA, logR; bool scaled; Fe* d; };
+    std::vector<Direct> direct;
     uint64_t last_use = 0;   // lookup tick (eviction order; see evict_tables)
 };
 struct OuterKey {        // direct outer-twiddle table of one rank's slab (multi-GPU column stage)
@@ -196,13 +193,18 @@ void pool_clear();
 hipEvent_t event_get();
 int fail(int code, const std::string& msg);
 int ensure_init();
-int scratch(int slot, size_t bytes, void** out);
-int ntt_work_buffer(hipStream_t st, size_t bytes, void** out);
+int grow_buffer(DevBuf& b, size_t bytes, void** out);
+inline int scratch(int slot, size_t bytes, void** out) { return grow_buffer(g.scratch[slot], bytes, out); }
 int check_root(Fe root, uint64_t n);
 int build_pow_table(Fe** out, uint64_t count, Fe base_m, uint64_t step, Fe scale_m, hipStream_t st);
 void free_plans();
 int evict_outer_tables();
 int get_plan(Fe root, int logn, bool need_ninv, hipStream_t st, PlanTables** out);
+inline NttTables tables_of(const PlanTables& t) {
+    NttTables tb;
+    tb.mt = t.mt; tb.mt_log = t.mt_log; tb.tl = t.tl; tb.th = t.th;
+    return tb;
+}
 int get_pow(Fe base, uint64_t count, hipStream_t st, PowTables** out);
 int plan_batched_direct(NttPlanDesc& d, BatchKind kind, int loglen, int logbatch, PlanTables* pt, const Fe* in, Fe* work, Fe* out, BatchExtras ex, hipStream_t st, bool* ok);
 int run_plan(NttPlanDesc& d, hipStream_t st);

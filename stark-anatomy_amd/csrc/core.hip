@@ -442,25 +442,8 @@ int ensure_init() {
     return SC_OK;
 }
 
-int scratch(int slot, size_t bytes, void** out) {
-    DevBuf& b = g.scratch[slot];
-    if (b.bytes < bytes) {
-        if (b.p) { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipFree(b.p)); b.p = nullptr; b.bytes = 0; }
-        size_t want = bytes < (1u << 20) ? (1u << 20) : bytes;
-        HIPCHK(hipMalloc(&b.p, want));
-        b.bytes = want;
-    }
-    *out = b.p;
-    return SC_OK;
-}
-
-// The intermediate vector of a multi-pass transform.  One per STREAM: calls on one stream reuse it in stream order (as the shared
-// scratch slot did), calls on different streams -- two independent columns transformed side by side, tools/two_stream_ntt.py -- each
-// have their own, so that sc_ntt_dev / sc_coset_evaluate_dev's transforms may be in flight on several streams at once.  (The coset
-// divisions, sc_coset_divide_dev and sc_coset_divide_later_dev, still keep their operands in the shared scratch slots 1-3: calls of
-// them are ordered on one stream.)
-int ntt_work_buffer(hipStream_t st, size_t bytes, void** out) {
-    DevBuf& b = g.ntt_work[st];
+// a buffer kept for reuse (a scratch slot, a stream's transform work buffer): grown to at least `bytes` (1 MiB at the least)
+int grow_buffer(DevBuf& b, size_t bytes, void** out) {
     if (b.bytes < bytes) {
         if (b.p) { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipFree(b.p)); b.p = nullptr; b.bytes = 0; }
         size_t want = bytes < (1u << 20) ? (1u << 20) : bytes;
@@ -495,8 +478,7 @@ int build_pow_table(Fe** out, uint64_t count, Fe base_m, uint64_t step, Fe scale
 void free_plan_tables(PlanTables& t) {
     hipFree(t.mt); hipFree(t.tl); hipFree(t.th);
     if (t.th_ninv) hipFree(t.th_ninv);
-    for (int v = 0; v < 2; ++v) for (int i = 0; i < 4; ++i) if (t.twd[v][i]) hipFree(t.twd[v][i]);
-    if (t.twd_b) hipFree(t.twd_b);
+    for (const PlanTables::Direct& e : t.direct) hipFree(e.d);
 }
 
 void free_plans() {
@@ -540,18 +522,19 @@ int get_plan(Fe root, int logn, bool need_ninv, hipStream_t st, PlanTables** out
         SCCHK(evict_tables(g.plans, PLAN_CAP, free_plan_tables));
         const uint64_t n = 1ull << logn;
         Fe rm = to_mont(root);
+        const TableSizes sz = table_sizes(logn);
         PlanTables t;
-        t.mt_log = logn < 12 ? logn : 12;
-        SCCHK(build_pow_table(&t.mt, 1ull << (t.mt_log - 1), rm, n >> t.mt_log, fe_mont_one(), st));
-        SCCHK(build_pow_table(&t.tl, n < 4096 ? n : 4096, rm, 1, fe_mont_one(), st));
-        SCCHK(build_pow_table(&t.th, n > 4096 ? n >> 12 : 1, rm, 4096, fe_mont_one(), st));
+        t.mt_log = sz.mt_log;
+        SCCHK(build_pow_table(&t.mt, sz.mt, rm, n >> sz.mt_log, fe_mont_one(), st));
+        SCCHK(build_pow_table(&t.tl, sz.tl, rm, 1, fe_mont_one(), st));
+        SCCHK(build_pow_table(&t.th, sz.th, rm, 4096, fe_mont_one(), st));
         it = g.plans.emplace(key, t).first;
         built = true;
     }
     if (need_ninv && !it->second.th_ninv) {
         const uint64_t n = 1ull << logn;
         Fe ninv_m = mont_inv(to_mont(Fe{n, 0}));
-        SCCHK(build_pow_table(&it->second.th_ninv, n > 4096 ? n >> 12 : 1, to_mont(root), 4096, ninv_m, st));
+        SCCHK(build_pow_table(&it->second.th_ninv, table_sizes(logn).th, to_mont(root), 4096, ninv_m, st));
         built = true;
     }
     if (built) HIPCHK(hipStreamSynchronize(st));   // tables are shared across streams afterwards
@@ -582,27 +565,34 @@ int get_pow(Fe base, uint64_t count, hipStream_t st, PowTables** out) {
     return SC_OK;
 }
 
-// plan a batched transform; two-pass plans get the direct inter-pass twiddle table (built once per (root, length, split))
+// The direct twiddle table of column pass i of plan d (one coalesced load + one modmul per element instead of the two-level
+// lookup's two loads + two modmuls), built on first use and kept with the root's tables; nullptr for a table of more than
+// 2^direct_tw_max_log entries (it would cost more HBM than it saves).  `scaled`: d is an inverse transform scaled by n^-1.
+int direct_twiddles(PlanTables* pt, const NttPlanDesc& d, int i, bool scaled, hipStream_t st, const Fe** out) {
+    const DirectTable t = direct_table(d, i, scaled);
+    *out = nullptr;
+    if (t.logR + t.logB > g.tuning.direct_tw_max_log) return SC_OK;
+    for (const PlanTables::Direct& e : pt->direct)
+        if (e.logA == t.logA && e.logR == t.logR && e.scaled == t.scaled) { *out = e.d; return SC_OK; }
+    const uint64_t count = 1ull << (t.logR + t.logB);
+    Fe* p;
+    HIPCHK(hipMalloc((void**)&p, count * sizeof(Fe)));
+    pt->direct.push_back({t.logA, t.logR, t.scaled, p});
+    hipLaunchKernelGGL(twiddle_table_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, p, t.logB, count, 1ull << t.logA,
+                       pt->tl, t.scaled ? pt->th_ninv : pt->th);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));   // tables are shared across streams afterwards
+    *out = p;
+    return SC_OK;
+}
+
+// plan a batched transform; two-pass plans get the direct inter-pass twiddle table
 int plan_batched_direct(NttPlanDesc& d, BatchKind kind, int loglen, int logbatch, PlanTables* pt, const Fe* in, Fe* work, Fe* out, BatchExtras ex, hipStream_t st, bool* ok) {
-    NttTables tb;
-    tb.mt = pt->mt; tb.mt_log = pt->mt_log; tb.tl = pt->tl; tb.th = pt->th;
+    const NttTables tb = tables_of(*pt);
     *ok = plan_batched(d, kind, loglen, logbatch, tb, in, work, out, g.tuning, ex);
-    if (!*ok || d.npasses != 2 || loglen > g.tuning.direct_tw_max_log || g.tuning.direct_tw_max_log <= 0) return SC_OK;
-    if (pt->twd_b && pt->twd_b_digit0 != d.digits[0]) {
-        HIPCHK(hipDeviceSynchronize());
-        hipFree(pt->twd_b);
-        pt->twd_b = nullptr;
-    }
-    if (!pt->twd_b) {
-        const uint64_t count = 1ull << loglen;
-        HIPCHK(hipMalloc((void**)&pt->twd_b, count * sizeof(Fe)));
-        hipLaunchKernelGGL(twiddle_table_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, pt->twd_b, loglen - d.digits[0], count, (uint64_t)1, pt->tl, pt->th);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(st));
-        pt->twd_b_digit0 = d.digits[0];
-    }
-    ex.inner_twd = pt->twd_b;
-    *ok = plan_batched(d, kind, loglen, logbatch, tb, in, work, out, g.tuning, ex);
+    if (!*ok || d.npasses != 2) return SC_OK;
+    SCCHK(direct_twiddles(pt, d, 0, false, st, &ex.inner_twd));
+    if (ex.inner_twd) *ok = plan_batched(d, kind, loglen, logbatch, tb, in, work, out, g.tuning, ex);
     return SC_OK;
 }
 
@@ -624,7 +614,7 @@ void launch_pass(const NttPassDesc& pd, hipStream_t st) {
                 else SC_LAUNCH_FIXED(LR, LC, false, false);                       \
                 return;                                                           \
             }
-            SC_FIXED(8, 3) SC_FIXED(7, 4) SC_FIXED(10, 2) SC_FIXED(6, 5) SC_FIXED(9, 3) SC_FIXED(8, 4)
+            SC_FIXED4_SHAPES(SC_FIXED)
 #undef SC_FIXED
         }
     }
@@ -632,7 +622,7 @@ void launch_pass(const NttPassDesc& pd, hipStream_t st) {
         if (g.fixed_shapes && !pd.p.trace && !pd.p.blk_enable && fixed_offsets_fit(pd.p)) {
             const int lr = pd.p.logR, lc = pd.p.logC;
 #define SC_FIXED8(LR, LC) if (lr == LR && lc == LC) { hipLaunchKernelGGL((ntt_pass_kernel_fixed8<LR, LC>), dim3(pd.ntiles * pd.cols), dim3(pd.threads), pd.lds_bytes, st, pd.p, pd.ntiles, remap, g.wave_local); return; }
-            SC_FIXED8(10, 2) SC_FIXED8(9, 3) SC_FIXED8(8, 4)
+            SC_FIXED8_SHAPES(SC_FIXED8)
 #undef SC_FIXED8
         }
     }
@@ -667,50 +657,22 @@ int ntt_device(const Fe* d_in, Fe* d_out, int logn, Fe root, bool inverse_scale,
     SCCHK(get_plan(root, logn, inverse_scale, st, &pt));
     const uint64_t n = 1ull << logn;
     const int m = plan_num_passes(logn, g.tuning);
-    NttTables tb;
-    tb.mt = pt->mt; tb.mt_log = pt->mt_log; tb.tl = pt->tl; tb.th = pt->th;
+    NttTables tb = tables_of(*pt);
     tb.th_scaled = (inverse_scale && m > 1) ? pt->th_ninv : nullptr;
     NttIo io;
     io.in = d_in; io.out = d_out; io.in_limit = o.in_limit; io.cols = o.cols; io.col_stride_in = o.col_stride_in;
-    if (m > 1) { void* w; SCCHK(ntt_work_buffer(st, n * o.cols * sizeof(Fe), &w)); io.work = (Fe*)w; }
+    if (m > 1) { void* w; SCCHK(grow_buffer(g.ntt_work[st], n * o.cols * sizeof(Fe), &w)); io.work = (Fe*)w; }
     if (o.coset) { io.ol = o.coset->lo; io.oh = o.coset->hi; }
     if (inverse_scale && m == 1) { io.scale_last = true; io.scale = mont_inv(to_mont(Fe{n, 0})); }
     NttPlanDesc d;
     if (!plan_ntt(d, logn, tb, io, g.tuning)) return fail(SC_ERR_UNSUPPORTED, "unsupported transform length");
-    if (d.npasses > 1 && g.tuning.direct_tw_max_log > 0) {   // tables bigger than the cap fall back to the two-level lookup
-        // direct twiddle tables (one coalesced load + one modmul per element instead of two loads + two modmuls);
-        // keyed by the digit split, rebuilt if the tuning changed it
-        bool same = pt->twd_passes == d.npasses;
-        for (int i = 0; same && i < d.npasses; ++i) same = pt->twd_digits[i] == d.digits[i];
-        if (!same) {
-            HIPCHK(hipDeviceSynchronize());
-            for (int v = 0; v < 2; ++v) for (int i = 0; i < 4; ++i) if (pt->twd[v][i]) { hipFree(pt->twd[v][i]); pt->twd[v][i] = nullptr; }
-            pt->twd_passes = d.npasses;
-            for (int i = 0; i < 4; ++i) pt->twd_digits[i] = (i < d.npasses) ? d.digits[i] : 0;
-        }
-        const int variant = inverse_scale ? 1 : 0;
-        bool built = false;
-        int logA = 0;
+    if (d.npasses > 1) {
+        bool any = false;
         for (int i = 0; i + 1 < d.npasses; ++i) {
-            const int logR = d.digits[i], logB = logn - logA - logR;
-            const int logcount = logR + logB;
-            const bool scaled = (variant == 1 && i == 0);
-            Fe*& slot = pt->twd[scaled ? 1 : 0][i];
-            if (logcount <= g.tuning.direct_tw_max_log) {
-                if (!slot) {
-                    const uint64_t count = 1ull << logcount;
-                    HIPCHK(hipMalloc((void**)&slot, count * sizeof(Fe)));
-                    hipLaunchKernelGGL(twiddle_table_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, slot, logB, count, 1ull << logA,
-                                       pt->tl, scaled ? pt->th_ninv : pt->th);
-                    HIPCHK(hipGetLastError());
-                    built = true;
-                }
-                tb.twd[i] = slot;
-            }
-            logA += logR;
+            SCCHK(direct_twiddles(pt, d, i, inverse_scale, st, &tb.twd[i]));
+            any |= tb.twd[i] != nullptr;
         }
-        if (built) HIPCHK(hipStreamSynchronize(st));
-        if (!plan_ntt(d, logn, tb, io, g.tuning)) return fail(SC_ERR_UNSUPPORTED, "unsupported transform length");
+        if (any && !plan_ntt(d, logn, tb, io, g.tuning)) return fail(SC_ERR_UNSUPPORTED, "unsupported transform length");
     }
     return run_plan(d, st);
 }

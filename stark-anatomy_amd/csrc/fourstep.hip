@@ -60,8 +60,6 @@ static int batch_call(const BatchCall& c, hipStream_t st, int* npasses_out = nul
     const int loglen = ilog2(len), logbatch = ilog2(batch);
     PlanTables* pt;
     SCCHK(get_plan(rt, loglen, false, st, &pt));
-    NttTables tb;
-    tb.mt = pt->mt; tb.mt_log = pt->mt_log; tb.tl = pt->tl; tb.th = pt->th;
     BatchExtras ex;
     ex.chunks_log = ilog2(chunks);
     ex.chunk_stride = c.chunk_stride;
@@ -106,7 +104,6 @@ static int batch_call(const BatchCall& c, hipStream_t st, int* npasses_out = nul
         }
         // get_plan may have rehashed the map: re-fetch the inner tables
         SCCHK(get_plan(rt, loglen, false, st, &pt));
-        tb.mt = pt->mt; tb.mt_log = pt->mt_log; tb.tl = pt->tl; tb.th = pt->th;
     }
     Fe* work = c.work;
     if (!work) { void* w; SCCHK(scratch(0, len * batch * sizeof(Fe), &w)); work = (Fe*)w; }
@@ -277,9 +274,6 @@ static int rccl_exchange(const sc_fourstep* p, int dirn, const Fe* send, Fe* rec
     return SC_OK;
 }
 
-// passes of a batched plan of this length (mirrors plan_batched: one pass up to the digit cap, two above)
-static int batched_passes(int loglen) { return loglen <= (g.tuning.max_digit_log < 0 ? 8 : g.tuning.max_digit_log) ? 1 : 2; }
-
 static int fourstep_cols(const sc_fourstep* p, int dirn, const Fe* src, Fe* send, Fe* recv_diag, hipStream_t st) {
     const sc_fourstep::Dir& d = p->dir[dirn];
     const uint64_t G = (uint64_t)p->world, rw = d.R / G, cw = d.C / G;
@@ -306,7 +300,7 @@ static int fourstep_rows(const sc_fourstep* p, int dirn, const Fe* recv, Fe* dst
     c.work = (Fe*)w + q * rk * d.C;
     c.roots_checked = true;
     // (a single-pass plan has nothing to defer: its one pass is the transposing one)
-    if (defer && batched_passes(ilog2(d.C)) == 2) { c.pass_lo = 0; c.pass_hi = 1; }
+    if (defer && plan_batched_passes(ilog2(d.C), g.tuning) == 2) { c.pass_lo = 0; c.pass_hi = 1; }
     return batch_call(c, st);
 }
 
@@ -389,7 +383,7 @@ int sc_fourstep_rows_finish_dev(const sc_fourstep_t* plan, int inverse, void* d_
     SCCHK(ensure_init());
     if (!plan || !d_dst) return fail(SC_ERR_BAD_ARG, "null argument");
     const sc_fourstep::Dir& d = plan->dir[inverse ? 1 : 0];
-    if (batched_passes(ilog2(d.C)) == 1) return SC_OK;     // single-pass rows: nothing was deferred
+    if (plan_batched_passes(ilog2(d.C), g.tuning) == 1) return SC_OK;     // single-pass rows: nothing was deferred
     return fourstep_rows_finish(plan, inverse ? 1 : 0, (Fe*)d_dst, pick_stream(stream));
 }
 
@@ -645,7 +639,7 @@ int sc_fourstep_run_dev(const sc_fourstep_t* plan, int inverse, const void* d_sr
         HIPCHK(hipStreamWaitEvent(st, g_comm_events[1 + q], 0));
         SCCHK(fourstep_rows(plan, dirn, recv, (Fe*)d_dst, q, K, defer_last_pass != 0, st));
     }
-    if (defer_last_pass && batched_passes(ilog2(d.C)) == 2) SCCHK(fourstep_rows_finish(plan, dirn, (Fe*)d_dst, st));
+    if (defer_last_pass && plan_batched_passes(ilog2(d.C), g.tuning) == 2) SCCHK(fourstep_rows_finish(plan, dirn, (Fe*)d_dst, st));
     return SC_OK;
 }
 

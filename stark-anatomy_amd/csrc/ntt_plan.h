@@ -91,6 +91,110 @@ inline int plan_num_passes(int logn, const NttTuning& tu_in) {
     return m < 2 ? 2 : m;
 }
 
+// ---- table geometry and the direct four-step twiddle tables, shared by the library (core.hip) and the emulator (tests/emu)
+
+// sizes of the power tables of a root w of order n = 2^logn (NttTables): mt[e] = w^(e * n / 2^mt_log), e < mt; tl[e] = w^e,
+// e < tl; th[h] = w^(4096 h), h < th
+struct TableSizes {
+    int mt_log;
+    uint64_t mt, tl, th;
+};
+inline TableSizes table_sizes(int logn) {
+    const int mt_log = logn < 12 ? logn : 12;
+    return {mt_log, 1ull << (mt_log - 1), logn < 12 ? 1ull << logn : 4096ull, logn > 12 ? 1ull << (logn - 12) : 1ull};
+}
+
+// The direct table of the four-step twiddles of column pass i of a plan (PassParams::twd, NttTables::twd[i], BatchExtras::
+// inner_twd): 2^(logR + logB) entries, entry k * 2^logB + b = w^(b * k * 2^logA), w the plan's root; `scaled`: times n^-1 (the
+// first pass of an inverse transform, built from th * n^-1).  Its contents depend on (logA, logR, scaled) once n is fixed.
+struct DirectTable {
+    int logA, logR, logB;
+    bool scaled;
+};
+inline DirectTable direct_table(const NttPlanDesc& d, int i, bool inverse_scaled) {
+    int logA = 0;
+    for (int j = 0; j < i; ++j) logA += d.digits[j];
+    return {logA, d.digits[i], d.logn - logA - d.digits[i], inverse_scaled && i == 0};
+}
+// entry q, from the two-level tables tl and th (th * n^-1 for a scaled table); twiddle_table_kernel computes the same
+inline Fe direct_table_entry(const DirectTable& t, const Fe* tl, const Fe* th, uint64_t q) {
+    const uint64_t k = q >> t.logB, b = q & ((1ull << t.logB) - 1);
+    return pow2level(tl, th, b * k * (1ull << t.logA));
+}
+
+// ---- pieces of a pass descriptor shared by plan_ntt and plan_batched
+
+// digits as even as possible, the larger ones first
+inline void split_digits(NttPlanDesc& d, int logn, int m) {
+    for (int i = 0; i < 4; ++i) d.digits[i] = i < m ? logn / m + (i < logn % m ? 1 : 0) : 0;
+}
+
+// LDS tile cap: shrunk (never below 4 columns of the widest digit) until a pass has at least 2^min_tiles_log tiles
+inline int shrink_tile_cap(const NttTuning& tu, int maxdigit, int logtotal) {
+    const int floor_log = maxdigit + 2 < tu.max_tile_log ? maxdigit + 2 : tu.max_tile_log;
+    int tile_cap = tu.max_tile_log;
+    while (tile_cap > floor_log && logtotal - tile_cap < tu.min_tiles_log) --tile_cap;
+    return tile_cap;
+}
+
+// columns per tile: as many as fit the tile cap, at most 2^limit and 2^max_col_log
+inline int clamp_logC(int tile_cap, int logR, int limit, const NttTuning& tu) {
+    int logC = tile_cap - logR;
+    if (logC > limit) logC = limit;
+    if (logC > tu.max_col_log) logC = tu.max_col_log;
+    return logC < 0 ? 0 : logC;
+}
+
+// a fresh pass of digit logR from `in` to `out` with the butterfly and two-level twiddle tables of tb
+inline void pass_common(PassParams& p, int logR, const Fe* in, Fe* out, const NttTables& tb) {
+    p = PassParams{};
+    p.logR = logR;
+    p.in = in;
+    p.out = out;
+    p.mt = tb.mt;
+    p.mt_shift = tb.mt_log - logR;
+    p.tl = tb.tl;
+    p.th = tb.th;
+    p.in_limit = ~0ull;
+}
+
+// Column pass on [A][R][B][batch], in place: a length-R transform over the R axis for every (a, b, batch column), then the
+// four-step twiddle w^(A * b * k) (b = column index >> logbatch), from the direct table twd when there is one.  A tile = all R
+// rows x C adjacent columns; t_lo = column block, t_mid = a.
+inline void column_pass(NttPassDesc& pd, int logA, int logR, int logB, int logbatch, int tile_cap, const NttTuning& tu, const Fe* twd) {
+    PassParams& p = pd.p;
+    const int logBB = logB + logbatch;
+    p.logC = clamp_logC(tile_cap, logR, logBB, tu);
+    p.lo_log = logBB - p.logC;
+    p.mid_log = logA;
+    p.in_lo = p.out_lo = 1ull << p.logC;
+    p.in_mid = p.out_mid = 1ull << (logR + logBB);
+    p.in_rs = p.out_rs = 1ull << logBB;
+    p.in_cs = p.out_cs = 1;
+    p.tw_enable = 1;
+    p.tw_col_shift = logbatch;
+    p.tw_scale = 1ull << logA;
+    p.tw_row_k = 1;
+    if (twd) { p.twd = twd; p.twd_stride = 1ull << logB; }
+    pd.ntiles = (uint32_t)(1ull << (logA + logBB - p.logC));
+}
+
+// elements per thread (from `loge` up, as the thread count demands), threads and LDS bytes of a pass; false if no kernel fits.
+// A transposing pass loads r-fast and stores c-fast: it needs at least two rounds.
+inline bool pass_launch(NttPassDesc& pd, int loge, bool transposing) {
+    const int logT = pd.p.logR + pd.p.logC;
+    if (loge > logT) loge = logT;
+    // threads per workgroup: <= 1024 (loge 1,2), 512 (loge 3), 256 (loge 4) -- matches the kernels' launch bounds
+    while (logT - loge > (loge >= 4 ? 8 : (loge == 3 ? 9 : 10))) ++loge;
+    if (loge > 4) return false;
+    if (transposing && pd.p.logR <= loge) loge = pd.p.logR - 1;
+    if (loge < 1) return false;
+    pd.loge = loge;
+    pd.threads = 1u << (logT - loge);
+    pd.lds_bytes = ((uint32_t)sizeof(Fe) << logT) + tile_twiddle_bytes(pd.p.logR);   // the tile, then its twiddles
+    return true;
+}
+
 // Fill the pass descriptors for a length-2^logn transform.  Returns false if unsupported.
 inline bool plan_ntt(NttPlanDesc& d, int logn, const NttTables& tb, const NttIo& io, const NttTuning& tu_in) {
     if (logn < 1 || logn > 32) return false;
@@ -109,77 +213,35 @@ inline bool plan_ntt(NttPlanDesc& d, int logn, const NttTables& tb, const NttIo&
         if (tu_in.max_col_log < 0) tu.max_col_log = 6;
     }
     d.npasses = m;
-    {
-        int base = logn / m, extra = logn % m;
-        for (int i = 0; i < m; ++i) d.digits[i] = base + (i < extra ? 1 : 0);
-    }
+    split_digits(d, logn, m);
     const uint64_t n = 1ull << logn;
-    int tile_cap = tu.max_tile_log;
-    {
-        int maxdigit = 0;
-        for (int i = 0; i < m; ++i) maxdigit = d.digits[i] > maxdigit ? d.digits[i] : maxdigit;
-        const int floor_log = maxdigit + 2 < tu.max_tile_log ? maxdigit + 2 : tu.max_tile_log;    // keep >= 4 columns per tile
-        while (tile_cap > floor_log && logn + cols_log - tile_cap < tu.min_tiles_log && m > 1) --tile_cap;
-    }
+    const int tile_cap = shrink_tile_cap(tu, d.digits[0], logn + cols_log);
 
     int logA = 0;                         // log2 of the product of the digits already transformed
     for (int i = 0; i < m; ++i) {
         NttPassDesc& pd = d.pass[i];
         PassParams& p = pd.p;
-        p = PassParams{};
         const int logR = d.digits[i];
         const int logB = logn - logA - logR;
         const bool lastp = (i == m - 1);
-        p.logR = logR;
-        p.in = (i == 0) ? io.in : io.work;
-        p.out = lastp ? io.out : io.work;
-        p.mt = tb.mt;
-        p.mt_shift = tb.mt_log - logR;
-        p.tl = tb.tl;
-        p.th = (i == 0 && tb.th_scaled) ? tb.th_scaled : tb.th;
-        p.in_limit = (i == 0) ? io.in_limit : ~0ull;
+        pass_common(p, logR, i == 0 ? io.in : io.work, lastp ? io.out : io.work, tb);
+        if (i == 0 && tb.th_scaled) p.th = tb.th_scaled;
+        if (i == 0) p.in_limit = io.in_limit;
         p.coset_enable = (i == 0 && io.ol != nullptr) ? 1 : 0;
         p.ol = io.ol;
         p.oh = io.oh;
         p.scale_enable = (lastp && io.scale_last) ? 1 : 0;
         p.scale = io.scale;
         if (m == 1) {
-            p.logC = 0;
-            p.lo_log = 0; p.mid_log = 0;
-            p.in_rs = 1; p.out_rs = 1;
-            p.in_cs = 0; p.out_cs = 0;
-            p.rfast_load = 0;
-            p.tw_enable = 0;
+            p.in_rs = p.out_rs = 1;
             pd.ntiles = 1;
         } else if (!lastp) {
-            // column pass on [A][R][B]
-            int logC = tile_cap - logR;
-            if (logC > logB) logC = logB;
-            if (logC > tu.max_col_log) logC = tu.max_col_log;
-            if (logC < 0) logC = 0;
-            p.logC = logC;
-            p.lo_log = logB - logC;       // t_lo = column block, t_mid = a
-            p.mid_log = logA;
-            p.in_lo = p.out_lo = 1ull << logC;
-            p.in_mid = p.out_mid = 1ull << (logR + logB);
-            p.in_hi = p.out_hi = 0;
-            p.in_rs = p.out_rs = 1ull << logB;
-            p.in_cs = p.out_cs = 1;
-            p.rfast_load = 0;
-            p.tw_enable = 1;
-            p.tw_scale = 1ull << logA;
-            p.tw_row_k = 1;
-            p.twd = tb.twd[i];
+            column_pass(pd, logA, logR, logB, 0, tile_cap, tu, tb.twd[i]);
             p.twd_stride = 1ull << logB;
-            pd.ntiles = (uint32_t)(n >> (logR + logC));
         } else {
             // transposing pass: memory [k_1][k_2]..[k_{m-1}][j_m] -> natural k = k_1 + N_1 k_2 + ... ; C adjacent k_1 per tile
             const int logN1 = d.digits[0];
-            int logC = tile_cap - logR;
-            if (logC > logN1) logC = logN1;
-            if (logC > tu.max_col_log) logC = tu.max_col_log;
-            if (logC < 0) logC = 0;
-            p.logC = logC;
+            p.logC = clamp_logC(tile_cap, logR, logN1, tu);
             // tile id -> (t_hi = k_1 block, t_mid = k_2, t_lo = k_3); for m == 2 there is no k_2/k_3, for m == 3 no k_3
             const int logN2 = (m >= 3) ? d.digits[1] : 0;
             const int logN3 = (m >= 4) ? d.digits[2] : 0;
@@ -187,30 +249,20 @@ inline bool plan_ntt(NttPlanDesc& d, int logn, const NttTables& tb, const NttIo&
             p.mid_log = logN2;
             p.in_rs = 1;
             p.in_cs = n >> logN1;                              // next k_1
-            p.in_hi = (n >> logN1) << logC;
+            p.in_hi = (n >> logN1) << p.logC;
             p.in_mid = 1ull << (logR + logN3);                  // next k_2
             p.in_lo = 1ull << logR;                             // next k_3
             p.out_cs = 1;
-            p.out_hi = 1ull << logC;
+            p.out_hi = 1ull << p.logC;
             p.out_mid = 1ull << logN1;
             p.out_lo = 1ull << (logN1 + logN2);
             p.out_rs = n >> logR;                               // k_m is the most significant output digit
             p.rfast_load = 1;
-            p.tw_enable = 0;
-            pd.ntiles = (uint32_t)(n >> (logR + logC));
+            pd.ntiles = (uint32_t)(n >> (logR + p.logC));
         }
-        int loge = tu.loge;
-        const int logT = p.logR + p.logC;
-        if (io.cols > 1 && loge == 2 && tu.loge_cols == 3 && logT == 12 && (p.logR == 10 || p.logR == 9 || p.logR == 8)) loge = 3;
-        if (loge > logT) loge = logT;
-        // threads per workgroup: <= 1024 (loge 1,2), 512 (loge 3), 256 (loge 4) -- matches the kernels' launch bounds
-        while (logT - loge > (loge >= 4 ? 8 : (loge == 3 ? 9 : 10))) ++loge;
-        if (loge > 4) return false;
-        if (lastp && m > 1 && p.logR <= loge) loge = p.logR - 1;   // transposing pass needs >= 2 rounds (load r-fast, store c-fast)
-        if (loge < 1) return false;
-        pd.loge = loge;
-        pd.threads = 1u << (logT - loge);
-        pd.lds_bytes = ((uint32_t)sizeof(Fe) << logT) + tile_twiddle_bytes(pd.p.logR);   // the tile, then its twiddles
+        const bool wide = p.logR + p.logC == 12 && (p.logR == 10 || p.logR == 9 || p.logR == 8);
+        const int loge = (io.cols > 1 && tu.loge == 2 && tu.loge_cols == 3 && wide) ? 3 : tu.loge;
+        if (!pass_launch(pd, loge, lastp && m > 1)) return false;
         pd.cols = io.cols;
         if (io.cols > 1) {
             p.col_enable = 1;
@@ -240,14 +292,13 @@ inline bool plan_ntt(NttPlanDesc& d, int logn, const NttTables& tb, const NttIo&
         // it with the same addresses as its data
         int logAi = 0;
         for (int i = 0; i + 1 < m; ++i) {
-            const int logR = d.digits[i], logB = logn - logAi - logR;
             if (tb.twd[i]) {
                 d.pass[i].p.tw_enable = 0;
                 d.pass[i].p.twd = nullptr;
                 d.pass[i + 1].p.twd_in = tb.twd[i];
-                d.pass[i + 1].p.twd_in_mask = (1ull << (logR + logB)) - 1;
+                d.pass[i + 1].p.twd_in_mask = (1ull << (logn - logAi)) - 1;
             }
-            logAi += logR;
+            logAi += d.digits[i];
         }
     }
     return true;
@@ -295,66 +346,49 @@ struct BatchExtras {
     uint32_t block_rows = 0;
 };
 
+// passes of a batched plan of length 2^loglen: one up to the digit cap, two above
+inline int plan_batched_passes(int loglen, const NttTuning& tu) {
+    return loglen <= (tu.max_digit_log < 0 ? 8 : tu.max_digit_log) ? 1 : 2;
+}
+
+// BATCH_ROWS_T with chunks_log > 0: the rows of a pass lie in 2^chunks_log chunks (stride chunk_stride, default the chunks of
+// this call back to back); false if a chunk boundary falls inside a row of the pass
+inline bool chunked_rows(PassParams& p, const BatchExtras& ex, int logR, uint64_t len, int logbatch) {
+    if (ex.chunks_log > logR) return false;
+    const uint64_t cs = ex.chunk_stride ? ex.chunk_stride : (len >> ex.chunks_log) << logbatch;     // next chunk
+    if (ex.chunks_log == logR) p.in_rs = cs;          // every row of this pass is a chunk of its own
+    else { p.in_split = logR - ex.chunks_log; p.in_rs_hi = cs; }
+    return true;
+}
+
 inline bool plan_batched(NttPlanDesc& d, BatchKind kind, int loglen, int logbatch, const NttTables& tb,
                          const Fe* in, Fe* work, Fe* out, const NttTuning& tu_in, const BatchExtras& ex = BatchExtras()) {
     if (loglen < 1 || loglen + logbatch > 34) return false;
-    NttTuning tu = resolve_tuning(tu_in, 24);
-    if (tu_in.max_digit_log < 0) tu.max_digit_log = 8;
-    const int m = (loglen <= tu.max_digit_log) ? 1 : 2;
+    const NttTuning tu = resolve_tuning(tu_in, 24);
+    const int m = plan_batched_passes(loglen, tu);
     if (loglen > 2 * tu.max_digit_log + 2) return false;
     d.logn = loglen;
     d.npasses = m;
-    d.digits[0] = (m == 1) ? loglen : (loglen + 1) / 2;
-    d.digits[1] = loglen - d.digits[0];
-    int tile_cap = tu.max_tile_log;
-    {
-        const int floor_log = d.digits[0] + 2 < tu.max_tile_log ? d.digits[0] + 2 : tu.max_tile_log;
-        while (tile_cap > floor_log && loglen + logbatch - tile_cap < tu.min_tiles_log) --tile_cap;
-    }
+    split_digits(d, loglen, m);
+    const int tile_cap = shrink_tile_cap(tu, d.digits[0], loglen + logbatch);
     const uint64_t len = 1ull << loglen, batch = 1ull << logbatch;
     for (int i = 0; i < m; ++i) {
         NttPassDesc& pd = d.pass[i];
         PassParams& p = pd.p;
-        p = PassParams{};
         const int logR = d.digits[i];
         const bool lastp = (i == m - 1);
         const int logA = (i == 0) ? 0 : d.digits[0];
-        p.logR = logR;
-        p.in = (i == 0) ? in : work;
-        p.out = lastp ? out : work;
-        p.mt = tb.mt;
-        p.mt_shift = tb.mt_log - logR;
-        p.tl = tb.tl;
-        p.th = tb.th;
-        p.in_limit = ~0ull;
+        pass_common(p, logR, i == 0 ? in : work, lastp ? out : work, tb);
         if (kind == BATCH_COLS) {
-            // [A][R][Blow * batch]: column pass; the last pass writes rows in natural order k = a + A*k_m
-            const int logBlow = loglen - logA - logR;       // untransformed lower digits of the transform axis
-            const int logB = logBlow + logbatch;
-            int logC = tile_cap - logR;
-            if (logC > logB) logC = logB;
-            if (logC > tu.max_col_log) logC = tu.max_col_log;
-            if (logC < 0) logC = 0;
-            p.logC = logC;
-            p.lo_log = logB - logC;
-            p.mid_log = logA;
-            p.in_lo = p.out_lo = 1ull << logC;
-            p.in_mid = 1ull << (logR + logB);
-            p.in_rs = 1ull << logB;
-            p.in_cs = p.out_cs = 1;
-            if (lastp && m == 2) {
-                p.out_mid = batch;                              // a = k_1 -> row k_1
-                p.out_rs = batch << logA;                       // k_2 -> row N_1 * k_2
-            } else {
-                p.out_mid = p.in_mid;
-                p.out_rs = p.in_rs;
+            // [A][R][Blow][batch]: column pass; the last pass writes rows in natural order k = a + A*k_m
+            column_pass(pd, logA, logR, loglen - logA - logR, logbatch, tile_cap, tu, lastp ? nullptr : ex.inner_twd);
+            if (lastp) {
+                p.tw_enable = 0;
+                if (m == 2) {
+                    p.out_mid = batch;                          // a = k_1 -> row k_1
+                    p.out_rs = batch << logA;                   // k_2 -> row N_1 * k_2
+                }
             }
-            p.rfast_load = 0;
-            p.tw_enable = lastp ? 0 : 1;
-            p.tw_col_shift = logbatch;
-            p.tw_scale = 1ull << logA;
-            p.tw_row_k = 1;
-            if (!lastp && ex.inner_twd) { p.twd = ex.inner_twd; p.twd_stride = 1ull << logBlow; }
             if (lastp && ex.outer_tl) {
                 // fused outer twiddle: natural output row = t_mid + N_1 * k (two passes) or k (one pass); column = local column
                 p.tw_enable = 1;
@@ -384,76 +418,40 @@ inline bool plan_batched(NttPlanDesc& d, BatchKind kind, int loglen, int logbatc
                 for (uint64_t h = 0; h < nblk; ++h)
                     p.out_blk[h] = ex.block_out ? ex.block_out[h] : (h == ex.diag_lo / rows ? ex.diag_out : p.out);
             }
-            pd.ntiles = (uint32_t)((len * batch) >> (logR + logC));
         } else if (!lastp) {
-            // rows, first digit: [batch][R][B = N_2]: t_lo = column block, t_mid = (none), t_hi = batch row
-            const int logB = loglen - logR;
-            int logC = tile_cap - logR;
-            if (logC > logB) logC = logB;
-            if (logC > tu.max_col_log) logC = tu.max_col_log;
-            if (logC < 0) logC = 0;
-            p.logC = logC;
-            p.lo_log = logB - logC;
-            p.mid_log = 0;
-            p.in_lo = p.out_lo = 1ull << logC;
+            // rows, first digit: the column pass of one row [R][B = N_2], repeated over the batch rows as t_hi
+            column_pass(pd, 0, logR, loglen - logR, 0, tile_cap, tu, ex.inner_twd);
+            p.in_mid = p.out_mid = 0;
             p.in_hi = p.out_hi = len;
-            p.in_rs = p.out_rs = 1ull << logB;
-            p.in_cs = p.out_cs = 1;
+            pd.ntiles = (uint32_t)((len * batch) >> (logR + p.logC));
             if (ex.chunks_log) {
                 // element (b, j) of the row sits at chunk (j / cw), row b, offset (j % cw), cw = len / chunks
-                if (ex.chunks_log > logR) return false;           // chunk boundaries must fall on whole rows of this pass
-                const uint64_t cs = ex.chunk_stride ? ex.chunk_stride : (len >> ex.chunks_log) << logbatch;     // next chunk
+                if (!chunked_rows(p, ex, logR, len, logbatch)) return false;
                 p.in_hi = len >> ex.chunks_log;                   // next batch row inside a chunk
-                if (ex.chunks_log == logR) p.in_rs = cs;          // every row of this pass is a chunk of its own
-                else { p.in_split = logR - ex.chunks_log; p.in_rs_hi = cs; }
             }
-            p.rfast_load = 0;
-            p.tw_enable = 1;
-            p.tw_scale = 1;
-            p.tw_row_k = 1;
-            if (ex.inner_twd) { p.twd = ex.inner_twd; p.twd_stride = 1ull << logB; }
-            pd.ntiles = (uint32_t)((len * batch) >> (logR + logC));
         } else {
             // rows, last digit: C adjacent batch rows x R contiguous; output [k][batch row], k = k_1 + N_1 * k_2
-            int logC = tile_cap - logR;
-            if (logC > logbatch) logC = logbatch;
-            if (logC > tu.max_col_log) logC = tu.max_col_log;
-            if (logC < 0) logC = 0;
-            p.logC = logC;
-            p.lo_log = 0;
+            p.logC = clamp_logC(tile_cap, logR, logbatch, tu);
             p.mid_log = logA;                                   // t_mid = k_1 (absent when m == 1)
             p.in_rs = 1;
             p.in_cs = len;
-            p.in_hi = len << logC;
+            p.in_hi = len << p.logC;
             p.in_mid = 1ull << logR;
             if (ex.chunks_log && m == 1) {
                 // single (transposing) pass straight from the chunked layout
-                if (ex.chunks_log > logR) return false;
-                const uint64_t cs = ex.chunk_stride ? ex.chunk_stride : (len >> ex.chunks_log) << logbatch;
+                if (!chunked_rows(p, ex, logR, len, logbatch)) return false;
                 p.in_cs = len >> ex.chunks_log;
-                p.in_hi = (len >> ex.chunks_log) << logC;
-                if (ex.chunks_log == logR) p.in_rs = cs;          // one element per chunk
-                else { p.in_split = logR - ex.chunks_log; p.in_rs_hi = cs; }
+                p.in_hi = (len >> ex.chunks_log) << p.logC;
             }
             const uint64_t ld = ex.out_ld ? ex.out_ld : batch;
             p.out_cs = 1;
-            p.out_hi = 1ull << logC;
+            p.out_hi = 1ull << p.logC;
             p.out_mid = ld;
             p.out_rs = ld << logA;
             p.rfast_load = 1;
-            p.tw_enable = 0;
-            pd.ntiles = (uint32_t)((len * batch) >> (logR + logC));
+            pd.ntiles = (uint32_t)((len * batch) >> (logR + p.logC));
         }
-        int loge = tu.loge;
-        const int logT = p.logR + p.logC;
-        if (loge > logT) loge = logT;
-        while (logT - loge > (loge >= 4 ? 8 : (loge == 3 ? 9 : 10))) ++loge;
-        if (loge > 4) return false;
-        if (kind == BATCH_ROWS_T && lastp && p.logR <= loge) loge = p.logR - 1;
-        if (loge < 1) return false;
-        pd.loge = loge;
-        pd.threads = 1u << (logT - loge);
-        pd.lds_bytes = ((uint32_t)sizeof(Fe) << logT) + tile_twiddle_bytes(pd.p.logR);   // the tile, then its twiddles
+        if (!pass_launch(pd, tu.loge, kind == BATCH_ROWS_T && lastp)) return false;
     }
     return true;
 }

@@ -559,6 +559,11 @@ SC_HD void tile_twiddles_to_lds(const PassParams& P, int logR, uint32_t tid, uin
 //     [SH - LOGE + GLC, SH + GLC) (derivation in DESIGN.md 3.1): once SH + GLC <= 6 every later exchange stays inside
 //     one 64-lane wave, each wave owns a closed set of LDS rows, and the workgroup barrier is replaced by a wave-level
 //     fence -- the waves of a workgroup then drift apart and overlap each other's LDS traffic, arithmetic and stores.
+//
+// The tile shapes (logR, logC) that have such instantiations, in instantiation order: four elements per thread
+// (ntt_pass_kernel_fixed) and eight (ntt_pass_kernel_fixed8).  core.hip's launch_pass and the emulator dispatch over these lists.
+#define SC_FIXED4_SHAPES(X) X(8, 3) X(7, 4) X(10, 2) X(6, 5) X(9, 3) X(8, 4)
+#define SC_FIXED8_SHAPES(X) X(10, 2) X(9, 3) X(8, 4)
 template <int LOGE, int GLR, int GLC, int ROUND = 0, bool ALT = false>
 struct FixedRounds {
     static constexpr int E = 1 << LOGE;

@@ -15,6 +15,27 @@ static void fill_table(std::vector<Fe>& t, uint64_t count, Fe base_m, uint64_t s
     for (uint64_t i = 0; i < count; ++i) t[i] = pow_table_entry(base_m, i, step, scale_m);
 }
 
+// the library's power tables of a root of order 2^logn (core.hip get_plan), th * scale as th_scaled
+struct RootTables {
+    std::vector<Fe> mt, tl, th, ths;
+    NttTables tb;
+    RootTables(Fe r_m, int logn, Fe scale_m = fe_mont_one()) {
+        const TableSizes sz = table_sizes(logn);
+        fill_table(mt, sz.mt, r_m, (1ull << logn) >> sz.mt_log, fe_mont_one());
+        fill_table(tl, sz.tl, r_m, 1, fe_mont_one());
+        fill_table(th, sz.th, r_m, 4096, fe_mont_one());
+        fill_table(ths, sz.th, r_m, 4096, scale_m);
+        tb.mt = mt.data(); tb.mt_log = sz.mt_log; tb.tl = tl.data(); tb.th = th.data();
+    }
+};
+
+// the library's direct twiddle table of column pass i of plan d (core.hip direct_twiddles)
+static void fill_direct(std::vector<Fe>& t, const NttPlanDesc& d, int i, bool inverse_scaled, const RootTables& rt) {
+    const DirectTable dt = direct_table(d, i, inverse_scaled);
+    t.resize(1ull << (dt.logR + dt.logB));
+    for (uint64_t q = 0; q < t.size(); ++q) t[q] = direct_table_entry(dt, rt.tl.data(), dt.scaled ? rt.ths.data() : rt.th.data(), q);
+}
+
 // geometry-specialised path (FixedRounds): on the CPU each round must finish for all threads before the next starts,
 // so the per-round bodies are invoked directly with the same compile-time schedule the kernel unrolls
 template <int LOGE, int GLR, int GLC, int ROUND = 0>
@@ -32,29 +53,33 @@ static void run_pass(const NttPassDesc& pd) {
     if (lds.size() < ((size_t)1 << (P.logR + P.logC)) + (P.logR > 0 ? ((size_t)1 << (P.logR - 1)) : 0)) abort();
     Fe* tw = lds.data() + ((size_t)1 << (P.logR + P.logC));
     for (uint32_t tid = 0; tid < pd.threads; ++tid) tile_twiddles_to_lds(P, P.logR, tid, pd.threads, tw);
-    if constexpr (LOGE == 2) {
-#define EMU_FIXED(LR, LC)                                                                                   \
-        if (P.logR == LR && P.logC == LC) {                                                                 \
-            for (uint32_t tile = 0; tile < pd.ntiles * pd.cols; ++tile) run_fixed_rounds<2, LR, LC>(pd, tile, lds.data(), tw); \
-            return;                                                                                         \
-        }
-        EMU_FIXED(8, 3) EMU_FIXED(7, 4) EMU_FIXED(10, 2) EMU_FIXED(6, 5) EMU_FIXED(9, 3) EMU_FIXED(8, 4)
-#undef EMU_FIXED
+#define RUN_FIXED(LR, LC)                                                                                   \
+    if (P.logR == LR && P.logC == LC) {                                                                     \
+        for (uint32_t tile = 0; tile < pd.ntiles * pd.cols; ++tile) run_fixed_rounds<LOGE, LR, LC>(pd, tile, lds.data(), tw); \
+        return;                                                                                             \
     }
-    if constexpr (LOGE == 3) {          // the batches' eight-elements-per-thread kernels (ntt_pass_kernel_fixed8)
-#define EMU_FIXED8(LR, LC)                                                                                  \
-        if (P.logR == LR && P.logC == LC) {                                                                 \
-            for (uint32_t tile = 0; tile < pd.ntiles * pd.cols; ++tile) run_fixed_rounds<3, LR, LC>(pd, tile, lds.data(), tw); \
-            return;                                                                                         \
-        }
-        EMU_FIXED8(10, 2) EMU_FIXED8(9, 3) EMU_FIXED8(8, 4)
-#undef EMU_FIXED8
-    }
+    if constexpr (LOGE == 2) { SC_FIXED4_SHAPES(RUN_FIXED) }
+    if constexpr (LOGE == 3) { SC_FIXED8_SHAPES(RUN_FIXED) }          // the batches' eight-elements-per-thread kernels (ntt_pass_kernel_fixed8)
+#undef RUN_FIXED
     RoundSched rs = make_rounds(P.logR, LOGE);
     for (uint32_t tile = 0; tile < pd.ntiles * pd.cols; ++tile)
         for (int r = 0; r < rs.nrounds; ++r)
             for (uint32_t tid = 0; tid < pd.threads; ++tid)
                 ntt_round_dispatch<LOGE>(P, rs.s[r], rs.sh[r], r == 0, tile, tid, lds.data(), tw);
+}
+
+// passes [lo, hi) of a plan; the plan's pass count, or -2 for a pass no kernel serves
+static int run_plan(const NttPlanDesc& d, int lo = 0, int hi = 4) {
+    for (int i = lo; i < d.npasses && i < hi; ++i) {
+        switch (d.pass[i].loge) {
+            case 1: run_pass<1>(d.pass[i]); break;
+            case 2: run_pass<2>(d.pass[i]); break;
+            case 3: run_pass<3>(d.pass[i]); break;
+            case 4: run_pass<4>(d.pass[i]); break;
+            default: return -2;
+        }
+    }
+    return d.npasses;
 }
 
 extern "C" int emu_ntt(const uint64_t* in, uint64_t* out, int logn, const uint64_t* root, int inverse, uint64_t in_limit,
@@ -72,14 +97,10 @@ extern "C" int emu_ntt(const uint64_t* in, uint64_t* out, int logn, const uint64
     tu.min_tiles_log = min_tiles_log; tu.max_col_log = max_col_log; tu.max_digit_log = max_digit_log;
     tu.tw_on_load = (direct_tw != 2) ? 1 : 0;      // direct_tw: 0 = two-level lookup, 1 = direct tables applied on load by the next pass, 2 = direct tables at the store
     const int m = plan_num_passes(logn, tu);
-    NttTables tb;
-    std::vector<Fe> mt, tl, th, ths, ol, oh;
-    tb.mt_log = logn < 12 ? logn : 12;
-    fill_table(mt, 1ull << (tb.mt_log - 1), r_m, n >> tb.mt_log, fe_mont_one());
-    fill_table(tl, n < 4096 ? n : 4096, r_m, 1, fe_mont_one());
-    fill_table(th, n > 4096 ? n >> 12 : 1, r_m, 4096, fe_mont_one());
-    fill_table(ths, n > 4096 ? n >> 12 : 1, r_m, 4096, scale_m);
-    tb.mt = mt.data(); tb.tl = tl.data(); tb.th = th.data(); tb.th_scaled = (inverse && m > 1) ? ths.data() : nullptr;
+    const RootTables rt(r_m, logn, scale_m);
+    NttTables tb = rt.tb;
+    tb.th_scaled = (inverse && m > 1) ? rt.ths.data() : nullptr;
+    std::vector<Fe> ol, oh;
     std::vector<Fe> work(n);
     NttIo io;
     io.in = (const Fe*)in; io.work = work.data(); io.out = (Fe*)out;
@@ -97,31 +118,13 @@ extern "C" int emu_ntt(const uint64_t* in, uint64_t* out, int logn, const uint64
     if (!plan_ntt(d, logn, tb, io, tu)) return -1;
     std::vector<Fe> twd[4];
     if (direct_tw && d.npasses > 1) {
-        int logA = 0;
         for (int i = 0; i + 1 < d.npasses; ++i) {
-            const int logR = d.digits[i], logB = logn - logA - logR;
-            const uint64_t count = 1ull << (logR + logB);
-            twd[i].resize(count);
-            const Fe* thp = (i == 0 && tb.th_scaled) ? tb.th_scaled : tb.th;
-            for (uint64_t q = 0; q < count; ++q) {
-                uint64_t k = q >> logB, b = q & ((1ull << logB) - 1);
-                twd[i][q] = pow2level(tb.tl, thp, b * k * (1ull << logA));
-            }
+            fill_direct(twd[i], d, i, tb.th_scaled != nullptr, rt);
             tb.twd[i] = twd[i].data();
-            logA += logR;
         }
         if (!plan_ntt(d, logn, tb, io, tu)) return -1;
     }
-    for (int i = 0; i < d.npasses; ++i) {
-        switch (d.pass[i].loge) {
-            case 1: run_pass<1>(d.pass[i]); break;
-            case 2: run_pass<2>(d.pass[i]); break;
-            case 3: run_pass<3>(d.pass[i]); break;
-            case 4: run_pass<4>(d.pass[i]); break;
-            default: return -2;
-        }
-    }
-    return d.npasses;
+    return run_plan(d);
 }
 
 // `cols` independent transforms in one set of launches (NttIo::cols, sc_ntt_columns_dev): in / out are [cols][n]
@@ -143,14 +146,9 @@ static int emu_columns_impl(const uint64_t* in, uint64_t* out, int logn, int col
     }
     NttTuning tu;
     const int m = plan_num_passes(logn, tu);
-    NttTables tb;
-    std::vector<Fe> mt, tl, th, ths;
-    tb.mt_log = logn < 12 ? logn : 12;
-    fill_table(mt, 1ull << (tb.mt_log - 1), r_m, n >> tb.mt_log, fe_mont_one());
-    fill_table(tl, n < 4096 ? n : 4096, r_m, 1, fe_mont_one());
-    fill_table(th, n > 4096 ? n >> 12 : 1, r_m, 4096, fe_mont_one());
-    fill_table(ths, n > 4096 ? n >> 12 : 1, r_m, 4096, scale_m);
-    tb.mt = mt.data(); tb.tl = tl.data(); tb.th = th.data(); tb.th_scaled = (inverse && m > 1) ? ths.data() : nullptr;
+    const RootTables rt(r_m, logn, scale_m);
+    NttTables tb = rt.tb;
+    tb.th_scaled = (inverse && m > 1) ? rt.ths.data() : nullptr;
     std::vector<Fe> work(n * cols);
     NttIo io;
     io.in = (const Fe*)in; io.work = work.data(); io.out = (Fe*)out;
@@ -170,31 +168,13 @@ static int emu_columns_impl(const uint64_t* in, uint64_t* out, int logn, int col
     if (!plan_ntt(d, logn, tb, io, tu)) return -1;
     std::vector<Fe> twd[4];
     if (direct_tw && d.npasses > 1) {
-        int logA = 0;
         for (int i = 0; i + 1 < d.npasses; ++i) {
-            const int logR = d.digits[i], logB = logn - logA - logR;
-            const uint64_t count = 1ull << (logR + logB);
-            twd[i].resize(count);
-            const Fe* thp = (i == 0 && tb.th_scaled) ? tb.th_scaled : tb.th;
-            for (uint64_t q = 0; q < count; ++q) {
-                uint64_t k = q >> logB, b = q & ((1ull << logB) - 1);
-                twd[i][q] = pow2level(tb.tl, thp, b * k * (1ull << logA));
-            }
+            fill_direct(twd[i], d, i, tb.th_scaled != nullptr, rt);
             tb.twd[i] = twd[i].data();
-            logA += logR;
         }
         if (!plan_ntt(d, logn, tb, io, tu)) return -1;
     }
-    for (int i = 0; i < d.npasses; ++i) {
-        switch (d.pass[i].loge) {
-            case 1: run_pass<1>(d.pass[i]); break;
-            case 2: run_pass<2>(d.pass[i]); break;
-            case 3: run_pass<3>(d.pass[i]); break;
-            case 4: run_pass<4>(d.pass[i]); break;
-            default: return -2;
-        }
-    }
-    return d.npasses;
+    return run_plan(d);
 }
 
 extern "C" void emu_field(const uint64_t* a, const uint64_t* b, uint64_t* out /* 7 x 2 limbs */) {
@@ -222,13 +202,8 @@ static int emu_batched_impl(const uint64_t* in, uint64_t* out, int kind, int log
     Fe r_m = to_mont(Fe{root[0], root[1]});
     NttTuning tu;
     tu.max_tile_log = max_tile_log; tu.loge = loge; tu.min_tiles_log = min_tiles_log; tu.max_col_log = max_col_log; tu.max_digit_log = max_digit_log;
-    NttTables tb;
-    std::vector<Fe> mt, tl, th;
-    tb.mt_log = loglen < 12 ? loglen : 12;
-    fill_table(mt, 1ull << (tb.mt_log - 1), r_m, len >> tb.mt_log, fe_mont_one());
-    fill_table(tl, len < 4096 ? len : 4096, r_m, 1, fe_mont_one());
-    fill_table(th, len > 4096 ? len >> 12 : 1, r_m, 4096, fe_mont_one());
-    tb.mt = mt.data(); tb.tl = tl.data(); tb.th = th.data();
+    const RootTables rt(r_m, loglen);
+    const NttTables& tb = rt.tb;
     std::vector<Fe> work_own(xx.work ? 0 : len * batch);
     Fe* work_p = xx.work ? (Fe*)xx.work : work_own.data();
     BatchExtras ex;
@@ -243,8 +218,8 @@ static int emu_batched_impl(const uint64_t* in, uint64_t* out, int kind, int log
         Fe o_m = to_mont(Fe{outer_root[0], outer_root[1]});
         const uint64_t on = 1ull << outer_logorder;
         Fe sc_m = outer_ninv ? mont_inv(to_mont(Fe{on, 0})) : fe_mont_one();
-        fill_table(otl, on < 4096 ? on : 4096, o_m, 1, fe_mont_one());
-        fill_table(oth, on > 4096 ? on >> 12 : 1, o_m, 4096, sc_m);
+        fill_table(otl, table_sizes(outer_logorder).tl, o_m, 1, fe_mont_one());
+        fill_table(oth, table_sizes(outer_logorder).th, o_m, 4096, sc_m);
         ex.outer_tl = otl.data(); ex.outer_th = oth.data(); ex.outer_col_base = outer_col_base;
         if (inner_direct & 2) {
             // the library's direct outer table (outer_table_kernel): [r][c] = w^(r * (col_base + c)) [* order^-1]
@@ -257,24 +232,11 @@ static int emu_batched_impl(const uint64_t* in, uint64_t* out, int kind, int log
     if (!plan_batched(d, kind == 0 ? BATCH_COLS : BATCH_ROWS_T, loglen, logbatch, tb, (const Fe*)in, work_p, (Fe*)out, tu, ex)) return -1;
     std::vector<Fe> itw;
     if ((inner_direct & 1) && d.npasses == 2) {
-        // the library's direct inter-pass table (twiddle_table_kernel): [k][b] = w^(b*k), B = len >> digits[0]
-        const int logB = loglen - d.digits[0];
-        itw.resize(len);
-        for (uint64_t i = 0; i < len; ++i) itw[i] = pow2level(tb.tl, tb.th, (i & ((1ull << logB) - 1)) * (i >> logB));
+        fill_direct(itw, d, 0, false, rt);
         ex.inner_twd = itw.data();
         if (!plan_batched(d, kind == 0 ? BATCH_COLS : BATCH_ROWS_T, loglen, logbatch, tb, (const Fe*)in, work_p, (Fe*)out, tu, ex)) return -1;
     }
-    for (int i = 0; i < d.npasses; ++i) {
-        if (i < xx.pass_lo || i >= xx.pass_hi) continue;
-        switch (d.pass[i].loge) {
-            case 1: run_pass<1>(d.pass[i]); break;
-            case 2: run_pass<2>(d.pass[i]); break;
-            case 3: run_pass<3>(d.pass[i]); break;
-            case 4: run_pass<4>(d.pass[i]); break;
-            default: return -2;
-        }
-    }
-    return d.npasses;
+    return run_plan(d, xx.pass_lo, xx.pass_hi);
 }
 
 // the stages of sc_fourstep_* on one rank's buffers (csrc/fourstep.hip: fourstep_cols / fourstep_rows / fourstep_rows_finish)

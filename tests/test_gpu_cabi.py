@@ -149,7 +149,7 @@ def test_coset_evaluate_columns_vs_oracle(sc, logn, cols, m):
 
 def test_transforms_in_flight_on_two_streams(sc):
     """Two independent columns transformed side by side (one per HIP stream, many times over, never waiting in between): every
-    multi-pass transform keeps its intermediate vector in a buffer of ITS stream (csrc/core.hip ntt_work_buffer), so the results are
+    multi-pass transform keeps its intermediate vector in a buffer of ITS stream (csrc/core.hip: Ctx::ntt_work), so the results are
     the oracle's whatever the interleaving -- with one shared work buffer the two transforms overwrite each other's passes
     (tools/two_stream_ntt.py found it).  Sizes with two and three passes, forward, inverse and an LDE."""
     import torch
