@@ -599,18 +599,16 @@ int plan_batched_direct(NttPlanDesc& d, BatchKind kind, int loglen, int logbatch
 template <int LOGE>
 void launch_pass(const NttPassDesc& pd, hipStream_t st) {
     int remap = (g.xcd_remap && pd.ntiles >= 16 && (pd.ntiles & 7u) == 0) ? 1 : 0;
+    const PassKernel k = pass_kernel(pd, g.fixed_shapes != 0);     // (ntt_plan.h: which instantiation, and why)
     if constexpr (LOGE == 2) {
-        // hot shapes of the default plans get geometry-specialised instantiations
-        if (g.fixed_shapes) {
+        if (k.kind == PK_FIXED4) {
             const int lr = pd.p.logR, lc = pd.p.logC;
 #define SC_LAUNCH_FIXED(LR, LC, TR, ALT) \
     hipLaunchKernelGGL((ntt_pass_kernel_fixed<2, LR, LC, TR, ALT>), dim3(pd.ntiles * pd.cols), dim3(pd.threads), pd.lds_bytes, st, pd.p, pd.ntiles, remap, g.wave_local)
-            // (a launch with a second destination -- the column stage of the sharded transform -- has its own instantiation; it
-            // is never traced: the generic kernel serves that combination)
 #define SC_FIXED(LR, LC)                                                          \
-            if (lr == LR && lc == LC && !(pd.p.trace && pd.p.blk_enable)) {          \
-                if (pd.p.trace) SC_LAUNCH_FIXED(LR, LC, true, false);             \
-                else if (pd.p.blk_enable) SC_LAUNCH_FIXED(LR, LC, false, true);      \
+            if (lr == LR && lc == LC) {                                           \
+                if (k.trace) SC_LAUNCH_FIXED(LR, LC, true, false);                \
+                else if (k.alt) SC_LAUNCH_FIXED(LR, LC, false, true);             \
                 else SC_LAUNCH_FIXED(LR, LC, false, false);                       \
                 return;                                                           \
             }
@@ -619,7 +617,7 @@ void launch_pass(const NttPassDesc& pd, hipStream_t st) {
         }
     }
     if constexpr (LOGE == 3) {
-        if (g.fixed_shapes && !pd.p.trace && !pd.p.blk_enable && fixed_offsets_fit(pd.p)) {
+        if (k.kind == PK_FIXED8) {
             const int lr = pd.p.logR, lc = pd.p.logC;
 #define SC_FIXED8(LR, LC) if (lr == LR && lc == LC) { hipLaunchKernelGGL((ntt_pass_kernel_fixed8<LR, LC>), dim3(pd.ntiles * pd.cols), dim3(pd.threads), pd.lds_bytes, st, pd.p, pd.ntiles, remap, g.wave_local); return; }
             SC_FIXED8_SHAPES(SC_FIXED8)
@@ -632,10 +630,7 @@ void launch_pass(const NttPassDesc& pd, hipStream_t st) {
 int run_plan(NttPlanDesc& d, hipStream_t st) {
     size_t trace_off = 0;    // diagnostics: pass i writes its stamps behind those of the passes before it
     for (int i = 0; i < d.npasses; ++i) {
-        const uint32_t grid = d.pass[i].ntiles * d.pass[i].cols;
-        d.pass[i].p.prio_balance = g.prio_balance >= 0 ? g.prio_balance
-                                 : grid <= (uint32_t)g.num_cus ? 1
-                                 : grid >= ((d.pass[i].p.logR == 10 && d.pass[i].p.logC == 2) ? 2u : 8u) * (uint32_t)g.num_cus ? 2 : 0;
+        d.pass[i].p.prio_balance = pass_prio_balance(d.pass[i], g.prio_balance, g.num_cus);
         d.pass[i].p.trace = g.trace ? g.trace + trace_off : nullptr;
         trace_off += (size_t)d.pass[i].ntiles * d.pass[i].cols * (d.pass[i].threads >> 6) * TRACE_STAMPS;
         switch (d.pass[i].loge) {
@@ -651,7 +646,8 @@ int run_plan(NttPlanDesc& d, hipStream_t st) {
 }
 
 // core transform on device pointers; root already validated.  forward: out = NTT_root(in); inverse handled by caller
-// passing root^-1 and inverse=true (adds the n^-1 scaling).
+// passing root^-1 and inverse=true (adds the n^-1 scaling).  tests/emu/kernel_cover.cpp (plan_ntt_call) plans like this function:
+// keep the two in step.
 int ntt_device(const Fe* d_in, Fe* d_out, int logn, Fe root, bool inverse_scale, const NttOpts& o, hipStream_t st) {
     PlanTables* pt;
     SCCHK(get_plan(root, logn, inverse_scale, st, &pt));

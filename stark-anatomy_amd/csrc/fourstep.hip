@@ -45,7 +45,8 @@ struct BatchCall {
     bool roots_checked = false;      // the caller has validated the roots already (a cached plan object)
 };
 
-// caller holds g_mu and has run ensure_init()
+// caller holds g_mu and has run ensure_init().  tests/emu/kernel_cover.cpp (plan_batch_call) plans like this function, and
+// tests/ntt_grid.py (_sharded_plans) issues the calls of fourstep_cols / fourstep_rows / fourstep_rows_finish below: keep them in step.
 static int batch_call(const BatchCall& c, hipStream_t st, int* npasses_out = nullptr) {
     const uint64_t len = c.len, batch = c.batch;
     const int kind = c.kind;

@@ -456,4 +456,43 @@ inline bool plan_batched(NttPlanDesc& d, BatchKind kind, int loglen, int logbatc
     return true;
 }
 
+// ---- which pass kernel a launch takes: core.hip's launch_pass and run_plan, and tests/emu/kernel_cover.cpp, which reports it
+// for the GPU test grid (tests/ntt_grid.py)
+
+enum PassKernelKind { PK_GENERIC = 0, PK_FIXED4 = 1, PK_FIXED8 = 2 };
+struct PassKernel {
+    int kind;             // PassKernelKind: ntt_pass_kernel<loge>, ntt_pass_kernel_fixed<2, logR, logC, trace, alt>, ntt_pass_kernel_fixed8<logR, logC>
+    bool trace, alt;      // (fixed4 only)
+};
+inline bool fixed4_shape(int lr, int lc) {
+#define SC_IS_SHAPE(LR, LC) if (lr == LR && lc == LC) return true;
+    SC_FIXED4_SHAPES(SC_IS_SHAPE)
+    return false;
+}
+inline bool fixed8_shape(int lr, int lc) {
+    SC_FIXED8_SHAPES(SC_IS_SHAPE)
+#undef SC_IS_SHAPE
+    return false;
+}
+// Hot shapes of the default plans get geometry-specialised instantiations.  A launch with a second destination (the column stage
+// of the sharded transform) has its own four-element instantiation; it is never traced: the generic kernel serves that
+// combination.  The eight-element ones take neither, and only launches whose lane byte offsets stay below 2^32.
+inline PassKernel pass_kernel(const NttPassDesc& pd, bool fixed_shapes) {
+    const PassParams& p = pd.p;
+    if (fixed_shapes && pd.loge == 2 && fixed4_shape(p.logR, p.logC) && !(p.trace && p.blk_enable))
+        return {PK_FIXED4, p.trace != nullptr, p.blk_enable != 0};
+    if (fixed_shapes && pd.loge == 3 && !p.trace && !p.blk_enable && fixed_offsets_fit(p) && fixed8_shape(p.logR, p.logC))
+        return {PK_FIXED8, false, false};
+    return {PK_GENERIC, false, false};
+}
+
+// PassParams::prio_balance of a launch: `forced` (>= 0) or by grid size -- 1 for at most one workgroup per CU, 2 for long grids
+// (>= 8 workgroups per CU; >= 2 of 2^10 x 4 tiles), else 0
+inline int pass_prio_balance(const NttPassDesc& pd, int forced, int num_cus) {
+    const uint32_t grid = pd.ntiles * pd.cols;
+    return forced >= 0 ? forced
+         : grid <= (uint32_t)num_cus ? 1
+         : grid >= ((pd.p.logR == 10 && pd.p.logC == 2) ? 2u : 8u) * (uint32_t)num_cus ? 2 : 0;
+}
+
 }  // namespace sc

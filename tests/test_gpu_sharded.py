@@ -25,17 +25,18 @@ def sc():
     return starkcore
 
 
-def _simulate(sc, log2n, world, seed, fused=True, blocks=1, defer=True, diag_in_place=True):
+def _simulate(sc, log2n, world, seed, fused=True, blocks=1, defer=True, diag_in_place=True, log_n1=None):
     """fused: the ranks' stage objects (sc_fourstep_*: column stage with the outer twiddle and, with diag_in_place, the rank's own
     block written straight into its receive buffer; row stage reading the [G][R/G][C/G] layout in place, optionally in `blocks`
-    row blocks with the second pass deferred); otherwise the primitive-by-primitive path (separate twiddle and reassembly)."""
+    row blocks with the second pass deferred); otherwise the primitive-by-primitive path (separate twiddle and reassembly).
+    log_n1: the split n = n1 * n2 (None: the library's).  (Also the sharded stages of tests/test_gpu_ntt_grid.py.)"""
     from sharded import ShardedNtt
     dev = torch.device("cuda", 0)
     n = 1 << log2n
     root = po.primitive_nth_root(n)
     stream = torch.cuda.Stream(device=dev)
     with torch.cuda.stream(stream):
-        engs = [ShardedNtt(log2n, root, r, world, dev) for r in range(world)]
+        engs = [ShardedNtt(log2n, root, r, world, dev, log_n1=log_n1) for r in range(world)]
         xs = [e.synthetic_input(seed) for e in engs]
         n1, n2 = engs[0].n1, engs[0].n2
 
