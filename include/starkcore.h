@@ -61,10 +61,11 @@ int sc_stream(void** stream_out);
 int sc_stream_join(void* other_stream);
 /* tuning knobs for experiments (defaults are the measured optimum; -1 = choose by size where applicable): key in
  * {"max_tile_log","loge","max_col_log","min_tiles_log","single_pass_max_log","max_digit_log","direct_tw_max_log",
- *  "xcd_remap","fixed_shapes","merkle_big_nlev","wave_local","prio_balance","loge_cols","tw_on_load","prune","fri_tail","fri_tail_stall","small_divisor_direct"}.  Plans are re-derived on the next
+ *  "xcd_remap","fixed_shapes","merkle_big_nlev","wave_local","prio_balance","loge_cols","tw_on_load","prune","fri_tail","fri_tail_stall","small_divisor_direct","verify_stage_kb"}.  Plans are re-derived on the next
  * call; results never depend on the tuning ("fri_tail_stall" = k >= 0 is a test hook: the host withholds the challenge after round k of
  * the persistent tail kernel, whose wait then gives up after 2^13 polls; -1 = off; "small_divisor_direct" = 0: sc_coset_divide* transforms a
- * divisor of <= 8 coefficients like any other instead of evaluating it point by point).  Two keys manage the device-memory pool instead (freed vectors and trees are kept
+ * divisor of <= 8 coefficients like any other instead of evaluating it point by point; "verify_stage_kb" = the size of the staging buffer
+ * of sc_merkle_verify_batch / sc_fri_colinearity_batch, 65536 by default, at least 16).  Two keys manage the device-memory pool instead (freed vectors and trees are kept
  * on exact-size free lists, by default up to a quarter of the device's memory divided by the processes sharing the device;
  * environment STARKCORE_POOL_CAP_MB): "pool_cap_mb" = what the lists may keep from now on, "pool_trim" = hand everything on them
  * back to the device now (a caller whose own allocator -- torch's -- ran out of memory). */
@@ -392,6 +393,20 @@ int sc_fri_sample_indices(const void* seed, uint64_t seed_len, uint64_t size, ui
 int sc_transcript_bytes(const void* data, const uint32_t* lens, uint64_t count, void* out, uint64_t out_cap, uint64_t* out_len);
 int sc_merkle_open(const sc_merkle_t* tree, uint64_t index, uint8_t* path_out /* 64*log2 N */); /* Merkle.open, merkle.py:16-27 */
 int sc_merkle_open_batch(const sc_merkle_t* tree, const uint64_t* indices, uint64_t k, uint8_t* paths_out /* k*64*log2 N */);
+/* The batched verifier's checks (FastStark.verify_batch, Fri.verify_batch; rows as in csrc/merkle_verify.cuh), synchronous, host buffers
+ * in and out, any row count: the rows go to the device in chunks through one bounded pinned staging buffer ("verify_stage_kb").
+ * sc_merkle_verify_batch: n rows of 48 bytes {u64 position, u64 path, u32 root, u32 depth <= 64, u32 kind, u32 0, u64 leaf[2]} --
+ * Merkle.verify_(roots[root], position, digests[path .. path + depth - 1], leaf) with the leaf the BLAKE2b-512 of the decimal ASCII of
+ * the 128-bit residue leaf[0] + 2^64 leaf[1] (kind 0) or digests[leaf[0]] (kind 1); digests and roots 64 bytes each.  verdicts_out[i]
+ * = 1 when the path leads to the root, else 0 (also when position >= 2^depth).  Each row is staged with its own path and, for kind 1,
+ * its leaf digest on its own, so a leaf digest may lie anywhere in `digests`; rows whose paths follow each other in `digests` go to
+ * the device in the fewest chunks.
+ * sc_fri_colinearity_batch: n rows of 80 bytes {u64 a, u64 b, u32 round, u32 0[3], y_a, y_b, y_c} over rounds of 48 bytes {offset,
+ * omega, alpha}, all residues 16 bytes little-endian -- test_colinearity([(x_a, y_a), (x_b, y_b), (alpha, y_c)]) with x = offset *
+ * omega^e: verdicts_out[i] = 1 / 0, or 2 (undecided: two abscissas coincide or an input is not below p; the caller decides).
+ * A row that indexes outside the digests, roots or rounds given: SC_ERR_BAD_ARG, nothing is run. */
+int sc_merkle_verify_batch(const void* rows, uint64_t n, const void* digests, uint64_t n_digests, const void* roots, uint64_t n_roots, uint8_t* verdicts_out);
+int sc_fri_colinearity_batch(const void* rows, uint64_t n, const void* rounds, uint64_t n_rounds, uint8_t* verdicts_out);
 /* opened elements AND their paths in one call: elems_out[i] = d_elems[indices[i]] (d_elems = the device vector the tree was built from) */
 int sc_merkle_query_dev(const sc_merkle_t* tree, const void* d_elems, const uint64_t* indices, uint64_t k, void* elems_out, uint8_t* paths_out);
 /* several (tree, vector) pairs in one round trip (the query phase of Fri.prove, fri.py:124-128): counts[t] of the concatenated

@@ -126,6 +126,7 @@ struct Ctx {
     int merkle_big_nlev = 2; // levels fused per launch for Merkle levels wider than FUSE_MAX_W (0: one level kernel per level)
     int fri_tail = -1;       // the persistent tail kernel of Fri.commit (csrc/fri_tail.cuh): -1 = environment STARKCORE_FRI_TAIL (default on), 0 / 1
     int fri_tail_stall = -1; // tests: the host withholds the challenge of this round of the tail kernel (its wait then times out: the abort path)
+    size_t verify_stage_bytes = 64ull << 20;   // sc_merkle_verify_batch / sc_fri_colinearity_batch: the pinned staging buffer and its device twin (sc_set_tuning("verify_stage_kb"))
     uint8_t* root_slots = nullptr;        // pinned host memory: roots of asynchronously built Merkle trees in flight
     uint8_t* later_words = nullptr;       // device memory: the flag and degree words of each deferred check, LATER_WORD_BYTES per pinned slot
     uint64_t root_seq = 0;

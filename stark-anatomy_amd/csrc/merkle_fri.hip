@@ -3,6 +3,7 @@
 #include "core.h"
 #include "merkle.cuh"
 #include "fri_tail.cuh"
+#include "merkle_verify.cuh"
 #include "transcript.h"
 #include "proof_pickle.h"
 #include <immintrin.h>      // _mm_sfence: the challenge written through the BAR (write-combined) must reach the device before its flag
@@ -1025,6 +1026,141 @@ int sc_merkle_open_batch(const sc_merkle_t* tree, const uint64_t* indices, uint6
     HIPCHK(hipGetLastError());
     return download(paths_out, d_out, out_bytes, g.stream);
 }
+
+// ---- the batched verifier's checks (csrc/merkle_verify.cuh).  Rows go to the device in chunks through ONE pinned staging buffer of
+// g.verify_stage_bytes (sc_set_tuning "verify_stage_kb", at least 16 KiB) and a device buffer of the same size.  A chunk holds
+// [its rows][its table entries (roots / rounds)][its digests][one slot per row][its verdicts]: the table entries and the digests are
+// each the contiguous index range the chunk's rows read, the slots carry what a row reads from elsewhere (a Merkle row's leaf
+// digest, which may lie anywhere in the caller's table).  A chunk is the longest run of rows whose layout fits; one row always fits
+// (its path is at most 64 digests), so rows laid out in order (each row's digests behind the previous row's, as verify_batch writes
+// them) make long chunks and any other order is served with shorter ones.  Nothing grows with the batch.
+extern "C++" {
+namespace {
+uint8_t* g_verify_stage = nullptr;
+size_t g_verify_stage_cap = 0;
+constexpr size_t VERIFY_ALIGN = 256;
+inline size_t verify_align(size_t b) { return (b + VERIFY_ALIGN - 1) & ~(VERIFY_ALIGN - 1); }
+
+int verify_stage(size_t bytes, uint8_t** out) {
+    if (g_verify_stage_cap < bytes) {
+        if (g_verify_stage) { HIPCHK(hipHostFree(g_verify_stage)); g_verify_stage = nullptr; g_verify_stage_cap = 0; }
+        HIPCHK(hipHostMalloc((void**)&g_verify_stage, bytes, hipHostMallocDefault));
+        g_verify_stage_cap = bytes;
+    }
+    *out = g_verify_stage;
+    return SC_OK;
+}
+
+struct VerifyChunk {          // device pointers and index bases of one staged chunk
+    uint64_t count, table_base, digest_base;
+    const uint8_t *rows, *table, *digests, *slots;
+    uint8_t* verdicts;
+};
+
+// span(row, tlo, thi, dlo, dhi): the row's table entries [tlo, thi) and digests [dlo, dhi) (either may be empty);
+// fill_slot(row, dst): the row's slot_bytes of the slot region (slot_bytes 0: none); launch(chunk) enqueues the kernel on g.stream
+template <class Row, class Span, class Slot, class Launch>
+int verify_chunked(const Row* rows, uint64_t n, const uint8_t* table, size_t entry_bytes, const uint64_t* digests, size_t slot_bytes,
+                   uint8_t* verdicts_out, Span span, Slot fill_slot, Launch launch) {
+    const size_t cap = g.verify_stage_bytes;
+    uint8_t* stage;
+    SCCHK(verify_stage(cap, &stage));
+    PoolTmp dev;
+    SCCHK(dev.get(cap));
+    uint8_t* d_stage = (uint8_t*)dev.p;
+    for (uint64_t i = 0; i < n;) {
+        uint64_t tlo = ~0ull, thi = 0, dlo = ~0ull, dhi = 0, j = i;
+        size_t rows_b = 0, table_b = 0, dig_b = 0, slot_b = 0;
+        for (; j < n; ++j) {
+            uint64_t a, b, c, d;
+            span(rows[j], a, b, c, d);
+            const uint64_t ntlo = b > a && a < tlo ? a : tlo, nthi = b > a && b > thi ? b : thi;
+            const uint64_t ndlo = d > c && c < dlo ? c : dlo, ndhi = d > c && d > dhi ? d : dhi;
+            const uint64_t cnt = j + 1 - i;
+            const size_t r_b = verify_align(cnt * sizeof(Row));
+            const size_t t_b = nthi > ntlo ? verify_align((nthi - ntlo) * entry_bytes) : 0;
+            const size_t d_b = ndhi > ndlo ? verify_align((ndhi - ndlo) * 64) : 0;
+            const size_t s_b = verify_align(cnt * slot_bytes);
+            if (r_b + t_b + d_b + s_b + verify_align(cnt) > cap) {
+                if (j == i) return fail(SC_ERR_BAD_ARG, "a row does not fit the staging buffer");   // (cannot happen for rows the entries accept)
+                break;
+            }
+            tlo = ntlo; thi = nthi; dlo = ndlo; dhi = ndhi;
+            rows_b = r_b; table_b = t_b; dig_b = d_b; slot_b = s_b;
+        }
+        const uint64_t count = j - i;
+        memcpy(stage, rows + i, count * sizeof(Row));
+        if (table_b) memcpy(stage + rows_b, table + tlo * entry_bytes, (thi - tlo) * entry_bytes);
+        if (dig_b) memcpy(stage + rows_b + table_b, digests + 8 * dlo, (dhi - dlo) * 64);
+        uint8_t* slots = stage + rows_b + table_b + dig_b;
+        if (slot_bytes)
+            for (uint64_t k = 0; k < count; ++k) fill_slot(rows[i + k], slots + k * slot_bytes);
+        const size_t in_b = rows_b + table_b + dig_b + slot_b;
+        HIPCHK(hipMemcpyAsync(d_stage, stage, in_b, hipMemcpyHostToDevice, g.stream));
+        VerifyChunk ch{count, table_b ? tlo : 0, dig_b ? dlo : 0, d_stage, d_stage + rows_b, d_stage + rows_b + table_b,
+                       d_stage + rows_b + table_b + dig_b, d_stage + in_b};
+        SCCHK(launch(ch));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(stage + in_b, d_stage + in_b, count, hipMemcpyDeviceToHost, g.stream));
+        HIPCHK(hipStreamSynchronize(g.stream));
+        memcpy(verdicts_out + i, stage + in_b, count);
+        i = j;
+    }
+    return SC_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int sc_merkle_verify_batch(const void* rows, uint64_t n, const void* digests, uint64_t n_digests, const void* roots, uint64_t n_roots, uint8_t* verdicts_out) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    if (n == 0) return SC_OK;
+    if (!rows || !verdicts_out || (n_roots && !roots) || (n_digests && !digests)) return fail(SC_ERR_BAD_ARG, "null argument");
+    const MerkleCheckRow* R = (const MerkleCheckRow*)rows;
+    for (uint64_t i = 0; i < n; ++i) {      // every index a row holds must lie inside what it is staged from
+        const MerkleCheckRow& r = R[i];
+        if (r.depth > MV_MAX_DEPTH || r.kind > MV_LEAF_DIGEST || r.root >= n_roots) return fail(SC_ERR_BAD_ARG, "merkle row: bad depth, leaf kind or root index");
+        if (r.depth && (r.path > n_digests || r.depth > n_digests - r.path)) return fail(SC_ERR_BAD_ARG, "merkle row: path outside the digests");
+        if (r.kind == MV_LEAF_DIGEST && r.leaf[0] >= n_digests) return fail(SC_ERR_BAD_ARG, "merkle row: leaf digest outside the digests");
+    }
+    const uint64_t* D = (const uint64_t*)digests;
+    return verify_chunked(R, n, (const uint8_t*)roots, 64, D, 64, verdicts_out,
+        [](const MerkleCheckRow& r, uint64_t& tlo, uint64_t& thi, uint64_t& dlo, uint64_t& dhi) {
+            tlo = r.root; thi = (uint64_t)r.root + 1;
+            dlo = r.path; dhi = r.path + r.depth;
+        },
+        [D](const MerkleCheckRow& r, uint8_t* slot) {
+            if (r.kind == MV_LEAF_DIGEST) memcpy(slot, D + 8 * r.leaf[0], 64);
+        },
+        [](const VerifyChunk& c) {
+            hipLaunchKernelGGL(merkle_verify_kernel, dim3((unsigned)((c.count + 255) / 256)), dim3(256), 0, g.stream, (const MerkleCheckRow*)c.rows, c.count,
+                               (const uint64_t*)c.digests, c.digest_base, (const uint64_t*)c.slots, (const uint64_t*)c.table, (uint32_t)c.table_base,
+                               c.verdicts);
+            return SC_OK;
+        });
+}
+
+int sc_fri_colinearity_batch(const void* rows, uint64_t n, const void* rounds, uint64_t n_rounds, uint8_t* verdicts_out) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    if (n == 0) return SC_OK;
+    if (!rows || !verdicts_out || !rounds) return fail(SC_ERR_BAD_ARG, "null argument");
+    const ColinearityRow* R = (const ColinearityRow*)rows;
+    for (uint64_t i = 0; i < n; ++i)
+        if (R[i].round >= n_rounds) return fail(SC_ERR_BAD_ARG, "colinearity row: round index outside the table");
+    return verify_chunked(R, n, (const uint8_t*)rounds, sizeof(ColinearityRound), nullptr, 0, verdicts_out,
+        [](const ColinearityRow& r, uint64_t& tlo, uint64_t& thi, uint64_t& dlo, uint64_t& dhi) {
+            tlo = r.round; thi = (uint64_t)r.round + 1;
+            dlo = dhi = 0;
+        },
+        [](const ColinearityRow&, uint8_t*) {},
+        [](const VerifyChunk& c) {
+            hipLaunchKernelGGL(colinearity_kernel, dim3((unsigned)((c.count + 255) / 256)), dim3(256), 0, g.stream, (const ColinearityRow*)c.rows, c.count,
+                               (const ColinearityRound*)c.table, (uint32_t)c.table_base, c.verdicts);
+            return SC_OK;
+        });
+}
+
 // elements + authentication paths for k indices in one round trip (the FRI query phase, code/fri.py:98-113)
 int sc_merkle_query_dev(const sc_merkle_t* tree, const void* d_elems, const uint64_t* indices, uint64_t k, void* elems_out, uint8_t* paths_out) {
     std::lock_guard<std::mutex> lk(g_mu);

@@ -624,6 +624,85 @@ class FastStark:
                 return False
         return True
 
+    def verify_batch(self, proofs, transition_constraints, boundaries, transition_zerofier_root, proof_streams=None):
+        """[self.verify(proofs[i], transition_constraints, boundaries[i], transition_zerofier_root, proof_streams[i]) for i ...] with
+        every Merkle path and FRI colinearity test of the whole batch checked in one device call per kind (csrc/merkle_verify.cuh).
+        The walk over each proof is `verify`'s, pull for pull; the checks that are cheap on the host (the last codeword, its degree,
+        the combination at the opened points) run here, the rest become rows.  A proof on which `verify` raises is reported False."""
+        if proof_streams is None:
+            proof_streams = [None] * len(proofs)
+        checks = BatchChecks(len(proofs))
+        for owner, (proof, boundary, proof_stream) in enumerate(zip(proofs, boundaries, proof_streams)):
+            try:
+                if not self._collect_checks(proof, transition_constraints, boundary, transition_zerofier_root, proof_stream, checks, owner):
+                    checks.reject(owner)
+            except Exception:
+                checks.reject(owner)
+        return checks.run()
+
+    def _collect_checks(self, proof, transition_constraints, boundary, transition_zerofier_root, proof_stream, checks, owner):
+        stream = (ProofStream() if proof_stream == None else proof_stream).deserialize(proof)
+        registers = range(self.num_registers)
+        trace_rows = 1 + max(cycle for cycle, _, _ in boundary) + self.num_randomizers
+
+        # the commitments, and the combination weights they determine
+        quotient_roots = [stream.pull() for _ in registers]
+        randomizer_root = stream.pull()
+        weights = self.sample_weights(1 + 2 * len(transition_constraints) + 2 * self.num_registers, stream.verifier_fiat_shamir())
+
+        # low-degree test of the combination; it reports the combination's values at the points it opened
+        opened = []
+        accepted = self.fri._collect_checks(stream, opened, checks, owner)
+        opened.sort(key=lambda index_value: index_value[0])
+        if not accepted:
+            return False
+
+        # every committed codeword opened at those points and at their successors on the trace domain
+        N, step = self.fri.domain_length, self.expansion_factor
+        positions = sorted([i for i, _ in opened] + [(i + step) % N for i, _ in opened])
+        quotient_leaves = []
+        for root in quotient_roots:
+            quotient_leaves.append(self._collect_openings(stream, root, positions, checks, owner))
+        randomizer = self._collect_openings(stream, randomizer_root, positions, checks, owner)
+        zerofier_values = self._collect_openings(stream, transition_zerofier_root, positions, checks, owner)
+
+        # the combination recomputed from the openings must agree with FRI's view of it at every queried point
+        zerofiers, interpolants = self.boundary_zerofiers(boundary), self.boundary_interpolants(boundary)
+        max_degree = self.max_degree(transition_constraints)
+        transition_shifts = [max_degree - bound for bound in self.transition_quotient_degree_bounds(transition_constraints)]
+        boundary_shifts = [max_degree - bound for bound in self.boundary_quotient_degree_bounds(trace_rows, boundary)]
+        constraint_at = [constraint.evaluator() for constraint in transition_constraints]      # term lists extracted once, not per point
+
+        def trace_row(index, x):
+            # undo the boundary quotient: trace = quotient * zerofier + interpolant
+            return [quotient_leaves[s][index] * zerofiers[s].evaluate(x) + interpolants[s].evaluate(x) for s in registers]
+
+        for index, claimed in opened:
+            successor = (index + step) % N
+            x = self.generator * (self.omega ^ index)
+            point = [x] + trace_row(index, x) + trace_row(successor, self.generator * (self.omega ^ successor))
+            weight = iter(weights)
+            total = randomizer[index] * next(weight)
+            for evaluate, shift in zip(constraint_at, transition_shifts):
+                quotient = evaluate(point) / zerofier_values[index]
+                total = total + quotient * next(weight) + quotient * (x ^ shift) * next(weight)
+            for s, shift in zip(registers, boundary_shifts):
+                quotient = quotient_leaves[s][index]
+                total = total + quotient * next(weight) + quotient * (x ^ shift) * next(weight)
+            if not (total == claimed):
+                return False
+        return True
+
+    @staticmethod
+    def _collect_openings(stream, root, positions, checks, owner):
+        """_pull_openings with the paths recorded in `checks` instead of verified"""
+        leaves = {}
+        for position in positions:
+            leaf, path = stream.pull(), stream.pull()
+            checks.merkle(owner, root, position, path, leaf)
+            leaves[position] = leaf
+        return leaves
+
     @staticmethod
     def _pull_openings(stream, root, positions):
         """{position: leaf} from the (leaf, authentication path) pairs the prover pushed for one commitment, in the order of

@@ -49,6 +49,137 @@ def library_transcript(proof_stream, rounds):
     return None
 
 
+class BatchChecks:
+    """The checks of a batch of proofs collected as rows (csrc/merkle_verify.cuh) instead of evaluated one by one: every Merkle
+    path and every colinearity test of every proof, tagged with the proof it belongs to, then ONE device call per kind (`run`).
+    A row the device format cannot hold (a leaf that is not a residue below 2^128, a path that is not 64-byte digests, a root that is
+    not a 64-byte string, a value that is not a residue of the main field) is decided here, by the host function it replaces."""
+
+    def __init__(self, count):
+        self.ok = [True] * count                 # host checks (and exceptions) per proof
+        # Merkle rows as columns (starkcore.merkle_rows), the digests their paths index, the root table
+        self.m_position, self.m_path, self.m_root, self.m_depth, self.m_kind, self.m_leaf, self.m_owner = [], [], [], [], [], [], []
+        self.digests, self.n_digests = [], 0
+        self.roots, self.root_index = [], {}
+        # colinearity rows as columns (starkcore.colinearity_rows) and the round table, 48 bytes per entry
+        self.c_a, self.c_b, self.c_round, self.c_y, self.c_owner, self.rounds = [], [], [], [], [], []
+        self.col_points = []                     # per colinearity row: its points, for test_colinearity if the device leaves it undecided
+        self.truncations = []                    # (values list, its length before round 0, round 0's colinearity references)
+
+    def reject(self, owner):
+        self.ok[owner] = False
+
+    def root(self, root):
+        """index of a 64-byte root in the root table, or None when the device cannot compare with it"""
+        if type(root) is not bytes or len(root) != 64:
+            return None
+        index = self.root_index.get(root)
+        if index is None:
+            index = self.root_index[root] = len(self.roots)
+            self.roots.append(root)
+        return index
+
+    def merkle(self, owner, root, index, path, data_element):
+        """Merkle.verify(root, index, path, data_element) as a row"""
+        r = self.root(root)
+        try:
+            joined = b"".join(path)
+            depth = len(path)
+            device = (r is not None and type(index) is int and 0 <= index < (1 << depth) and depth <= 64 and len(joined) == 64 * depth
+                      and (depth == 0 or max(map(len, path)) == 64))
+        except Exception:
+            device = False
+        if device:
+            if type(data_element) is FieldElement and type(data_element.value) is int and 0 <= data_element.value < (1 << 128):
+                kind, leaf = _sc.LEAF_RESIDUE, data_element.value.to_bytes(16, "little")
+            else:
+                try:
+                    digest = Merkle.H(bytes(data_element)).digest()
+                except Exception:
+                    self.ok[owner] = False
+                    return
+                kind, leaf = _sc.LEAF_DIGEST, self.n_digests.to_bytes(16, "little")
+                self.digests.append(digest)
+                self.n_digests += 1
+            self.m_position.append(index)
+            self.m_path.append(self.n_digests)
+            self.m_root.append(r)
+            self.m_depth.append(depth)
+            self.m_kind.append(kind)
+            self.m_leaf.append(leaf)
+            self.m_owner.append(owner)
+            self.digests.append(joined)
+            self.n_digests += depth
+            return
+        try:
+            accepted = Merkle.verify(root, index, path, data_element)
+        except Exception:
+            accepted = False
+        if not accepted:
+            self.ok[owner] = False
+
+    def round(self, offset, omega, alpha):
+        """a round-table entry (offset_r, omega_r, alpha_r); None when they are not residues of the main field"""
+        if not all(type(e) is FieldElement and type(e.value) is int and 0 <= e.value < Field.P_MAIN and e.field.p == Field.P_MAIN
+                   for e in (offset, omega, alpha)):
+            return None
+        self.rounds.append(offset.value.to_bytes(16, "little") + omega.value.to_bytes(16, "little") + alpha.value.to_bytes(16, "little"))
+        return len(self.rounds) - 1
+
+    def colinearity(self, owner, round_index, offset, omega, a, b, alpha, ya, yb, yc):
+        """test_colinearity([(offset * omega^a, ya), (offset * omega^b, yb), (alpha, yc)]) as a row; returns ("row", row index) or
+        ("host", verdict) for `truncate`"""
+        ys = (ya, yb, yc)
+        if round_index is not None and all(type(y) is FieldElement and type(y.value) is int and 0 <= y.value < Field.P_MAIN
+                                           and y.field.p == Field.P_MAIN for y in ys) and 0 <= a < (1 << 64) and 0 <= b < (1 << 64):
+            self.c_a.append(a)
+            self.c_b.append(b)
+            self.c_round.append(round_index)
+            self.c_y.append(ya.value.to_bytes(16, "little") + yb.value.to_bytes(16, "little") + yc.value.to_bytes(16, "little"))
+            self.c_owner.append(owner)
+            self.col_points.append((offset, omega, a, b, alpha, ya, yb, yc))
+            return ("row", len(self.c_a) - 1)
+        try:
+            accepted = test_colinearity([(offset * (omega ^ a), ya), (offset * (omega ^ b), yb), (alpha, yc)])
+        except Exception:
+            accepted = False
+        if not accepted:
+            self.ok[owner] = False
+        return ("host", accepted)
+
+    def run(self):
+        """the device calls, then a proof's verdict: its host checks passed and every row of it passes"""
+        import numpy as np
+        ok = np.array(self.ok, dtype=bool)
+        if self.m_position:
+            rows = _sc.merkle_rows(self.m_position, self.m_path, self.m_root, self.m_depth, self.m_kind, b"".join(self.m_leaf))
+            verdicts = _sc.merkle_verify_batch(rows, b"".join(self.digests), b"".join(self.roots))
+            ok[np.asarray(self.m_owner, dtype=np.int64)[verdicts != 1]] = False
+        col_verdicts = None
+        if self.c_a:
+            rows = _sc.colinearity_rows(self.c_a, self.c_b, self.c_round, b"".join(self.c_y))
+            col_verdicts = _sc.colinearity_batch(rows, b"".join(self.rounds))
+            for t in np.flatnonzero(col_verdicts == _sc.UNDECIDED):
+                offset, omega, a, b, alpha, ya, yb, yc = self.col_points[t]
+                try:
+                    col_verdicts[t] = 1 if test_colinearity([(offset * (omega ^ int(a)), ya), (offset * (omega ^ int(b)), yb), (alpha, yc)]) else 0
+                except Exception:
+                    col_verdicts[t] = 0
+            ok[np.asarray(self.c_owner, dtype=np.int64)[col_verdicts != 1]] = False
+        # Fri.verify appends round 0's pairs test by test and stops at the first failed colinearity test: the same prefix here
+        for values, base, refs in self.truncations:
+            for t, (where, what) in enumerate(refs):
+                if not (col_verdicts[what] == 1 if where == "row" else what):
+                    del values[base + 2 * (t + 1):]
+                    break
+        return [bool(v) for v in ok]
+
+    def truncate(self, values, base, refs):
+        """round 0 appends its pairs to `values` from position `base` on; refs: what `colinearity` returns for its tests, filled in
+        place as they are recorded (a walk that raises half-way leaves the tests recorded so far)"""
+        self.truncations.append((values, base, refs))
+
+
 class Fri:
     def __init__(self, offset, omega, initial_domain_length, expansion_factor, num_colinearity_tests):
         self.offset, self.omega, self.field = offset, omega, omega.field
@@ -400,5 +531,62 @@ class Fri:
                 for root, position, leaf, label in ((roots[r], a, ya, "aa"), (roots[r], b, yb, "bb"), (roots[r + 1], a, yc, "cc")):
                     if not Merkle.verify(root, position, proof_stream.pull(), leaf):
                         return Fri._reject("merkle authentication path verification fails for " + label)
+            omega, offset = omega ^ 2, offset ^ 2
+        return True
+
+    def verify_batch(self, proof_streams, polynomial_values_lists):
+        """[self.verify(stream, values) for ...] with every Merkle path and colinearity test of the batch checked in one device call
+        per kind (csrc/merkle_verify.cuh); a proof on which `verify` raises is reported False, and never affects the others"""
+        checks = BatchChecks(len(proof_streams))
+        for owner, (proof_stream, polynomial_values) in enumerate(zip(proof_streams, polynomial_values_lists)):
+            self._collect(proof_stream, polynomial_values, checks, owner)
+        return checks.run()
+
+    def _collect(self, proof_stream, polynomial_values, checks, owner):
+        """`verify`'s walk over one proof (line by line the same pulls), its checks recorded in `checks` instead of evaluated"""
+        try:
+            if not self._collect_checks(proof_stream, polynomial_values, checks, owner):
+                checks.reject(owner)
+        except Exception:
+            checks.reject(owner)
+
+    def _collect_checks(self, proof_stream, polynomial_values, checks, owner):
+        rounds, s = self.num_rounds(), self.num_colinearity_tests
+        # the commit phase replayed: per round a root and the challenge it determines, then the last codeword in the clear
+        roots, alphas = [], []
+        for _ in range(rounds):
+            roots.append(proof_stream.pull())
+            alphas.append(self.field.sample(proof_stream.verifier_fiat_shamir()))
+        last_codeword = proof_stream.pull()
+        if Merkle.commit(last_codeword) != roots[-1]:
+            return False
+        # the last codeword lives on the coset after rounds - 1 squarings; it must be of low degree there
+        squarings = 1 << (rounds - 1)
+        last_omega, last_offset = self.omega ^ squarings, self.offset ^ squarings
+        assert(last_omega.inverse() == last_omega ^ (len(last_codeword) - 1)), "omega does not have right order"
+        allowed = len(last_codeword) // self.expansion_factor - 1
+        observed = self._last_codeword_degree(last_codeword, last_omega, last_offset)
+        if observed > allowed:
+            return False
+        # the query phase: consistency of consecutive codewords at the sampled positions
+        top_level_indices = self.sample_indices(proof_stream.verifier_fiat_shamir(), self.domain_length >> 1, self.domain_length >> (rounds - 1), s)
+        omega, offset = self.omega, self.offset
+        for r in range(rounds - 1):
+            half = self.domain_length >> (r + 1)
+            lower = [index % half for index in top_level_indices]
+            upper = [index + half for index in lower]
+            triples = [proof_stream.pull() for _ in range(s)]
+            round_index = checks.round(offset, omega, alphas[r])
+            refs = []
+            if r == 0:        # registered before the tests: a later triple that raises must not keep pairs verify would not have appended
+                checks.truncate(polynomial_values, len(polynomial_values), refs)
+            for a, b, (ya, yb, yc) in zip(lower, upper, triples):
+                if r == 0:
+                    polynomial_values += [(a, ya), (b, yb)]
+                # (x_a, y_a), (x_b, y_b) and (alpha, y_c) lie on one line: that is the fold of fri.py:85 read backwards
+                refs.append(checks.colinearity(owner, round_index, offset, omega, a, b, alphas[r], ya, yb, yc))
+            for a, b, (ya, yb, yc) in zip(lower, upper, triples):
+                for root, position, leaf in ((roots[r], a, ya), (roots[r], b, yb), (roots[r + 1], a, yc)):
+                    checks.merkle(owner, root, position, proof_stream.pull(), leaf)
             omega, offset = omega ^ 2, offset ^ 2
         return True

@@ -116,6 +116,8 @@ SIGNATURES = {
     "sc_transcript_bytes": (_int, [_vp, _vp, _u64, _vp, _u64, ctypes.POINTER(_u64)]),
     "sc_merkle_open": (_int, [_vp, _u64, _vp]),
     "sc_merkle_open_batch": (_int, [_vp, _vp, _u64, _vp]),
+    "sc_merkle_verify_batch": (_int, [_vp, _u64, _vp, _u64, _vp, _u64, _vp]),
+    "sc_fri_colinearity_batch": (_int, [_vp, _u64, _vp, _u64, _vp]),
     "sc_merkle_query_dev": (_int, [_vp, _vp, _vp, _u64, _vp, _vp]),
     "sc_merkle_query_multi_dev": (_int, [_u64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sc_merkle_level_copy_dev": (_int, [_vp, _int, _vp, _vp]),
@@ -467,6 +469,67 @@ def query_codewords(codewords, requests):
         out.append((cw._entries(req, values[vo:vo + k]), _path_lists(view, po, d, k)))
         vo += k
         po += 64 * k * d
+    return out
+
+
+# The batched verifier's rows (csrc/merkle_verify.cuh MerkleCheckRow / ColinearityRow / ColinearityRound; include/starkcore.h)
+def _row_dtypes():
+    import numpy as np
+    merkle = np.dtype([("position", "<u8"), ("path", "<u8"), ("root", "<u4"), ("depth", "<u4"), ("kind", "<u4"), ("reserved", "<u4"),
+                       ("leaf", "<u8", (2,))])
+    colinearity = np.dtype([("a", "<u8"), ("b", "<u8"), ("round", "<u4"), ("reserved", "<u4", (3,)), ("ya", "<u8", (2,)), ("yb", "<u8", (2,)),
+                            ("yc", "<u8", (2,))])
+    rnd = np.dtype([("offset", "<u8", (2,)), ("omega", "<u8", (2,)), ("alpha", "<u8", (2,))])
+    assert (merkle.itemsize, colinearity.itemsize, rnd.itemsize) == (48, 80, 48)
+    return merkle, colinearity, rnd
+
+
+MERKLE_ROW, COLINEARITY_ROW, COLINEARITY_ROUND = _row_dtypes()
+LEAF_RESIDUE, LEAF_DIGEST = 0, 1
+UNDECIDED = 2
+
+
+def merkle_rows(positions, paths, roots, depths, kinds, leaves):
+    """a MERKLE_ROW array from columns; leaves: 16 bytes per row (the residue little-endian, or the leaf digest's index)"""
+    import numpy as np
+    rows = np.zeros(len(positions), dtype=MERKLE_ROW)
+    if len(rows):
+        rows["position"], rows["path"], rows["root"], rows["depth"], rows["kind"] = positions, paths, roots, depths, kinds
+        rows["leaf"] = np.frombuffer(leaves, dtype="<u8").reshape(len(rows), 2)
+    return rows
+
+
+def colinearity_rows(a, b, rounds, ys):
+    """a COLINEARITY_ROW array from columns; ys: 48 bytes per row (y_a, y_b, y_c, 16 bytes little-endian each)"""
+    import numpy as np
+    rows = np.zeros(len(a), dtype=COLINEARITY_ROW)
+    if len(rows):
+        rows["a"], rows["b"], rows["round"] = a, b, rounds
+        y = np.frombuffer(ys, dtype="<u8").reshape(len(rows), 6)
+        rows["ya"], rows["yb"], rows["yc"] = y[:, 0:2], y[:, 2:4], y[:, 4:6]
+    return rows
+
+
+def merkle_verify_batch(rows, digests, roots):
+    """sc_merkle_verify_batch: rows (a MERKLE_ROW array), digests and roots (bytes, 64 per entry) -> uint8 verdicts (1 = the path
+    leads to the root)"""
+    import numpy as np
+    rows = np.ascontiguousarray(rows, dtype=MERKLE_ROW)
+    out = np.zeros(len(rows), dtype=np.uint8)
+    if len(rows):
+        _check(lib().sc_merkle_verify_batch(rows.ctypes.data, len(rows), digests, len(digests) // 64, roots, len(roots) // 64, out.ctypes.data))
+    return out
+
+
+def colinearity_batch(rows, rounds):
+    """sc_fri_colinearity_batch: rows (a COLINEARITY_ROW array) over rounds (a COLINEARITY_ROUND array, or 48 bytes each) -> uint8 verdicts
+    (1 / 0, UNDECIDED: the caller decides the row with test_colinearity)"""
+    import numpy as np
+    rows = np.ascontiguousarray(rows, dtype=COLINEARITY_ROW)
+    rounds = np.frombuffer(rounds, dtype=COLINEARITY_ROUND) if isinstance(rounds, bytes) else np.ascontiguousarray(rounds, dtype=COLINEARITY_ROUND)
+    out = np.zeros(len(rows), dtype=np.uint8)
+    if len(rows):
+        _check(lib().sc_fri_colinearity_batch(rows.ctypes.data, len(rows), rounds.ctypes.data, len(rounds), out.ctypes.data))
     return out
 
 
