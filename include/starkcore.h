@@ -296,6 +296,17 @@ int sc_mpoly_eval_ex_dev(void* d_vals, uint64_t nvars, uint64_t n, const uint8_t
 int sc_mpoly_eval_rot_dev(void* d_vals, uint64_t nvars, uint64_t n, const uint8_t* exps, const void* coefs, uint64_t nterms, void* d_out, int vals_converted,
                           const uint32_t* var_src, const uint64_t* var_rot, void* stream);
 
+/* ---- Rescue-Prime : code/rescue_prime.py:25-60 (hash), :62-104 (trace) ----------------------- */
+/* The permutation of the tutorial's hash over n inputs, one lane each.  The state width is fixed: m = 2 (rate 1, capacity 1), alpha = 3.
+ * d_in: n elements (reduced mod p on load).  params: HOST pointer to 4 + 4 * rounds packed canonical residues -- the MDS matrix
+ * (row-major, 2 x 2), then the 2 m rounds round constants (round r: [4 r, 4 r + 2) after the cube, [4 r + 2, 4 r + 4) after the
+ * inverse cube).  Enqueued on `stream`; n == 0 launches nothing.
+ * hash:  d_out[k] = state[0] after `rounds` rounds (n elements).
+ * trace: all rounds + 1 states, register s of input k's state t at d_out[(2 k + s) * (rounds + 1) + t] (2 n (rounds + 1) elements).
+ * SC_ERR_BAD_ARG: rounds == 0 or > 27, a constant not below p, params NULL, or a NULL buffer with n > 0. */
+int sc_rescue_prime_hash_dev(const void* d_in, uint64_t n, const void* params, uint64_t rounds, void* d_out, void* stream);
+int sc_rescue_prime_trace_dev(const void* d_in, uint64_t n, const void* params, uint64_t rounds, void* d_out, void* stream);
+
 /* ---- FRI split-and-fold : code/fri.py:85 ---------------------------------------------------- */
 /* out[i] = 2^-1 * ((1 + alpha/(offset*omega^i)) * in[i] + (1 - alpha/(offset*omega^i)) * in[N/2+i]), i < N/2 */
 int sc_fri_fold(const void* in, uint64_t N, const uint64_t alpha[2], const uint64_t offset[2], const uint64_t omega[2], void* out);

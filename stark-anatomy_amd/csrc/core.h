@@ -6,6 +6,7 @@
 //   merkle_fri.hip    Merkle trees, the FRI fold and commit loop, the Fiat-Shamir transcript, openings
 //   polytree_geo.hip  subproduct trees and geometric progressions (fast_zerofier / fast_evaluate / fast_interpolate)
 //   fourstep.hip      batched transforms, the sharded four-step plan, the RCCL communicator, the direct-store corner turn
+//   rescue.hip        the Rescue-Prime permutation (hash and trace) over many inputs
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
