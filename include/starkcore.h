@@ -45,6 +45,7 @@ extern "C" {
 
 typedef struct sc_vec sc_vec_t;        /* device-resident vector of field elements */
 typedef struct sc_merkle sc_merkle_t;  /* device-resident BLAKE2b Merkle tree (all levels kept) */
+typedef struct sc_merkle_forest sc_merkle_forest_t; /* device-resident forest of equal-sized Merkle trees over one matrix (all levels kept) */
 typedef struct sc_later sc_later_t;    /* a check whose words arrive behind the work that produces them (sc_*_later_dev, sc_later_wait) */
 typedef struct sc_polytree sc_polytree_t; /* device-resident subproduct tree over a list of points (all levels kept) */
 typedef struct sc_geodomain sc_geodomain_t; /* tables of a domain that is a geometric progression first * ratio^i */
@@ -61,11 +62,12 @@ int sc_stream(void** stream_out);
 int sc_stream_join(void* other_stream);
 /* tuning knobs for experiments (defaults are the measured optimum; -1 = choose by size where applicable): key in
  * {"max_tile_log","loge","max_col_log","min_tiles_log","single_pass_max_log","max_digit_log","direct_tw_max_log",
- *  "xcd_remap","fixed_shapes","merkle_big_nlev","wave_local","prio_balance","loge_cols","tw_on_load","prune","fri_tail","fri_tail_stall","small_divisor_direct","verify_stage_kb"}.  Plans are re-derived on the next
+ *  "xcd_remap","fixed_shapes","merkle_big_nlev","wave_local","prio_balance","loge_cols","tw_on_load","prune","fri_tail","fri_tail_stall","small_divisor_direct","verify_stage_kb","forest_four_lane_wgs"}.  Plans are re-derived on the next
  * call; results never depend on the tuning ("fri_tail_stall" = k >= 0 is a test hook: the host withholds the challenge after round k of
  * the persistent tail kernel, whose wait then gives up after 2^13 polls; -1 = off; "small_divisor_direct" = 0: sc_coset_divide* transforms a
  * divisor of <= 8 coefficients like any other instead of evaluating it point by point; "verify_stage_kb" = the size of the staging buffer
- * of sc_merkle_verify_batch / sc_fri_colinearity_batch, 65536 by default, at least 16).  Two keys manage the device-memory pool instead (freed vectors and trees are kept
+ * of sc_merkle_verify_batch / sc_fri_colinearity_batch, 65536 by default, at least 16; "forest_four_lane_wgs" = a launch of a Merkle forest of
+ * at most this many workgroups runs its narrow levels four lanes per BLAKE2b compression, 0 = never).  Two keys manage the device-memory pool instead (freed vectors and trees are kept
  * on exact-size free lists, by default up to a quarter of the device's memory divided by the processes sharing the device;
  * environment STARKCORE_POOL_CAP_MB): "pool_cap_mb" = what the lists may keep from now on, "pool_trim" = hand everything on them
  * back to the device now (a caller whose own allocator -- torch's -- ran out of memory). */
@@ -438,6 +440,36 @@ int sc_fri_fold_slab_build_dev(const void* d_in, uint64_t rows, uint64_t cols, u
                                const uint64_t omega[2], void* d_out, sc_merkle_t** tree, void* stream);
 uint64_t sc_merkle_leaves(const sc_merkle_t* tree);
 int sc_merkle_free(sc_merkle_t* tree);
+
+/* ---- Merkle forests: Merkle.commit (merkle.py:13-14) of `count` arrays of N leaves each in one set of launches ------------------ */
+/* d_elems: a device matrix [count][N] of residues, row t = the leaves of tree t; N a power of two >= 2, count >= 1.  All levels of all
+ * trees are kept (tree-major, csrc/merkle_forest.cuh).  The largest forest an entry takes has SC_FOREST_MAX_LEAVES leaves in total
+ * (count * N; the fold: of its input): above it SC_ERR_UNSUPPORTED and the caller splits the batch.  N not a power of two or below 2,
+ * count 0, a NULL argument: SC_ERR_BAD_ARG.  Nothing is enqueued by a call that fails.  Enqueue only: sc_merkle_forest_roots waits.
+ * The roots travel to pinned memory of the forest's own (the pool of sc_host_alloc), written by the launch that computes them: a
+ * forest takes none of the 256 pinned slots the asynchronous single trees and the deferred checks share. */
+#define SC_FOREST_MAX_LEAVES (1ull << 24)
+int sc_merkle_forest_build_dev(const void* d_elems, uint64_t N, uint64_t count, sc_merkle_forest_t** forest, void* stream);
+/* One round of Fri.commit (fri.py:73-88) for `count` codewords at once: row t of d_out [count][N/2] = the split-and-fold (fri.py:85) of
+ * row t of d_in [count][N] with its own challenge alphas_host[2t .. 2t+1] (packed canonical residues in HOST memory: they come from the
+ * host's Fiat-Shamir step; offset and omega are shared), and the forest over d_out, whose leaf stage computes the fold.  Equal to
+ * sc_fri_fold_dev row by row, bit for bit.  N = 2 leaves trees of one leaf.  Enqueue only. */
+int sc_fri_fold_forest_dev(const void* d_in, uint64_t N, uint64_t count, const uint64_t* alphas_host, const uint64_t offset[2], const uint64_t omega[2], void* d_out,
+                           sc_merkle_forest_t** forest, void* stream);
+/* waits for the build, once, with the library's lock released: a forest has ONE owner -- no other thread may free the handle while a
+ * call on it is in progress (as for every handle of this header) */
+int sc_merkle_forest_roots(sc_merkle_forest_t* forest, uint8_t* roots_out /* 64 * count */);
+uint64_t sc_merkle_forest_trees(const sc_merkle_forest_t* forest);
+uint64_t sc_merkle_forest_leaves(const sc_merkle_forest_t* forest);                            /* per tree */
+int sc_merkle_forest_free(sc_merkle_forest_t* forest);
+/* sc_merkle_query_multi_dev for forests: opening i of pair p is element and path (Merkle.open, merkle.py:16-27) of leaf indices[i] of
+ * tree trees[i] of forests[p] over the matrix d_elems[p]; counts[p] openings belong to pair p, concatenated; outputs concatenated in
+ * the same order (16 bytes per element, 64 * log2 N_p bytes per path).  One launch for all pairs.  elems_out / paths_out inside
+ * buffers of sc_host_alloc are written by the kernel itself; other host pointers are served through a copy.  A tree >= count or an
+ * index >= N: SC_ERR_BAD_ARG, nothing enqueued.  Synchronous. */
+int sc_merkle_forest_query_dev(uint64_t n_pairs, const sc_merkle_forest_t* const* forests, const void* const* d_elems, const uint64_t* trees, const uint64_t* indices,
+                               const uint64_t* counts, void* elems_out, uint8_t* paths_out);
+int sc_merkle_forest_stats(uint64_t out[2]);   /* forests built and trees in them since sc_init */
 
 #ifdef __cplusplus
 }

@@ -3,7 +3,7 @@
 // (include/starkcore.h is); everything lives in namespace sci and is hidden from the shared object's export table.
 //
 //   core.hip          state, pool, streams, tables, planner + pass launches, vectors / randomness / transforms / pointwise entries
-//   merkle_fri.hip    Merkle trees, the FRI fold and commit loop, the Fiat-Shamir transcript, openings
+//   merkle_fri.hip    Merkle trees and forests of them, the FRI fold and commit loop, the Fiat-Shamir transcript, openings
 //   polytree_geo.hip  subproduct trees and geometric progressions (fast_zerofier / fast_evaluate / fast_interpolate)
 //   fourstep.hip      batched transforms, the sharded four-step plan, the RCCL communicator, the direct-store corner turn
 //   rescue.hip        the Rescue-Prime permutation (hash and trace) over many inputs
@@ -58,6 +58,17 @@ struct sc_merkle {
     bool have_root = false;
     bool lazy = false;    // built "enqueue only" (BUILD_NOROOT): no slot, no publish kernel; the root is copied out if ever asked for
     uint8_t root[64] = {};
+};
+
+struct sc_merkle_forest {   // count trees of N leaves, tree-major (csrc/merkle_forest.cuh)
+    uint64_t* d_levels;   // count blocks of 2N digests
+    uint64_t N, count;
+    int logN;
+    uint64_t* h_roots = nullptr;   // pinned (the pool of sc_host_alloc): 64 bytes per tree, written by the launch that reaches the roots; behind them the fold's staged c_m
+    Fe* d_cm = nullptr;            // the fused fold's per-tree constants (pool), or null
+    hipEvent_t done = nullptr;     // recorded behind the build
+    hipStream_t st = nullptr;
+    bool have_roots = false;
 };
 
 namespace sci {
@@ -124,6 +135,7 @@ struct Ctx {
     int prio_balance = -1;   // -1: 1 for launches of at most one workgroup per CU, 2 for long grids (>= 8 workgroups per CU; >= 2 of 2^10 x 4 tiles), else 0; 0 / 1 / 2: force (PassParams::prio_balance)
     int wave_local = 1;      // wave-level fences instead of workgroup barriers once a tile's exchanges stay inside one wave
     unsigned long long* trace = nullptr;   // diagnostics: phase stamps of the next fixed-shape pass launches (sc_debug_trace)
+    int forest_four_lane_wgs = 256;  // a forest launch of at most this many workgroups runs its narrow levels four lanes per compression (0: never)
     int merkle_big_nlev = 2; // levels fused per launch for Merkle levels wider than FUSE_MAX_W (0: one level kernel per level)
     int fri_tail = -1;       // the persistent tail kernel of Fri.commit (csrc/fri_tail.cuh): -1 = environment STARKCORE_FRI_TAIL (default on), 0 / 1
     int fri_tail_stall = -1; // tests: the host withholds the challenge of this round of the tail kernel (its wait then times out: the abort path)
@@ -230,6 +242,10 @@ void root_poll_unlocked(std::unique_lock<std::mutex>& lk, const sc_merkle* t);
 int fold_prepare(const Fe* d_in, uint64_t N, Fe alpha, Fe offset, Fe omega, Fe* d_out, hipStream_t st, FoldIn* f);
 int fold_device(const Fe* d_in, uint64_t N, Fe alpha, Fe offset, Fe omega, Fe* d_out, hipStream_t st);
 int fold_and_build(const Fe* d_in, uint64_t N, Fe alpha, Fe offset, Fe omega, Fe* d_out, sc_merkle** tree, hipStream_t st);
+int fold_constants(uint64_t N, Fe offset, Fe omega, hipStream_t st, PowTables** pw_out, Fe* i2o_m_out);
+int host_pool_get(size_t bytes, void** out);
+int host_pool_put(void* p);
+bool host_pool_holds(const void* p, size_t bytes);
 
 // ---- polytree_geo.hip
 Fe canonical_root(int logn);

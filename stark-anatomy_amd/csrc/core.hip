@@ -939,6 +939,7 @@ int sc_set_tuning(const char* key, int value) {
     else if (k == "tw_on_load") g.tuning.tw_on_load = value;
     else if (k == "prune") g.tuning.prune = value;
     else if (k == "merkle_big_nlev") g.merkle_big_nlev = value < 0 ? 0 : (value > 8 ? 8 : value);
+    else if (k == "forest_four_lane_wgs") g.forest_four_lane_wgs = value < 0 ? 0 : value;
     else if (k == "fri_tail") g.fri_tail = value ? 1 : 0;
     else if (k == "small_divisor_direct") g.small_divisor_direct = value ? 1 : 0;
     else if (k == "verify_stage_kb") g.verify_stage_bytes = (size_t)(value < 16 ? 16 : value) << 10;           // (a chunk must hold one row of any depth)

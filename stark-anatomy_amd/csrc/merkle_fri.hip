@@ -2,6 +2,7 @@
 // Fiat-Shamir step of code/ip.py:18-25 on the host side of the library, and the openings of the query phase.
 #include "core.h"
 #include "merkle.cuh"
+#include "merkle_forest.cuh"
 #include "fri_tail.cuh"
 #include "merkle_verify.cuh"
 #include "transcript.h"
@@ -746,7 +747,18 @@ int sc_host_alloc(uint64_t bytes, void** out) {
     std::lock_guard<std::mutex> lk(g_mu);
     SCCHK(ensure_init());
     if (!out) return fail(SC_ERR_BAD_ARG, "null argument");
-    const size_t want = host_pool_size((size_t)bytes);
+    return host_pool_get((size_t)bytes, out);
+}
+int sc_host_free(void* p) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (!p) return SC_OK;
+    return host_pool_put(p);
+}
+extern "C++" {
+namespace sci {
+// the pool behind sc_host_alloc for the library's own pinned buffers (a forest's roots); g_mu held
+int host_pool_get(size_t bytes, void** out) {
+    const size_t want = host_pool_size(bytes);
     auto it = g_host_pool.find(want);
     void* p = nullptr;
     if (it != g_host_pool.end()) { p = it->second; g_host_pool.erase(it); }
@@ -755,15 +767,23 @@ int sc_host_alloc(uint64_t bytes, void** out) {
     *out = p;
     return SC_OK;
 }
-int sc_host_free(void* p) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (!p) return SC_OK;
+int host_pool_put(void* p) {
     auto it = g_host_live.find(p);
     if (it == g_host_live.end()) return fail(SC_ERR_BAD_ARG, "not a buffer of sc_host_alloc");
     g_host_pool.emplace(it->second, p);
     g_host_live.erase(it);
     return SC_OK;
 }
+// [p, p + bytes) lies inside one live buffer of the pool (a kernel may then store to it directly)
+bool host_pool_holds(const void* p, size_t bytes) {
+    auto it = g_host_live.upper_bound((void*)p);
+    if (it == g_host_live.begin()) return false;
+    --it;
+    const char* base = (const char*)it->first;
+    return (const char*)p >= base && (const char*)p + bytes <= base + it->second;
+}
+}  // namespace sci
+}  // extern "C++"
 
 // openings of codeword j of a commit phase of `rounds` codewords in sc_fri_prove_dev's answers: its own round's a and b; the c positions
 // of the round before are among them (c = that round's a, which is this round's a or b), except in the last codeword, which has no round of its own
@@ -1346,6 +1366,226 @@ int sc_merkle_free(sc_merkle_t* tree) {
     if (tree->slot >= 0) (void)merkle_root_wait(tree, true);  // a root still in flight: let it land, return the slot
     release_after_streams(tree->d_levels, (2 * tree->N - 1) * 64);
     delete tree;
+    return SC_OK;
+}
+
+}  // extern "C"
+
+// ---- forests of equal-sized Merkle trees (csrc/merkle_forest.cuh): the commitment of many codewords in one set of launches
+// (Merkle.commit_batch), a FRI round of many proofs -- the fold of fri.py:85 with one challenge per codeword, fused into the leaf
+// stage -- and the openings of the query phase at positions (tree, index).  The Fiat-Shamir step between the rounds stays with the
+// caller (Fri.prove_batch: every member has its own proof stream).
+namespace {
+uint64_t g_forests = 0, g_forest_trees = 0;      // sc_merkle_forest_stats
+
+// wait for an event by polling (a blocking wait that has gone to sleep costs tens of microseconds to wake up); lk: the library lock
+// to release meanwhile (not while a kernel in flight reads the shared scratch buffers)
+int wait_polled(std::unique_lock<std::mutex>* lk, hipEvent_t ev) {
+    if (lk) lk->unlock();
+    hipError_t e = hipErrorNotReady;
+    for (long spin = 0; spin < SPIN_POLLS / 64 && e == hipErrorNotReady; ++spin) e = hipEventQuery(ev);
+    if (e == hipErrorNotReady) e = hipEventSynchronize(ev);
+    if (lk) lk->lock();
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(SC_ERR_HIP, hipGetErrorString(e)); }
+    return SC_OK;
+}
+
+template <bool LEAVES, bool FOLD>
+void launch_climb(bool four_lane, unsigned wgs, hipStream_t st, const Fe* elems, uint64_t* levels, const ForestShape& s, int lvl0, int nlev, const ForestFold& fold,
+                  uint64_t* roots) {
+    if (four_lane) hipLaunchKernelGGL((forest_climb_kernel<LEAVES, true, FOLD>), dim3(wgs), dim3(256), 0, st, elems, levels, s, lvl0, nlev, fold, roots);
+    else hipLaunchKernelGGL((forest_climb_kernel<LEAVES, false, FOLD>), dim3(wgs), dim3(256), 0, st, elems, levels, s, lvl0, nlev, fold, roots);
+}
+
+void forest_release(sc_merkle_forest* f) {
+    if (f->done && !f->have_roots) { (void)hipEventSynchronize(f->done); (void)hipGetLastError(); }      // nothing may still write to the pinned roots when they are reused
+    if (f->d_levels) release_after_streams(f->d_levels, f->count * 2 * f->N * 64);
+    if (f->d_cm) release_after_streams(f->d_cm, f->count * sizeof(Fe));
+    if (f->h_roots) (void)host_pool_put(f->h_roots);
+    if (f->done) g_event_pool.push_back(f->done);
+    delete f;
+}
+
+// the launches of a forest over d_elems [count][N] (fold: the leaves are computed into d_elems = fold->out first); N >= 1 here
+// (a fold of two-element codewords leaves trees of one leaf).  alphas_cm: the fold's per-tree constants, staged behind the roots.
+int forest_build(const Fe* d_elems, uint64_t N, uint64_t count, const ForestFold* fold, const std::vector<Fe>* cm, sc_merkle_forest** out, hipStream_t st) {
+    sc_merkle_forest* f = new sc_merkle_forest{nullptr, N, count, ilog2(N)};
+    f->st = st;
+    const size_t tree_bytes = count * 2 * N * 64;
+    hipError_t e = pool_alloc((void**)&f->d_levels, tree_bytes);
+    if (e != hipSuccess) { f->d_levels = nullptr; forest_release(f); return fail(SC_ERR_HIP, hipGetErrorString(e)); }
+    int rc = host_pool_get(count * 64 + (fold ? count * sizeof(Fe) : 0), (void**)&f->h_roots);
+    if (rc != SC_OK) { f->h_roots = nullptr; forest_release(f); return rc; }
+    f->done = event_get();
+    if (!f->done) { forest_release(f); return fail(SC_ERR_HIP, "no event"); }
+    ForestFold ff{};
+    if (fold) {
+        ff = *fold;
+        e = pool_alloc((void**)&f->d_cm, count * sizeof(Fe));
+        if (e != hipSuccess) { f->d_cm = nullptr; forest_release(f); return fail(SC_ERR_HIP, hipGetErrorString(e)); }
+        Fe* staged = (Fe*)((uint8_t*)f->h_roots + count * 64);
+        memcpy(staged, cm->data(), count * sizeof(Fe));
+        e = hipMemcpyAsync(f->d_cm, staged, count * sizeof(Fe), hipMemcpyHostToDevice, st);      // one small copy for all the challenges
+        if (e != hipSuccess) { forest_release(f); return fail(SC_ERR_HIP, hipGetErrorString(e)); }
+        ff.c_m = f->d_cm;
+    }
+    const ForestShape s{N, count, f->logN};
+    int lvl = 0;
+    do {
+        const int nlev = forest_launch_levels(s.logN, lvl);
+        const uint64_t wgs = forest_launch_workgroups(s, lvl);
+        // one lane or four per compression on the levels of <= 64 parents per workgroup: four lanes shorten a lone wave's dependent
+        // chain at ~1.6 x the instructions, which pays only while the launch leaves the machine's SIMDs idle
+        const bool four = nlev >= 2 && wgs <= (uint64_t)g.forest_four_lane_wgs;
+        uint64_t* roots = lvl + nlev == s.logN ? f->h_roots : nullptr;
+        if (lvl == 0 && fold) launch_climb<true, true>(four, (unsigned)wgs, st, d_elems, f->d_levels, s, lvl, nlev, ff, roots);
+        else if (lvl == 0) launch_climb<true, false>(four, (unsigned)wgs, st, d_elems, f->d_levels, s, lvl, nlev, ff, roots);
+        else launch_climb<false, false>(four, (unsigned)wgs, st, d_elems, f->d_levels, s, lvl, nlev, ff, roots);
+        lvl += nlev;
+    } while (lvl < s.logN);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipEventRecord(f->done, st);
+    if (e != hipSuccess) { (void)hipStreamSynchronize(st); (void)hipGetLastError(); forest_release(f); return fail(SC_ERR_HIP, hipGetErrorString(e)); }
+    ++g_forests;
+    g_forest_trees += count;
+    *out = f;
+    return SC_OK;
+}
+
+int forest_args(uint64_t N, uint64_t count, uint64_t min_n) {
+    if (N < min_n || !is_pow2(N)) return fail(SC_ERR_BAD_ARG, "a forest's trees have a power of two of leaves, at least two");
+    if (count == 0) return fail(SC_ERR_BAD_ARG, "a forest has at least one tree");
+    if (count > SC_FOREST_MAX_LEAVES / N) return fail(SC_ERR_UNSUPPORTED, "forest larger than SC_FOREST_MAX_LEAVES leaves: split the batch");
+    return SC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int sc_merkle_forest_build_dev(const void* d_elems, uint64_t N, uint64_t count, sc_merkle_forest_t** forest, void* stream) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    if (!d_elems || !forest) return fail(SC_ERR_BAD_ARG, "null argument");
+    SCCHK(forest_args(N, count, 2));
+    return forest_build((const Fe*)d_elems, N, count, nullptr, nullptr, forest, pick_stream(stream));
+}
+
+int sc_fri_fold_forest_dev(const void* d_in, uint64_t N, uint64_t count, const uint64_t* alphas, const uint64_t offset[2], const uint64_t omega[2], void* d_out,
+                           sc_merkle_forest_t** forest, void* stream) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    if (!d_in || !d_out || !forest || !alphas || !offset || !omega) return fail(SC_ERR_BAD_ARG, "null argument");
+    SCCHK(forest_args(N, count, 2));
+    const Fe off = fe_from(offset), om = fe_from(omega);
+    if (fe_is_zero(off) || fe_is_zero(om)) return fail(SC_ERR_DIV_ZERO, "divide by zero");
+    hipStream_t st = pick_stream(stream);
+    PowTables* pw;
+    Fe i2o_m;
+    SCCHK(fold_constants(N, off, om, st, &pw, &i2o_m));
+    std::vector<Fe> cm(count);
+    for (uint64_t t = 0; t < count; ++t) cm[t] = mont_mul(to_mont(Fe{alphas[2 * t], alphas[2 * t + 1]}), i2o_m);     // alpha~ * (2 offset)^-1~ / R = c~ (fold_prepare)
+    ForestFold ff{(const Fe*)d_in, (Fe*)d_out, pw->lo, pw->hi, nullptr};
+    return forest_build((const Fe*)d_out, N / 2, count, &ff, &cm, forest, st);
+}
+
+int sc_merkle_forest_roots(sc_merkle_forest_t* forest, uint8_t* roots_out) {
+    std::unique_lock<std::mutex> lk(g_mu);
+    if (!forest || !roots_out) return fail(SC_ERR_BAD_ARG, "null argument");
+    SCCHK(ensure_init());
+    // (the handle belongs to the caller until this returns -- include/starkcore.h; what the wait needs is read before the lock goes)
+    const hipEvent_t done = forest->done;
+    const bool waited = !forest->have_roots;
+    if (waited) SCCHK(wait_polled(&lk, done));
+    if (waited) forest->have_roots = true;
+    memcpy(roots_out, forest->h_roots, 64 * forest->count);
+    return SC_OK;
+}
+uint64_t sc_merkle_forest_trees(const sc_merkle_forest_t* forest) { return forest ? forest->count : 0; }
+uint64_t sc_merkle_forest_leaves(const sc_merkle_forest_t* forest) { return forest ? forest->N : 0; }
+int sc_merkle_forest_free(sc_merkle_forest_t* forest) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (!forest) return SC_OK;
+    forest_release(forest);
+    return SC_OK;
+}
+int sc_merkle_forest_stats(uint64_t out[2]) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (!out) return fail(SC_ERR_BAD_ARG, "null argument");
+    out[0] = g_forests;
+    out[1] = g_forest_trees;
+    return SC_OK;
+}
+
+int sc_merkle_forest_query_dev(uint64_t n_pairs, const sc_merkle_forest_t* const* forests, const void* const* d_elems, const uint64_t* trees, const uint64_t* indices,
+                               const uint64_t* counts, void* elems_out, uint8_t* paths_out) {
+    std::unique_lock<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    if (n_pairs && (!forests || !d_elems || !counts)) return fail(SC_ERR_BAD_ARG, "null argument");
+    uint64_t total = 0;
+    size_t path_bytes = 0;
+    for (uint64_t p = 0; p < n_pairs; ++p) {
+        if (!forests[p] || !d_elems[p]) return fail(SC_ERR_BAD_ARG, "null forest or matrix");
+        if (counts[p] && (!trees || !indices)) return fail(SC_ERR_BAD_ARG, "null argument");
+        for (uint64_t i = 0; i < counts[p]; ++i)
+            if (trees[total + i] >= forests[p]->count || indices[total + i] >= forests[p]->N) return fail(SC_ERR_BAD_ARG, "cannot open invalid index");
+        total += counts[p];
+        path_bytes += counts[p] * 64 * (size_t)forests[p]->logN;
+    }
+    if (total == 0) return SC_OK;
+    if (!elems_out || (path_bytes && !paths_out)) return fail(SC_ERR_BAD_ARG, "null argument");
+    hipStream_t st = g.stream;
+    for (uint64_t p = 0; p < n_pairs; ++p)        // a forest built on another stream: ordered in front of the gather on the device
+        if (!forests[p]->have_roots && forests[p]->st != st) HIPCHK(hipStreamWaitEvent(st, forests[p]->done, 0));
+    const size_t idx_bytes = (total * 8 + 255) & ~255ull;
+    const size_t el_bytes = (total * sizeof(Fe) + 255) & ~255ull;
+    // answers go straight to pinned memory of sc_host_alloc's pool when that is what the caller gave (the stores cross the bus as they
+    // are made: no staging buffer, no copy engine behind the kernel); any other host pointer is served through device scratch
+    const bool direct = host_pool_holds(elems_out, total * sizeof(Fe)) && (!path_bytes || host_pool_holds(paths_out, path_bytes));
+    void* buf;
+    SCCHK(scratch(5, 2 * idx_bytes + (direct ? 0 : el_bytes + path_bytes) + 256, &buf));
+    uint64_t* d_trees = (uint64_t*)buf;
+    uint64_t* d_idx = (uint64_t*)((char*)buf + idx_bytes);
+    Fe* d_el = direct ? (Fe*)elems_out : (Fe*)((char*)buf + 2 * idx_bytes);
+    uint64_t* d_paths = direct ? (uint64_t*)paths_out : (uint64_t*)((char*)buf + 2 * idx_bytes + el_bytes);
+    SCCHK(upload(d_trees, trees, total * 8, st));
+    SCCHK(upload(d_idx, indices, total * 8, st));
+    uint64_t off = 0, poff = 0;
+    for (uint64_t p0 = 0; p0 < n_pairs; p0 += FOREST_QUERY_MAX_PAIRS) {      // one launch per FOREST_QUERY_MAX_PAIRS pairs (Fri.prove_batch: one launch)
+        ForestQuery Q;
+        Q.count = 0;
+        Q.total_threads = 0;
+        for (uint64_t p = p0; p < n_pairs && p < p0 + FOREST_QUERY_MAX_PAIRS; ++p) {
+            const uint64_t k = counts[p];
+            if (!k) continue;
+            ForestQueryPair& T = Q.p[Q.count++];
+            T.levels = forests[p]->d_levels;
+            T.elems = (const Fe*)d_elems[p];
+            T.N = forests[p]->N;
+            T.logN = (uint32_t)forests[p]->logN;
+            T.per_query = 4 * T.logN + 1;
+            T.thread_off = Q.total_threads;
+            T.idx_off = off;
+            T.path_off = poff;
+            Q.total_threads += k * T.per_query;
+            off += k;
+            poff += k * (uint64_t)T.logN;
+        }
+        if (!Q.count) continue;
+        hipLaunchKernelGGL(forest_query_kernel, dim3((unsigned)((Q.total_threads + 255) / 256)), dim3(256), 0, st, Q, (const uint64_t*)d_trees, (const uint64_t*)d_idx, d_el,
+                           d_paths);
+    }
+    HIPCHK(hipGetLastError());
+    if (direct) {
+        hipEvent_t ev = event_get();
+        if (!ev) { HIPCHK(hipStreamSynchronize(st)); return SC_OK; }
+        hipError_t e = hipEventRecord(ev, st);
+        int rc = e == hipSuccess ? wait_polled(nullptr, ev) : fail(SC_ERR_HIP, hipGetErrorString(e));
+        g_event_pool.push_back(ev);
+        return rc;
+    }
+    HIPCHK(hipMemcpyAsync(elems_out, d_el, total * sizeof(Fe), hipMemcpyDeviceToHost, st));
+    if (path_bytes) HIPCHK(hipMemcpyAsync(paths_out, d_paths, path_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     return SC_OK;
 }
 

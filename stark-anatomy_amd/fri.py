@@ -342,6 +342,102 @@ class Fri:
         self._query_all(codewords, top_level_indices, proof_stream, also_open)
         return top_level_indices
 
+    def _batchable(self, codewords):
+        """what the forest path serves: the main field, at least two rounds (fri.py:122 reads codewords[1]), a power-of-two length,
+        and members that are device codewords or sequences of residues below 2^128"""
+        N, rounds, s = self.domain_length, self.num_rounds(), self.num_colinearity_tests
+        if self.field.p != Field.P_MAIN or rounds < 2 or N < 2 or N & (N - 1) != 0 or s < 1 or s > (N >> (rounds - 1)):
+            return False
+        for cw in codewords:
+            if isinstance(cw, DeviceCodeword):
+                if cw.field.p != Field.P_MAIN:
+                    return False
+            elif not (type(cw[0]) is FieldElement and cw[0].field.p == Field.P_MAIN):       # (as Merkle._tree judges a list)
+                return False
+        return True
+
+    def prove_batch(self, codewords, proof_streams):
+        """[self.prove(codeword, stream) for ...] -- the same top-level indices, and after it every stream holds exactly what `prove`
+        would have pushed (serialize() is byte-identical, member by member) -- with the members' work on the device done together:
+        per round ONE Merkle forest over all members' codewords (csrc/merkle_forest.cuh; from the second round on its leaf stage
+        computes every member's fold with that member's alpha) and ONE wait for all roots; then one kernel for every opening of
+        every member.  The Fiat-Shamir step goes through each stream's own push / prover_fiat_shamir, so any ProofStream subclass
+        and streams that already hold objects are served.  Shapes the forest path does not serve go member by member through `prove`."""
+        codewords, proof_streams = list(codewords), list(proof_streams)
+        assert(len(codewords) == len(proof_streams)), "prove_batch needs one proof stream per codeword"
+        for codeword in codewords:
+            assert(self.domain_length == len(codeword)), "initial codeword length does not match length of initial codeword"
+        if not codewords:
+            return []
+        if not self._batchable(codewords):
+            return [self.prove(codeword, stream) for codeword, stream in zip(codewords, proof_streams)]
+        self._check_omega_order(self.domain_length)              # (before anything is enqueued)
+        step = max(1, _sc.FOREST_MAX_LEAVES // self.domain_length)
+        indices = []
+        for lo in range(0, len(codewords), step):
+            indices += self._prove_forest(codewords[lo:lo + step], proof_streams[lo:lo + step])
+        return indices
+
+    def _prove_forest(self, members, streams):
+        rounds, s, N, K = self.num_rounds(), self.num_colinearity_tests, self.domain_length, len(members)
+        # commit phase (fri.py:66-94) for all members: forest r holds the members' r-th codewords
+        forests = [_sc.MerkleForest.build(_sc.CodewordMatrix.from_members(members))]
+        omega, offset = self.omega, self.offset
+        for r in range(rounds):
+            roots = forests[r].roots                             # one wait for K roots
+            for stream, root in zip(streams, roots):
+                stream.push(root)
+            if r == rounds - 1:
+                break
+            alphas = [self.field.sample(stream.prover_fiat_shamir()).value for stream in streams]
+            forests.append(_sc.MerkleForest.fold_build(forests[r].matrix, alphas, offset.value, omega.value))
+            omega, offset = omega ^ 2, offset ^ 2
+        # entries are created once per (member, codeword, index): the transcript is pickled by object identity (DeviceCodeword._entries)
+        n_last = N >> (rounds - 1)
+        last_raw = forests[-1].matrix.to_bytes()
+        holders, top = [], []
+        for m, (codeword, stream) in enumerate(zip(members, streams)):
+            first = codeword if isinstance(codeword, DeviceCodeword) else DeviceCodeword(None, self.field, elements=list(codeword))
+            middle = [DeviceCodeword(None, self.field) for _ in range(rounds - 2)]
+            last = DeviceCodeword(None, self.field, elements=[FieldElement(v, self.field) for v in _sc.unpack(last_raw[16 * n_last * m:16 * n_last * (m + 1)], n_last)])
+            holders.append([first] + middle + [last])
+            stream.push(last._full)                              # the last codeword in the clear (fri.py:91)
+            top.append(self.sample_indices(stream.prover_fiat_shamir(), N // 2, n_last, s))
+        # query phase (fri.py:124-128): codeword j opens its round's a and b positions and the c positions of the round before
+        per_round, requests = [], [[] for _ in range(rounds)]
+        for m in range(K):
+            mine, current = [], top[m]
+            for j in range(rounds - 1):
+                half = N >> (j + 1)
+                current = [index % half for index in current]
+                mine.append(current)
+            per_round.append(mine)
+            for j in range(rounds):
+                request = []
+                if j < rounds - 1:
+                    request += mine[j] + [index + (N >> (j + 1)) for index in mine[j]]
+                if j > 0:
+                    request += mine[j - 1]
+                requests[j] += [(m, index) for index in request]
+        fetched = _sc.query_forests(forests, requests)           # ONE launch for every opening of every member
+        for m, stream in enumerate(streams):
+            opened = []
+            for j in range(rounds):
+                values, paths = fetched[j]
+                k = len(requests[j]) // K
+                request = [index for _, index in requests[j][k * m:k * (m + 1)]]
+                opened.append((holders[m][j]._entries(request, values[k * m:k * (m + 1)]), paths[k * m:k * (m + 1)]))
+            for i in range(rounds - 1):
+                entries, paths = opened[i]
+                next_entries, next_paths = opened[i + 1]
+                c_at = 2 * s if i + 2 < rounds else 0
+                for triple in zip(entries[:s], entries[s:2 * s], next_entries[c_at:c_at + s]):
+                    stream.push(triple)
+                for trio in zip(paths[:s], paths[s:2 * s], next_paths[c_at:c_at + s]):
+                    for path in trio:
+                        stream.push(path)
+        return top
+
     def _prove_in_library(self, codeword, proof_stream, also_open):
         """fri.py:115-130 as ONE library call (sc_fri_prove_dev): commit phase, the challenge over the transcript with the last
         codeword, the sampled indices, and one kernel that writes every opening of the proof into pinned host memory.  What comes

@@ -7,7 +7,8 @@ instead of the reference's full rebuild per call.  The raw-digest variants (`com
 """
 from hashlib import blake2b
 
-from starkcore import DeviceCodeword, MerkleTree
+from starkcore import CodewordMatrix, DeviceCodeword, MerkleForest, MerkleTree
+import starkcore as _sc
 
 
 class Merkle:
@@ -30,6 +31,27 @@ class Merkle:
     def commit(data_array):
         assert(len(data_array) & (len(data_array) - 1) == 0), "length must be power of two"
         return Merkle._tree(data_array).root
+
+    def commit_batch(data_arrays):
+        """[Merkle.commit(a) for a in data_arrays], the arrays of one length as ONE forest (csrc/merkle_forest.cuh: one set of launches
+        and one wait for all their roots); a batch above the library's forest limit is split"""
+        data_arrays = list(data_arrays)
+        roots, by_length = [None] * len(data_arrays), {}
+        for k, a in enumerate(data_arrays):
+            assert(len(a) & (len(a) - 1) == 0), "length must be power of two"
+            if len(a) < 2:
+                roots[k] = Merkle.commit(a)
+                continue
+            assert(isinstance(a, DeviceCodeword) or a[0].field.p <= (1 << 128)), "the MI355X Merkle kernels take residues below 2^128 only"
+            by_length.setdefault(len(a), []).append(k)
+        for n, members in by_length.items():
+            step = max(1, _sc.FOREST_MAX_LEAVES // n)
+            for lo in range(0, len(members), step):
+                part = members[lo:lo + step]
+                forest = MerkleForest.build(CodewordMatrix.from_members([data_arrays[k] for k in part]))
+                for k, root in zip(part, forest.roots):
+                    roots[k] = root
+        return roots
 
     def open_(index, leafs):
         assert(len(leafs) & (len(leafs) - 1) == 0), "length must be power of two"

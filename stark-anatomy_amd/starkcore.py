@@ -22,6 +22,7 @@ SC_ERR_ROOT_NOT_PRIMITIVE = -4
 SC_ERR_DIV_ZERO = -5
 SC_ERR_UNSUPPORTED = -7
 SC_ERR_TIMEOUT = -9
+FOREST_MAX_LEAVES = 1 << 24        # SC_FOREST_MAX_LEAVES of include/starkcore.h: leaves of the largest forest an entry takes
 
 # every symbol include/starkcore.h declares: (restype, argtypes)
 SIGNATURES = {
@@ -128,6 +129,14 @@ SIGNATURES = {
     "sc_fri_fold_slab_build_dev": (_int, [_vp, _u64, _u64, _u64, _u64, _vp, _vp, _vp, _vp, ctypes.POINTER(_vp), _vp]),
     "sc_merkle_leaves": (_u64, [_vp]),
     "sc_merkle_free": (_int, [_vp]),
+    "sc_merkle_forest_build_dev": (_int, [_vp, _u64, _u64, ctypes.POINTER(_vp), _vp]),
+    "sc_fri_fold_forest_dev": (_int, [_vp, _u64, _u64, _vp, _vp, _vp, _vp, ctypes.POINTER(_vp), _vp]),
+    "sc_merkle_forest_roots": (_int, [_vp, _vp]),
+    "sc_merkle_forest_trees": (_u64, [_vp]),
+    "sc_merkle_forest_leaves": (_u64, [_vp]),
+    "sc_merkle_forest_free": (_int, [_vp]),
+    "sc_merkle_forest_query_dev": (_int, [_u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sc_merkle_forest_stats": (_int, [_vp]),
     "sc_mpoly_eval_dev": (_int, [_vp, _u64, _u64, _vp, _vp, _u64, _vp, _vp]),
     "sc_mpoly_eval_ex_dev": (_int, [_vp, _u64, _u64, _vp, _vp, _u64, _vp, _int, _vp]),
     "sc_mpoly_eval_rot_dev": (_int, [_vp, _u64, _u64, _vp, _vp, _u64, _vp, _int, _vp, _vp, _vp]),
@@ -810,6 +819,134 @@ class MerkleTree:
             self.free()
         except Exception:
             pass
+
+
+class CodewordMatrix:
+    """K equal-length codewords as ONE device matrix [K][n], row t = member t: what a MerkleForest is built over."""
+
+    def __init__(self, count, n, vec=None):
+        self.count, self.n = int(count), int(n)
+        self.vec = vec if vec is not None else DeviceVector(self.count * self.n)
+
+    @classmethod
+    def from_members(cls, members):
+        """members: DeviceCodewords (device copies), packed bytes or sequences of FieldElements (uploads; ONE upload when no member is
+        on the device yet), all of one length"""
+        members = list(members)
+        n = len(members[0]) // 16 if isinstance(members[0], (bytes, bytearray)) else len(members[0])
+        rows = []
+        for m in members:
+            if isinstance(m, DeviceCodeword):
+                rows.append(None)
+            else:
+                rows.append(bytes(m) if isinstance(m, (bytes, bytearray)) else pack(list(map(_value_of, m))))
+                assert len(rows[-1]) == 16 * n, "the members of a codeword matrix have one length"
+        if all(r is not None for r in rows):
+            return cls(len(members), n, DeviceVector.from_bytes(b"".join(rows)))
+        matrix = cls(len(members), n)
+        for t, (m, r) in enumerate(zip(members, rows)):
+            if r is None:
+                assert len(m) == n, "the members of a codeword matrix have one length"
+                if n:
+                    _check(lib().sc_memcpy_dev(_vp(matrix.vec.ptr + 16 * n * t), m.vec.ptr, n, None))
+            elif n:
+                _check(lib().sc_vec_upload(matrix.vec._h, n * t, r, n))
+        return matrix
+
+    def to_bytes(self):
+        return self.vec.to_bytes()
+
+
+class MerkleForest:
+    """Owner of an sc_merkle_forest_t: the trees of all rows of a CodewordMatrix, built by one set of launches and resident in HBM.
+    `roots` waits for the build (once, for all of them); `open(tree, index)` is a gather."""
+
+    def __init__(self, handle, matrix):
+        self._h, self.matrix = handle, matrix
+        self.count, self.n = matrix.count, matrix.n
+        self.depth = self.n.bit_length() - 1
+        self._roots = None
+
+    @classmethod
+    def build(cls, matrix):
+        h = _vp()
+        _check(lib().sc_merkle_forest_build_dev(matrix.vec.ptr, matrix.n, matrix.count, ctypes.byref(h), None))
+        return cls(h, matrix)
+
+    @classmethod
+    def fold_build(cls, matrix, alphas, offset, omega):
+        """one round of Fri.commit for every row (fri.py:85 with the row's own alpha, then the forest of the folded rows), enqueued;
+        alphas / offset / omega: int residues"""
+        out = CodewordMatrix(matrix.count, matrix.n // 2)
+        h = _vp()
+        _check(lib().sc_fri_fold_forest_dev(matrix.vec.ptr, matrix.n, matrix.count, pack(alphas), fe_bytes(offset), fe_bytes(omega), out.vec.ptr,
+                                            ctypes.byref(h), None))
+        return cls(h, out)
+
+    @property
+    def roots(self):
+        if self._roots is None:
+            out = ctypes.create_string_buffer(64 * self.count)
+            _check(lib().sc_merkle_forest_roots(self._h, out))
+            raw = out.raw
+            self._roots = [raw[64 * t:64 * t + 64] for t in range(self.count)]
+        return self._roots
+
+    def open(self, tree, index):
+        return self.query([(tree, index)])[1][0]
+
+    def query(self, positions):
+        """elements (int residues) and authentication paths at positions [(tree, index)]"""
+        return query_forests([self], [positions])[0]
+
+    def free(self):
+        if self._h is not None and _lib is not None:
+            _lib.sc_merkle_forest_free(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def forest_stats():
+    """(forests built, trees in them) so far"""
+    out = (ctypes.c_uint64 * 2)()
+    _check(lib().sc_merkle_forest_stats(out))
+    return out[0], out[1]
+
+
+def query_forests(forests, requests):
+    """openings of several forests in ONE device round trip: requests[p] = [(tree, index)] into forests[p]; returns per pair
+    (int residues, paths as lists of fresh 64-byte digests).  The kernel writes into pinned memory of the library's pool."""
+    n = len(forests)
+    try:
+        trees = array.array("Q", [t for req in requests for t, _ in req])
+        flat = array.array("Q", [i for req in requests for _, i in req])
+    except OverflowError:
+        raise AssertionError("cannot open invalid index")
+    total = len(flat)
+    if total == 0:
+        return [([], []) for _ in forests]
+    depths = [f.depth for f in forests]
+    el_bytes = (16 * total + 255) & ~255
+    path_bytes = sum(64 * d * len(req) for d, req in zip(depths, requests))
+    answers = HostBuffer(el_bytes + max(path_bytes, 64))
+    _check(lib().sc_merkle_forest_query_dev(n, (_vp * n)(*[f._h for f in forests]), (_vp * n)(*[f.matrix.vec.ptr for f in forests]),
+                                            (ctypes.c_uint64 * total).from_buffer(trees), (ctypes.c_uint64 * total).from_buffer(flat),
+                                            (ctypes.c_uint64 * n)(*[len(req) for req in requests]), answers.ptr, _vp(answers.ptr.value + el_bytes)))
+    data = answers.array
+    values = unpack(data[:16 * total].tobytes(), total)
+    view = memoryview(data[el_bytes:].tobytes())
+    out, vo, po = [], 0, 0
+    for req, d in zip(requests, depths):
+        k = len(req)
+        out.append((values[vo:vo + k], _path_lists(view, po, d, k)))
+        vo += k
+        po += 64 * k * d
+    return out
 
 
 import operator as _operator
