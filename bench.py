@@ -7,13 +7,13 @@
 N = 1: workload = BASELINE configs[1]: forward + inverse 2^20-point NTT, data resident in HBM, over one BATCH of independent
        columns per step (--columns, default 64: the registers of a trace, code/fast_stark.py:84-104; 1 GiB per vector, well past
        the 256 MiB Infinity Cache) through sc_ntt_columns_dev -- one set of launches per direction;
-       value = 2 * n * columns * K / elapsed  (field elements / s).  `one_column_at_a_time` carries the same transforms issued one
-       column after the other with sc_ntt_dev (--columns 1 makes that the step: the headline of rounds 1-5),
+       value = 2 * n * columns * K / elapsed  (field elements / s).  With --full, `one_column_at_a_time` carries the same transforms
+       issued one column after the other with sc_ntt_dev (--columns 1 makes that the step: the headline of rounds 1-5),
        `extras.ntt_2p24_strong` the N = 1 member of the north_star series (forward + inverse at 2^24, with `frac`).
 N > 1: the north_star line: forward + inverse 2^24-point NTT as a four-step transform sharded over the ranks (STRONG scaling:
        the same 2^24 for every N; `--scaling weak` times 2^21 elements per GPU instead, `--log2n` any size), one corner turn per
        transform (stark-anatomy_amd/sharded.py).  A bare `python bench.py --gpus N` re-launches itself under
-       torch.distributed.run; the line also carries the whole BASELINE configs[4] call census on the sharded layout
+       torch.distributed.run; with --full the line also carries the whole BASELINE configs[4] call census on the sharded layout
        (extras.stark_census_sharded); `--workload stark_census` makes that the timed step.  With fewer GPUs than ranks the
        ranks share devices and exchange through gloo (labelled functional run).
        The forms of the corner turn (torch.distributed or the library's own RCCL communicator; one blocking exchange or row
@@ -21,11 +21,18 @@ N > 1: the north_star line: forward + inverse 2^24-point NTT as a four-step tran
        one is measured (`config.corner_turn` names it and lists the probe times).
 
 Timing: W untimed steps, then exactly K steps between barrier + torch.cuda.synchronize(), max over ranks -> `value`,
-`ms_per_step`, `roofline` (launch duration by HIP events on the launch stream).  The same window is then repeated after
-CLOCK_RAMP_MS of untimed steps and reported beside it as `clock_ramp.steady_state` (information: a short window straight after
-start-up runs at the board's idle clock).  `cpu_baseline` and `extras` (Fri.prove, LDE, census, Merkle, ...) follow, rank 0, N = 1.
+`ms_per_step`, `roofline` (launch duration by HIP events on the launch stream).  A plain run does that and no more: it sets up,
+warms up, times the K steps, writes --dump-outputs and prints its line.
 
---dump-outputs DIR (N = 1, ntt): after the timed windows, the last step's forward and inverse outputs go to DIR/ntt_forward.npy
+--full adds everything else the benchmark measures or checks, as before: the same window repeated after CLOCK_RAMP_MS of untimed
+steps, reported beside the first as `clock_ramp.steady_state` (information: a short window straight after start-up runs at the
+board's idle clock); the round trip compared bit for bit and the forward transform's SHA-256 against the reference's
+(tests/golden/ntt_big.json), a mismatch ending the run non-zero; `one_column_at_a_time`; `cpu_baseline` and `extras` (Fri.prove,
+LDE, census, Merkle, other sizes, ...), rank 0, N = 1; for N > 1 the stage breakdown, the other member of strong / weak, the
+sharded call census and the sharded prover.  --no-extras and --no-cpu-baseline take their legs out of a --full run.  (N > 1
+compares the round trip in a plain run too: its verdict decides which form of the corner turn the line reports.)
+
+--dump-outputs DIR (N = 1, ntt): after the timed window(s), the last step's forward and inverse outputs go to DIR/ntt_forward.npy
 and DIR/ntt_inverse.npy (a fixed, seeded sample of 2^19 elements each, as 32-bit limbs in float64; positions in
 DIR/element_index.npy).  The inputs depend on the arguments alone, so two builds can be compared output for output.
 """
@@ -152,9 +159,13 @@ def main():
                     help="N = 1: independent columns per step (default 64 at 2^20, fewer above so that a vector stays at 1 GiB; 1 = one "
                          "transform at a time through sc_ntt_dev, the step of rounds 1-5)")
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE", help="sc_set_tuning(KEY, VALUE) before anything runs (A/B of a library knob in bench conditions; the line carries it in config.tune)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the window repeated at the steady clock, the round-trip and reference checks, the lone-column "
+                         "leg, cpu_baseline and extras (N > 1: stage breakdown, other member of strong / weak, sharded census and prover); "
+                         "a run without it sets up, warms up, times the steps and prints its line")
     ap.add_argument("--cpu-sample-log2n", type=int, default=18)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the Fri.prove / LDE / census side measurements")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the Fri.prove / LDE / census side measurements")
     ap.add_argument("--force-sharded", action="store_true", help="run the multi-GPU four-step code path (process group, corner turn) even with one rank")
     ap.add_argument("--scaling", choices=("strong", "weak"), default="strong",
                     help="N > 1: strong = the north_star's 2^24 transform for every N (default); weak = 2^21 elements per GPU")
@@ -328,18 +339,24 @@ def main():
     # 79-82 us per 2^20 pair for the first ~5 ms after idle, 69 us from then on), so a short window straight after start-up
     # measures the clock ramp as much as the transform.  `value` is the contract's window, run first, straight after start-up;
     # then CLOCK_RAMP_MS of the same untimed steps and the same window once more, reported beside it as
-    # "clock_ramp.steady_state" (information only).  With the default 200 + 2000 steps the two agree to ~1 %.
+    # "clock_ramp.steady_state" (information only; --full).  With the default 200 + 2000 steps the two agree to ~1 %.
     elapsed, ev_ms = timed_window()
     ramp_steps = max(1, min(20000, int(math.ceil(CLOCK_RAMP_MS * 1e-3 / (elapsed / args.steps)))))
-    for _ in range(ramp_steps):
-        step()
-    steady_elapsed, steady_ev_ms = timed_window()
+
+    def steady_window():
+        for _ in range(ramp_steps):
+            step()
+        return timed_window()
+
+    steady_elapsed, steady_ev_ms = steady_window() if args.full else (None, None)
     dumped = dump_outputs(args.dump_outputs, {"ntt_forward": y, "ntt_inverse": z}) if args.dump_outputs else None
 
-    # correctness guard inside the bench: the round trip must reproduce the input bit for bit
-    ok = bool(torch.equal(z, x))
+    # correctness guard inside the bench (--full; N > 1 always: the verdict picks the corner turn that is reported): the round
+    # trip must reproduce the input bit for bit
+    checked = args.full or sharded
+    ok = bool(torch.equal(z, x)) if checked else True
     one_column = None
-    if not sharded and cols > 1 and not args.no_extras:
+    if args.full and not sharded and cols > 1 and not args.no_extras:
         # (a side leg like `extras`: --no-extras, which the profiling commands use, keeps every launch of the run a launch of the batch)
         # the same kernels with the columns issued one after the other (sc_ntt_dev on column 0: the step of rounds 1-5), at the clock
         # the windows above have brought the board to
@@ -387,9 +404,8 @@ def main():
             corner_probes["discarded_after_timed_run"] = discarded["chosen"]
             corner_probes["probes"] = [q for q in discarded["probes"] if "direct store" in q["form"]] + corner_probes["probes"]
             elapsed, ev_ms = timed_window()
-            for _ in range(ramp_steps):
-                step()
-            steady_elapsed, steady_ev_ms = timed_window()
+            if args.full:
+                steady_elapsed, steady_ev_ms = steady_window()
             flag = torch.tensor([1 if torch.equal(z, x) else 0], dtype=torch.int32, device=dev if backend == "nccl" else "cpu")
             dist.all_reduce(flag, op=dist.ReduceOp.MIN)
             ok = int(flag.item()) == 1
@@ -397,7 +413,7 @@ def main():
     # code/ntt.py's own output for this very input (synth seed 1, n = 2^20, Field.primitive_nth_root), generated by
     # tests/golden/make_golden.py from the imported reference (BASELINE configs[1]: "bit-exact vs code/ntt.py")
     reference_sha = None
-    if not sharded and world == 1:
+    if args.full and not sharded and world == 1:
         try:
             import hashlib
             gold = json.load(open(os.path.join(REPO, "tests", "golden", "ntt_big.json")))
@@ -428,7 +444,7 @@ def main():
         legs["seconds"][name] = round(time.perf_counter() - legs.pop("_t"), 2)
 
     stages = weak = None
-    if sharded and args.workload == "ntt":
+    if args.full and sharded and args.workload == "ntt":
         # where the time of the sharded transform goes (per stage, max over ranks), and the OTHER member of the pair strong / weak:
         # the first multi-GPU run should need no second run to be read
         leg("stage_breakdown", float("inf"))          # (always runs; booked like the others)
@@ -466,7 +482,7 @@ def main():
             weak = {"error": repr(e)[:300]}
 
     census = prover = None
-    if sharded and world > 1 and not args.no_extras:
+    if args.full and sharded and world > 1 and not args.no_extras:
         # the whole config-5 pipeline on the same ranks, once warm and once timed (all ranks take part; rank 0 reports)
         if leg("stark_census_sharded", 0.5):
             try:
@@ -515,13 +531,8 @@ def main():
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
             "scaling": scaling_label, "vs_baseline": None, "dtype": "u128", "data": "synthetic",
             "config": {"workload": workload, "log2n": log2n, "columns_per_step": (cols if not sharded else 1), "elements_per_step": 2 * total_n, "parallelism": parallelism,
-                       "passes_per_transform": passes, "roundtrip_bit_exact": ok, "forward_sha256_equals_reference_output": reference_sha,
+                       "passes_per_transform": passes, "roundtrip_bit_exact": ok if checked else None, "forward_sha256_equals_reference_output": reference_sha,
                        **({"tune": args.tune} if args.tune else {}), **({"dumped_outputs": dumped} if dumped else {})},
-            "clock_ramp": {"untimed_steps_between_windows": ramp_steps, "target_ms": CLOCK_RAMP_MS,
-                           "steady_state": {"value": 2.0 * total_n * args.steps / steady_elapsed, "ms_per_step": 1e3 * steady_elapsed / args.steps,
-                                            "avg_launch_us": steady_ev_ms * 1e3 / (args.steps * launches_per_step),
-                                            "roofline_frac": alg_bytes_per_launch / ((steady_ev_ms * 1e-3) / (args.steps * launches_per_step)) / 1e9 / HBM_PEAK_GBS},
-                           "note": "information only: the same W + K window repeated after the board has clocked up (`value` is the first window, straight after start-up)"},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                          "traffic": measured_traffic(pmc_key) if not sharded else None, "kernel": "ntt_pass_kernel" if not sharded else "whole sharded transform (per rank)", "avg_launch_us": avg_launch_s * 1e6,
                          "alg_bytes_per_launch": alg_bytes_per_launch,
@@ -533,6 +544,12 @@ def main():
                                  "12.8 us for the lone column's kernel, which takes 17.4: one "
                                  "workgroup per CU with every CU in the same phase), see DESIGN.md 3.1"},
         }
+        if args.full:
+            out["clock_ramp"] = {"untimed_steps_between_windows": ramp_steps, "target_ms": CLOCK_RAMP_MS,
+                                 "steady_state": {"value": 2.0 * total_n * args.steps / steady_elapsed, "ms_per_step": 1e3 * steady_elapsed / args.steps,
+                                                  "avg_launch_us": steady_ev_ms * 1e3 / (args.steps * launches_per_step),
+                                                  "roofline_frac": alg_bytes_per_launch / ((steady_ev_ms * 1e-3) / (args.steps * launches_per_step)) / 1e9 / HBM_PEAK_GBS},
+                                 "note": "information only: the same W + K window repeated after the board has clocked up (`value` is the first window, straight after start-up)"}
         if sharded:
             # the N > 1 line prices a rank's WHOLE transform (column stage, corner turn, row stage), not one launch of one kernel: no
             # per-launch PMC figures belong here (they are the single-GPU kernel's, in the N = 1 line and profiles/); what bounds this
@@ -564,7 +581,7 @@ def main():
             out.setdefault("extras", {})["stark_census_sharded"] = census
         if prover is not None:
             out.setdefault("extras", {})["stark_prove_sharded"] = prover
-        if not args.no_extras and not sharded and world == 1:
+        if args.full and not args.no_extras and not sharded and world == 1:
             try:
                 out["extras"] = extras(sc, lib, stream)
             except Exception as e:       # side measurements never invalidate the headline
@@ -578,7 +595,7 @@ def main():
                                             "note": "NOT the headline: two independent 2^20 forward+inverse transforms on two HIP streams; details in extras"}
         if one_column is not None:
             out["one_column_at_a_time"] = one_column
-        if not args.no_cpu_baseline and not sharded and world == 1:
+        if args.full and not args.no_cpu_baseline and not sharded and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.cpu_sample_log2n)
         emit(out)
     if sharded:

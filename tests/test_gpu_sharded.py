@@ -399,10 +399,10 @@ def _run_bench(args, timeout=900, env_extra=None):
 
 
 def test_bench_headline_line_is_the_contract_and_matches_the_reference(sc):
-    """the N = 1 headline exactly as the driver runs it (BASELINE configs[1]): the JSON contract's keys, `roofline` and -- with
+    """the N = 1 headline (BASELINE configs[1]) with --full: the JSON contract's keys, `roofline` and -- with
     cpu_baseline switched off here for time -- a forward transform whose SHA-256 equals the one the reference's code/ntt.py produced
     for the same input (tests/golden/ntt_big.json)"""
-    out = _run_bench(["--gpus", "1", "--steps", "5", "--warmup", "2", "--no-extras", "--no-cpu-baseline"])
+    out = _run_bench(["--gpus", "1", "--steps", "5", "--warmup", "2", "--full", "--no-extras", "--no-cpu-baseline"])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline"):
         assert key in out, key
     assert out["metric"] == "ntt_field_elements_per_sec" and out["n_gpus"] == 1 and out["steps"] == 5 and out["dtype"] == "u128"
@@ -417,17 +417,34 @@ def test_bench_headline_line_is_the_contract_and_matches_the_reference(sc):
     assert abs(out["value"] - 2 * cols * (1 << 20) * 5 / (out["ms_per_step"] * 5e-3)) < 1e-3 * out["value"]
     assert "one_column_at_a_time" not in out                                                # a side leg, off with --no-extras
     # ... and --columns 1 makes that the step again
-    out1 = _run_bench(["--gpus", "1", "--steps", "5", "--warmup", "2", "--no-extras", "--no-cpu-baseline", "--columns", "1"])
+    out1 = _run_bench(["--gpus", "1", "--steps", "5", "--warmup", "2", "--full", "--no-extras", "--no-cpu-baseline", "--columns", "1"])
     assert out1["config"]["columns_per_step"] == 1 and out1["config"]["forward_sha256_equals_reference_output"] is True
     assert "one_column_at_a_time" not in out1 and out1["roofline"]["traffic"] > out1["roofline"]["alg_bytes_per_launch"]
     assert abs(out1["value"] - 2 * (1 << 20) * 5 / (out1["ms_per_step"] * 5e-3)) < 1e-3 * out1["value"]
+
+
+def test_bench_plain_run_prints_the_headline_and_leaves_the_side_legs_to_full(sc):
+    """`bench.py --gpus 1 --steps K --warmup W` sets up, warms up, times its K steps and prints the line: the contract's keys with
+    the meaning they have under --full (value from ms_per_step, the batch of 64 columns), `roofline` from the same window, and
+    none of what --full adds -- no second window, no checks, no lone-column leg, no extras, no CPU baseline"""
+    out = _run_bench(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline"):
+        assert key in out, key
+    assert out["metric"] == "ntt_field_elements_per_sec" and out["unit"] == "field-elements/s" and out["higher_is_better"] is True
+    assert out["n_gpus"] == 1 and out["steps"] == 5 and out["warmup"] == 2 and out["dtype"] == "u128"
+    assert out["config"]["workload"] == "ntt_fwd_inv_2^20_1gpu" and out["config"]["columns_per_step"] == 64
+    assert abs(out["value"] - 2 * 64 * (1 << 20) * 5 / (out["ms_per_step"] * 5e-3)) < 1e-3 * out["value"]
+    assert out["roofline"]["avg_launch_us"] > 0 and abs(out["roofline"]["frac"] - out["roofline"]["achieved"] / out["roofline"]["peak"]) < 1e-12
+    for key in ("clock_ramp", "one_column_at_a_time", "extras", "two_columns_in_flight", "cpu_baseline"):
+        assert key not in out, key
+    assert out["config"]["roundtrip_bit_exact"] is None and out["config"]["forward_sha256_equals_reference_output"] is None
 
 
 def test_bench_two_ranks_print_the_north_star_record(sc):
     """`python bench.py --gpus 2` times the north_star's transform -- forward + inverse at 2^24, strong scaling --
     and carries it as extras.ntt_2p24_strong with the roofline fraction, the bytes exchanged, the form of the corner turn and a
     round trip checked on every element (on this box: two ranks sharing the GPU over gloo, labelled functional)."""
-    out = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--no-extras", "--no-cpu-baseline"])
+    out = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-extras", "--no-cpu-baseline"])
     assert out["n_gpus"] == 2 and out["scaling"] == "strong" and out["config"]["log2n"] == 24
     assert "ntt_fwd_inv_2^24_fourstep_2gpu" == out["config"]["workload"] and "north_star" in out["config"]["series"]
     rec = out["extras"]["ntt_2p24_strong"]
@@ -471,7 +488,7 @@ def test_bench_time_budget_drops_the_side_legs_in_the_stated_order(sc):
     """`--budget-s`: the legs behind the headline start only while the command has used less than a fraction of its budget (other
     member of strong / weak 0.35, census 0.5, prover 0.7), every rank taking the same branch; with a budget the set-up alone
     exhausts all three are dropped and named, and the headline, its stage breakdown and the north_star record are still there."""
-    out = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--budget-s", "1"])
+    out = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--budget-s", "1"])
     legs = out["config"]["legs"]
     assert legs["dropped_for_the_budget"] == ["other_member_of_strong_weak", "stark_census_sharded", "stark_prove_sharded"]
     assert "ntt_other_scaling" not in out["extras"] and "stark_census_sharded" not in out["extras"] and "stark_prove_sharded" not in out["extras"]
@@ -483,7 +500,7 @@ def test_bench_bare_launch_two_ranks_and_census_parity(sc):
     """`python bench.py --gpus 2` must launch itself (one rank per GPU; on this 1-GPU box the two ranks share
     the device and exchange through gloo, labelled as such), carry the config-5 census on the sharded layout, and the census
     must produce the SAME commitments and the SAME proof whatever the world size -- and the oracle's commitment."""
-    out = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--log2n", "16", "--no-cpu-baseline"])
+    out = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--log2n", "16", "--full", "--no-cpu-baseline"])
     assert out["n_gpus"] == 2 and out["config"]["world_size"] == 2 and out["config"]["roundtrip_bit_exact"] is True
     assert "fourstep_2gpu" in out["config"]["workload"] and out["value"] > 0
     assert "gloo" in out["config"]["collective_backend"] and "NOT a scaling measurement" in out["config"]["collective_backend"]

@@ -4,7 +4,7 @@ O=gpurun_out/ab_bench; mkdir -p $O
 for i in 1 2 3; do
   for which in old new; do
     if [ $which = old ]; then export STARKCORE_LIB=$GRAFT_REPO_ROOT/stark-anatomy_amd/libstarkcore_ab.so; else unset STARKCORE_LIB; fi
-    timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/${which}_$i.json 2> $O/${which}_$i.err
+    timeout 600 python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline > $O/${which}_$i.json 2> $O/${which}_$i.err
     python - $O/${which}_$i.json $which $i <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); e = d["extras"]

@@ -4,9 +4,9 @@
 O=gpurun_out/${1:-record}; mkdir -p $O
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-(timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 2>$O/bench_s20.err | tail -1) > $O/bench_default_steps20_driver_style.json
-(timeout 900 python bench.py --no-extras --no-cpu-baseline 2>$O/bench_default.err | tail -1) > $O/bench_default_2000steps.json
-(timeout 900 python bench.py --no-extras --no-cpu-baseline --columns 1 2>$O/bench_default_1col.err | tail -1) > $O/bench_one_column_2000steps.json
+(timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 --full 2>$O/bench_s20.err | tail -1) > $O/bench_default_steps20_driver_style.json
+(timeout 900 python bench.py --full --no-extras --no-cpu-baseline 2>$O/bench_default.err | tail -1) > $O/bench_default_2000steps.json
+(timeout 900 python bench.py --full --no-extras --no-cpu-baseline --columns 1 2>$O/bench_default_1col.err | tail -1) > $O/bench_one_column_2000steps.json
 # kernel stats of the same commands: the headline (2^20 x 64 columns per step), one 2^20 column at a time, one 2^24 column at a time
 (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $R/$O/kt20x64 -o b --output-format csv -- python $R/bench.py --no-extras --no-cpu-baseline 2>$R/$O/kt20x64.err | tail -1 > $R/$O/bench_2p20x64_under_rocprof.json)
 (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $R/$O/kt20 -o b --output-format csv -- python $R/bench.py --no-extras --no-cpu-baseline --columns 1 2>$R/$O/kt20.err | tail -1 > $R/$O/bench_2p20_under_rocprof.json)
