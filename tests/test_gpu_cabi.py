@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+import leaf_edges
 from oracle import py_oracle as po
 import synth
 
@@ -469,9 +470,8 @@ def test_merkle(sc):
     for rec in g["open"]:
         tree = sc.MerkleTree.from_bytes(packed(rec["seed"], rec["n"]))
         assert [d.hex() for d in tree.open(rec["index"])] == rec["path"]
-    # leaf encoding edge cases: every decimal length 1..39
-    vals = [0] + [10 ** k for k in range(39)] + [10 ** k - 1 for k in range(1, 39)] + [P - 1, (1 << 64) - 1, 1 << 64, (1 << 127)]
-    vals = vals[:64] + synth.synth_ints(3, 128 - len(vals[:64]))
+    # leaf encoding edge cases: every decimal length 1..39 (tests/leaf_edges.py: 128 residues)
+    vals = leaf_edges.EDGE_LEAVES
     root = ctypes.create_string_buffer(64)
     sc._check(lib.sc_merkle_commit(synth.pack_ints(vals), len(vals), root))
     assert root.raw == po.merkle_commit(vals)

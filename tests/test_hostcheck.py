@@ -1,7 +1,7 @@
 """The two arithmetic shortcuts of the tree kernels' leaf stage (csrc/merkle.cuh: div1e9_step, the fixed-point digits of
 leaf_message_lds), restated in C and checked against plain division on the host: all 10^9 values of a nine-digit group, 3 * 10^8
-random and boundary dividends of the long division.  (The device code itself is pinned by the Merkle goldens in the -m gpu tests;
-these programs are what the constants were chosen with.)"""
+random and boundary dividends of the long division.  (The device code itself is pinned by the Merkle goldens in the -m gpu tests
+and, on short and boundary strings, by tests/test_gpu_leaf_edges.py; these programs are what the constants were chosen with.)"""
 import os
 import subprocess
 
