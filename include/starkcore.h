@@ -62,12 +62,14 @@ int sc_stream(void** stream_out);
 int sc_stream_join(void* other_stream);
 /* tuning knobs for experiments (defaults are the measured optimum; -1 = choose by size where applicable): key in
  * {"max_tile_log","loge","max_col_log","min_tiles_log","single_pass_max_log","max_digit_log","direct_tw_max_log",
- *  "xcd_remap","fixed_shapes","merkle_big_nlev","wave_local","prio_balance","loge_cols","tw_on_load","prune","fri_tail","fri_tail_stall","small_divisor_direct","verify_stage_kb","forest_four_lane_wgs"}.  Plans are re-derived on the next
+ *  "xcd_remap","fixed_shapes","merkle_big_nlev","wave_local","prio_balance","loge_cols","tw_on_load","prune","fast_fixups","fri_tail","fri_tail_stall","small_divisor_direct","verify_stage_kb","forest_four_lane_wgs"}.  Plans are re-derived on the next
  * call; results never depend on the tuning ("fri_tail_stall" = k >= 0 is a test hook: the host withholds the challenge after round k of
  * the persistent tail kernel, whose wait then gives up after 2^13 polls; -1 = off; "small_divisor_direct" = 0: sc_coset_divide* transforms a
  * divisor of <= 8 coefficients like any other instead of evaluating it point by point; "verify_stage_kb" = the size of the staging buffer
  * of sc_merkle_verify_batch / sc_fri_colinearity_batch, 65536 by default, at least 16; "forest_four_lane_wgs" = a launch of a Merkle forest of
- * at most this many workgroups runs its narrow levels four lanes per BLAKE2b compression, 0 = never).  Two keys manage the device-memory pool instead (freed vectors and trees are kept
+ * at most this many workgroups runs its narrow levels four lanes per BLAKE2b compression, 0 = never; "fast_fixups" = 1: the eight-element
+ * batch kernels correct by +-p on two limbs and an exact kernel redoes the tiles they flag, 0: exact arithmetic on every tile, 2: both
+ * kernels on every tile (a test hook) -- see sc_ntt_columns_dev).  Two keys manage the device-memory pool instead (freed vectors and trees are kept
  * on exact-size free lists, by default up to a quarter of the device's memory divided by the processes sharing the device;
  * environment STARKCORE_POOL_CAP_MB): "pool_cap_mb" = what the lists may keep from now on, "pool_trim" = hand everything on them
  * back to the device now (a caller whose own allocator -- torch's -- ran out of memory). */
@@ -113,7 +115,13 @@ int sc_ntt_dev(const void* d_in, void* d_out, uint64_t n, const uint64_t root[2]
  * launches covers up to 2^26 elements (64 columns of 2^20), every pass over cols x its tiles, so the workgroups of one column start
  * while those of another finish, and the 2^12-element tiles of a batch run two workgroups per CU (a lone 2^20 transform is one
  * workgroup per CU with every CU in the same phase: 30 G elements/s; 16-64 columns: 43-44; 64 columns of 2^16: 45-49 against 3.4
- * one at a time -- DESIGN.md 3.1). */
+ * one at a time -- DESIGN.md 3.1).
+ * The time of a batched transform depends a little on its DATA: the eight-element kernels correct by +-p on the top and bottom 32-bit
+ * limbs only and flag the tile when the carry between them would have mattered (probability 2^-32 per lane and operation on the
+ * values a transform carries after its first twiddles); a flagged 2^12-element tile is transformed again by an exact kernel behind
+ * the pass.  A column whose first butterflies see u - v = -1 -- a 0/1-valued trace whose halves differ, say -- redoes every tile of
+ * its first pass.  sc_set_tuning("fast_fixups", 0) restores data-independent work (exact arithmetic on every tile); results are the
+ * same bits either way. */
 int sc_ntt_columns_dev(const void* d_in, void* d_out, uint64_t n, uint64_t cols, const uint64_t root[2], int inverse, void* stream);
 
 /* ---- building blocks of the multi-GPU four-step NTT (no reference counterpart: the reference is single-process;

@@ -75,21 +75,53 @@ __global__ void __launch_bounds__(1 << (GLR + GLC - LOGE)) ntt_pass_kernel_fixed
 // round, and the register budget of four waves per SIMD (122 of 128 VGPRs, no scratch), so that two workgroups share a CU and one computes
 // while the other loads or drains.  Global accesses are  s[base] + 32-bit lane offset  (Round::SPLIT_ADDR), so the launch needs every
 // per-thread offset below 4 GiB (fixed_offsets_fit).  No trace, no second destination (those launches take the generic kernel).
+//
+// This kernel runs the rounds with the top-limb field corrections (FixedRounds FAST, field.cuh): a correction by +-p touches limbs 0
+// and 3 only, and the carry that limbs 1 and 2 would have passed on -- there with probability 2^-32 per lane on transform data --
+// is collected in one SGPR mask.  A wave that ends with the mask set marks its workgroup in flags[grid index]; the launch is
+// followed by ntt_pass_redo8_kernel, which transforms the marked tiles again from the pass's input with the exact arithmetic.
 template <int GLR, int GLC>
-__global__ void __launch_bounds__(1 << (GLR + GLC - 3)) __attribute__((amdgpu_waves_per_eu(4)))
-ntt_pass_kernel_fixed8(const PassParams P, uint32_t ntiles, int xcd_remap, int wave_local) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    Fe* lds = reinterpret_cast<Fe*>(smem_raw);
-    uint32_t wg = blockIdx.x, colbits = 0;
+__device__ __forceinline__ uint32_t fixed8_tile(const PassParams& P, uint32_t index, uint32_t ntiles, int xcd_remap) {
+    uint32_t wg = index, colbits = 0;
     if (P.col_enable) { colbits = (wg >> P.col_tiles_log) << P.col_tiles_log; wg -= colbits; }
     uint32_t tile = wg;
     if (xcd_remap) tile = (wg & 7u) * (ntiles >> 3) + (wg >> 3);
-    tile |= colbits;
+    return tile | colbits;
+}
+template <int GLR, int GLC>
+__global__ void __launch_bounds__(1 << (GLR + GLC - 3)) __attribute__((amdgpu_waves_per_eu(4)))
+ntt_pass_kernel_fixed8(const PassParams P, uint32_t ntiles, int xcd_remap, int wave_local, uint32_t* flags) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    Fe* lds = reinterpret_cast<Fe*>(smem_raw);
+    const uint32_t tile = fixed8_tile<GLR, GLC>(P, blockIdx.x, ntiles, xcd_remap);
     Fe* tw = lds + (1u << (GLR + GLC));
     auto stamp = [](int) {};
     auto sync = [] { __syncthreads(); };
     auto wsync = [] { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); };
-    FixedRounds<3, GLR, GLC, 0, false>::run(P, tile, threadIdx.x, lds, tw, sync, wsync, stamp, wave_local != 0);
+    rare_t rare = 0;
+    FixedRounds<3, GLR, GLC, 0, false, true>::run(P, tile, threadIdx.x, lds, tw, sync, wsync, stamp, wave_local != 0, rare);
+    // wave-uniform; the lanes of a flagged wave all store the same word to the same place (idempotent, no atomics)
+    if (rare_any(rare)) Round<3, 3, GLR, GLC>::store_word_at(flags + blockIdx.x, 0u, 1u);
+}
+
+// The exact rounds (today's arithmetic) on the tiles the fast kernel marked, or on every tile (`all`: an in-place pass, whose input
+// the fast kernel would have overwritten, the first pass of an LDE, sc_set_tuning("fast_fixups", 0 / 2)).  Same grid as the pass, one
+// tile per workgroup: an unmarked workgroup reads its flag and leaves.  (A resident grid of two workgroups per CU striding over the
+// flags keeps the loop's state live across the rounds: 117 VGPRs and 97 SGPRs spilled, the all-tiles launch at 0.57 of today's speed.)
+// Leaves its flag zero.
+template <int GLR, int GLC>
+__global__ void __launch_bounds__(1 << (GLR + GLC - 3)) __attribute__((amdgpu_waves_per_eu(4)))
+ntt_pass_redo8_kernel(const PassParams P, uint32_t ntiles, int xcd_remap, int wave_local, uint32_t* flags, int all) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    if (!all && flags[blockIdx.x] == 0) return;               // the same word for every thread: cleared only behind the barrier below
+    Fe* lds = reinterpret_cast<Fe*>(smem_raw);
+    Fe* tw = lds + (1u << (GLR + GLC));
+    auto stamp = [](int) {};
+    auto sync = [] { __syncthreads(); };
+    auto wsync = [] { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); };
+    FixedRounds<3, GLR, GLC, 0, false>::run(P, fixed8_tile<GLR, GLC>(P, blockIdx.x, ntiles, xcd_remap), threadIdx.x, lds, tw, sync, wsync, stamp, wave_local != 0);
+    if (!all) __syncthreads();                                 // every thread has read the flag
+    if (threadIdx.x == 0) flags[blockIdx.x] = 0;
 }
 
 __global__ void __launch_bounds__(256) pow_table_kernel(Fe* out, uint64_t count, Fe base_m, uint64_t step, Fe scale_m) {
@@ -596,8 +628,20 @@ int plan_batched_direct(NttPlanDesc& d, BatchKind kind, int loglen, int logbatch
     return SC_OK;
 }
 
+// the tile flags of the eight-element kernels on stream st: one word per workgroup of the grid, all zero between launches
+int pass_flags(hipStream_t st, uint32_t nwg, uint32_t** out) {
+    DevBuf& b = g.ntt_flags[st];
+    const void* before = b.p;
+    const size_t had = b.bytes;
+    void* p;
+    SCCHK(grow_buffer(b, (size_t)nwg * sizeof(uint32_t), &p));
+    if (p != before || b.bytes != had) HIPCHK(hipMemsetAsync(p, 0, b.bytes, st));
+    *out = (uint32_t*)p;
+    return SC_OK;
+}
+
 template <int LOGE>
-void launch_pass(const NttPassDesc& pd, hipStream_t st) {
+int launch_pass(const NttPassDesc& pd, hipStream_t st) {
     int remap = (g.xcd_remap && pd.ntiles >= 16 && (pd.ntiles & 7u) == 0) ? 1 : 0;
     const PassKernel k = pass_kernel(pd, g.fixed_shapes != 0);     // (ntt_plan.h: which instantiation, and why)
     if constexpr (LOGE == 2) {
@@ -610,7 +654,7 @@ void launch_pass(const NttPassDesc& pd, hipStream_t st) {
                 if (k.trace) SC_LAUNCH_FIXED(LR, LC, true, false);                \
                 else if (k.alt) SC_LAUNCH_FIXED(LR, LC, false, true);             \
                 else SC_LAUNCH_FIXED(LR, LC, false, false);                       \
-                return;                                                           \
+                return SC_OK;                                                     \
             }
             SC_FIXED4_SHAPES(SC_FIXED)
 #undef SC_FIXED
@@ -619,12 +663,27 @@ void launch_pass(const NttPassDesc& pd, hipStream_t st) {
     if constexpr (LOGE == 3) {
         if (k.kind == PK_FIXED8) {
             const int lr = pd.p.logR, lc = pd.p.logC;
-#define SC_FIXED8(LR, LC) if (lr == LR && lc == LC) { hipLaunchKernelGGL((ntt_pass_kernel_fixed8<LR, LC>), dim3(pd.ntiles * pd.cols), dim3(pd.threads), pd.lds_bytes, st, pd.p, pd.ntiles, remap, g.wave_local); return; }
+            // fast kernel, then the exact one on the tiles it marked -- from the pass's input, so only where the pass is not in
+            // place (both passes of a two-pass plan: in -> work -> out); an in-place pass (the middle one of three), the first pass
+            // of an LDE (coset scaling, pruned stages: fast_pass_ok) and fast_fixups = 0 take the exact kernel on every tile;
+            // fast_fixups = 2 (tests) runs both on every tile
+            const uint32_t nwg = pd.ntiles * pd.cols;
+            const bool fast = g.fast_fixups != 0 && fast_pass_ok(pd.p) && !pass_in_place(pd);
+            const int all = (!fast || g.fast_fixups == 2) ? 1 : 0;
+            uint32_t* flags;
+            SCCHK(pass_flags(st, nwg, &flags));
+#define SC_FIXED8(LR, LC)                                                                                                                                   \
+            if (lr == LR && lc == LC) {                                                                                                                     \
+                if (fast) hipLaunchKernelGGL((ntt_pass_kernel_fixed8<LR, LC>), dim3(nwg), dim3(pd.threads), pd.lds_bytes, st, pd.p, pd.ntiles, remap, g.wave_local, flags); \
+                hipLaunchKernelGGL((ntt_pass_redo8_kernel<LR, LC>), dim3(nwg), dim3(pd.threads), pd.lds_bytes, st, pd.p, pd.ntiles, remap, g.wave_local, flags, all); \
+                return SC_OK;                                                                                                                               \
+            }
             SC_FIXED8_SHAPES(SC_FIXED8)
 #undef SC_FIXED8
         }
     }
     hipLaunchKernelGGL(ntt_pass_kernel<LOGE>, dim3(pd.ntiles * pd.cols), dim3(pd.threads), pd.lds_bytes, st, pd.p, pd.ntiles, remap);
+    return SC_OK;
 }
 
 int run_plan(NttPlanDesc& d, hipStream_t st) {
@@ -634,10 +693,10 @@ int run_plan(NttPlanDesc& d, hipStream_t st) {
         d.pass[i].p.trace = g.trace ? g.trace + trace_off : nullptr;
         trace_off += (size_t)d.pass[i].ntiles * d.pass[i].cols * (d.pass[i].threads >> 6) * TRACE_STAMPS;
         switch (d.pass[i].loge) {
-            case 1: launch_pass<1>(d.pass[i], st); break;
-            case 2: launch_pass<2>(d.pass[i], st); break;
-            case 3: launch_pass<3>(d.pass[i], st); break;
-            case 4: launch_pass<4>(d.pass[i], st); break;
+            case 1: SCCHK(launch_pass<1>(d.pass[i], st)); break;
+            case 2: SCCHK(launch_pass<2>(d.pass[i], st)); break;
+            case 3: SCCHK(launch_pass<3>(d.pass[i], st)); break;
+            case 4: SCCHK(launch_pass<4>(d.pass[i], st)); break;
             default: return fail(SC_ERR_UNSUPPORTED, "bad loge");
         }
         HIPCHK(hipGetLastError());
@@ -872,6 +931,8 @@ int sc_shutdown(void) {
     for (auto& b : g.scratch) { if (b.p) hipFree(b.p); b = DevBuf{}; }
     for (auto& kv : g.ntt_work) if (kv.second.p) hipFree(kv.second.p);
     g.ntt_work.clear();
+    for (auto& kv : g.ntt_flags) if (kv.second.p) hipFree(kv.second.p);
+    g.ntt_flags.clear();
     if (g.later_words) hipFree(g.later_words);     // (no check is in flight after the device-wide wait above; re-allocated on the next)
     g.later_words = nullptr;
     if (g.stream) hipStreamDestroy(g.stream);
@@ -934,6 +995,7 @@ int sc_set_tuning(const char* key, int value) {
     else if (k == "xcd_remap") g.xcd_remap = value;
     else if (k == "fixed_shapes") g.fixed_shapes = value;
     else if (k == "wave_local") g.wave_local = value;
+    else if (k == "fast_fixups") g.fast_fixups = value < 0 ? 0 : (value > 2 ? 2 : value);
     else if (k == "prio_balance") g.prio_balance = value;
     else if (k == "loge_cols") g.tuning.loge_cols = value;
     else if (k == "tw_on_load") g.tuning.tw_on_load = value;

@@ -122,6 +122,65 @@ SC_HD Fe mont_mul_c(Fe a, Fe b) {
     return Fe{rl, v3 - sh - br};
 }
 
+// ---- top-limb corrections (the eight-element batch kernels).  p = [1, 0, 0, PH3] in 32-bit limbs, so adding or
+// subtracting p changes limb 0 by one and limb 3 by PH3; limbs 1 and 2 only pass on the carry that exists when limb 0 wraps.  The
+// fast forms leave limbs 1 and 2 alone and OR that wrap into `rare` (device: a 64-lane mask; here: 0 / 1).  rare clear <=> the
+// result is the canonical one; rare set: the result may be wrong and whoever consumed it redoes the work with the exact forms.
+typedef uint64_t rare_t;
+static constexpr uint32_t P_TOP32 = (uint32_t)(P_HI >> 32);
+
+// d (mod 2^128) + p where `neg` (the subtraction that made d borrowed)
+SC_HD Fe fe_fixup_fast_c(uint64_t lo, uint64_t hi, bool neg, rare_t& rare) {
+    const uint32_t d0 = (uint32_t)lo, d3 = (uint32_t)(hi >> 32);
+    const uint32_t o0 = d0 + (neg ? 1u : 0u);
+    rare |= (neg && o0 == 0) ? 1u : 0u;                       // limb 0 wrapped: the carry into limb 1 is dropped
+    const uint32_t o3 = neg ? d3 + P_TOP32 : d3;
+    return Fe{(lo & 0xFFFFFFFF00000000ull) | o0, (hi & 0xFFFFFFFFull) | ((uint64_t)o3 << 32)};
+}
+SC_HD Fe fe_sub_fast_c(Fe a, Fe b, rare_t& rare) {
+    const uint64_t lo = a.lo - b.lo;
+    const uint64_t b0 = a.lo < b.lo;
+    const uint64_t hi = a.hi - b.hi;
+    const bool neg = (a.hi < b.hi) || (hi < b0);
+    return fe_fixup_fast_c(lo, hi - b0, neg, rare);
+}
+SC_HD Fe fe_add_fast_c(Fe a, Fe b, rare_t& rare) {
+    const uint64_t lo = a.lo + b.lo;
+    const uint64_t c0 = lo < a.lo;
+    const uint64_t hi = a.hi + b.hi;
+    const uint64_t hi2 = hi + c0;
+    const bool ca = (hi < a.hi) || (hi2 < hi);
+    const uint32_t r0 = (uint32_t)lo, r3 = (uint32_t)(hi2 >> 32);
+    // r >= p is decided by the top limb alone, except when the low 96 bits are zero: then limb 0 borrows and raises the flag
+    const bool sel = ca || r3 >= P_TOP32;
+    const uint32_t o0 = r0 - (sel ? 1u : 0u);
+    rare |= (sel && r0 == 0) ? 1u : 0u;
+    const uint32_t o3 = sel ? r3 - P_TOP32 : r3;
+    return Fe{(lo & 0xFFFFFFFF00000000ull) | o0, (hi2 & 0xFFFFFFFFull) | ((uint64_t)o3 << 32)};
+}
+// The subtractive Montgomery step of field_asm.cuh in portable C (m' = T_lo * p^-1 touches only the top limb of T_lo;
+// T * 2^-128 = T_hi - floor(m' * PH / 2^32) - delta in (-p, p)), then the fast correction of a negative difference.
+SC_HD Fe mont_mul_fast_c(Fe a, Fe b, rare_t& rare) {
+    u128 p00 = (u128)a.lo * b.lo, p01 = (u128)a.lo * b.hi, p10 = (u128)a.hi * b.lo, p11 = (u128)a.hi * b.hi;
+    const uint64_t t0 = (uint64_t)p00;
+    u128 mid = (p00 >> 64) + (uint64_t)p01 + (uint64_t)p10;
+    const uint64_t t1 = (uint64_t)mid;
+    u128 top = (mid >> 64) + (p01 >> 64) + (p10 >> 64) + p11;
+    const uint32_t w0 = (uint32_t)t0, w1 = (uint32_t)(t0 >> 32), w2 = (uint32_t)t1, w3 = (uint32_t)(t1 >> 32);
+    const uint64_t PH = P_TOP32;
+    const uint64_t s0 = (uint64_t)w0 * PH;
+    const uint32_t m3 = w3 - (uint32_t)s0;
+    const uint64_t delta = w3 < (uint32_t)s0;
+    const uint64_t s1 = (uint64_t)w1 * PH + (s0 >> 32);
+    const uint64_t s2 = (uint64_t)w2 * PH + (s1 >> 32);
+    const uint64_t s3 = (uint64_t)m3 * PH + (s2 >> 32);
+    const u128 q = (u128)(uint32_t)s1 | ((u128)(uint32_t)s2 << 32) | ((u128)s3 << 64);
+    const u128 d = top - q;
+    const bool neg = top < q || d < delta;
+    const u128 r = d - delta;
+    return fe_fixup_fast_c((uint64_t)r, (uint64_t)(r >> 64), neg, rare);
+}
+
 SC_HD Fe to_mont(Fe a) { return mont_mul(a, Fe{R2_LO, R2_HI}); }
 SC_HD Fe from_mont(Fe a) { return mont_mul(a, fe_one()); }
 // plain modular product of two canonical values (two Montgomery steps)
@@ -238,6 +297,51 @@ SC_HD Fe fe_sub(Fe a, Fe b) {
     return fe_sub_asm(a, b);
 #else
     return fe_sub_c(a, b);
+#endif
+}
+// the top-limb-correction forms (see fe_fixup_fast_c): same dispatch
+SC_HD bool rare_any(rare_t rare) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return rare_any_asm(rare);
+#else
+    return rare != 0;
+#endif
+}
+SC_HD Fe fe_add_fast(Fe a, Fe b, rare_t& rare) {
+#if defined(__HIP_DEVICE_COMPILE__) && SC_ASM_ADDSUB
+    return fe_add_fast_asm(a, b, rare);
+#else
+    return fe_add_fast_c(a, b, rare);
+#endif
+}
+SC_HD Fe fe_sub_fast(Fe a, Fe b, rare_t& rare) {
+#if defined(__HIP_DEVICE_COMPILE__) && SC_ASM_ADDSUB
+    return fe_sub_fast_asm(a, b, rare);
+#else
+    return fe_sub_fast_c(a, b, rare);
+#endif
+}
+SC_HD Fe mont_mul_fast(Fe a, Fe b, rare_t& rare) {
+#if defined(__HIP_DEVICE_COMPILE__) && SC_ASM_MUL
+    return mont_mul_fast_asm(a, b, rare);
+#else
+    return mont_mul_fast_c(a, b, rare);
+#endif
+}
+SC_HD void mont_mul2_fast(Fe a0, Fe b0, Fe a1, Fe b1, Fe& r0, Fe& r1, rare_t& rare) {
+#if defined(__HIP_DEVICE_COMPILE__) && SC_ASM_MUL && SC_MUL2
+    mont_mul2_fast_asm(a0, b0, a1, b1, r0, r1, rare);
+#else
+    r0 = mont_mul_fast(a0, b0, rare);
+    r1 = mont_mul_fast(a1, b1, rare);
+#endif
+}
+SC_HD void fe_addsub2_fast(Fe u0, Fe v0, Fe u1, Fe v1, Fe& s0, Fe& d0, Fe& s1, Fe& d1, rare_t& rare) {
+#if defined(__HIP_DEVICE_COMPILE__) && SC_ASM_ADDSUB && SC_MUL2
+    fe_addsub2_fast_asm(u0, v0, u1, v1, s0, d0, s1, d1, rare);
+#else
+    s0 = fe_add_fast(u0, v0, rare); d0 = fe_sub_fast(u0, v0, rare);
+    s1 = fe_add_fast(u1, v1, rare); d1 = fe_sub_fast(u1, v1, rare);
 #endif
 }
 }  // namespace sc

@@ -88,6 +88,17 @@ __device__ __forceinline__ uint32_t a_cnd(uint32_t a, uint32_t b, smask_t sel) {
     return r;
 }
 
+// The flag accumulator of the top-limb corrections lives in an SGPR pair and is updated on the SALU.  Written as asm: hipcc takes
+// the SGPR outputs of the asm statements for divergent values and would keep a C++ `rare |= c` in VGPRs (two v_or3_b32 and two
+// v_mov_b32 per update).
+__device__ __forceinline__ void rare_or(smask_t& rare, smask_t c) { asm volatile("s_or_b64 %0, %0, %1" : "+s"(rare) : "s"(c) : "scc"); }
+// any lane flagged? (wave-uniform, decided on the SALU)
+__device__ __forceinline__ bool rare_any_asm(smask_t rare) {
+    uint32_t any;
+    asm("s_cmp_lg_u64 %1, 0\n\ts_cselect_b32 %0, 1, 0" : "=s"(any) : "s"(rare) : "scc");
+    return __builtin_amdgcn_readfirstlane(any) != 0;
+}
+
 __device__ __forceinline__ uint32_t lo32(uint64_t x) { return (uint32_t)x; }
 __device__ __forceinline__ uint32_t hi32(uint64_t x) { return (uint32_t)(x >> 32); }
 
@@ -105,7 +116,19 @@ __device__ __forceinline__ Fe a_cond_sub_p(uint32_t r0, uint32_t r1, uint32_t r2
     return Fe{((uint64_t)o1 << 32) | o0, ((uint64_t)o3 << 32) | o2};
 }
 
-__device__ __forceinline__ Fe mont_mul_asm(Fe a, Fe b) {
+// d (4 limbs, mod 2^128) + p where the subtraction that made it borrowed (mask bw), top-limb form (field.cuh, fe_fixup_fast_c):
+// limb 0 takes the borrow as carry-in and its carry-out goes into `rare`; limb 3 gets PH3 by a plain add and a select
+__device__ __forceinline__ Fe a_fixup_fast(uint32_t d0, uint32_t d1, uint32_t d2, uint32_t d3, smask_t bw, smask_t& rare) {
+    smask_t c;
+    const uint32_t d3p = d3 + PH3;
+    uint32_t o0 = a_addc(d0, 0u, bw, c);
+    uint32_t o3 = a_cnd(d3, d3p, bw);
+    rare_or(rare, c);
+    return Fe{((uint64_t)d1 << 32) | o0, ((uint64_t)o3 << 32) | d2};
+}
+
+template <bool FAST>
+__device__ __forceinline__ Fe mont_mul_core(Fe a, Fe b, smask_t& rare) {
     const uint32_t a0 = lo32(a.lo), a1 = hi32(a.lo), a2 = lo32(a.hi), a3 = hi32(a.hi);
     const uint32_t b0 = lo32(b.lo), b1 = hi32(b.lo), b2 = lo32(b.hi), b3 = hi32(b.hi);
     smask_t c;
@@ -159,6 +182,7 @@ __device__ __forceinline__ Fe mont_mul_asm(Fe a, Fe b) {
     uint32_t r1 = a_subb(t5, lo32(s2), bw, bw);
     uint32_t r2 = a_subb(t6, lo32(s3), bw, bw);
     uint32_t r3 = a_subb(t7, hi32(s3), bw, bw);
+    if constexpr (FAST) return a_fixup_fast(r0, r1, r2, r3, bw, rare);
     uint32_t ph = a_cnd(0u, PH3, bw);
     uint32_t o0 = a_addc(r0, 0u, bw, c);
     uint32_t o1 = a_addc(r1, 0u, c, c);
@@ -166,6 +190,11 @@ __device__ __forceinline__ Fe mont_mul_asm(Fe a, Fe b) {
     uint32_t o3 = a_addc_last(r3, ph, c);
     return Fe{((uint64_t)o1 << 32) | o0, ((uint64_t)o3 << 32) | o2};
 }
+__device__ __forceinline__ Fe mont_mul_asm(Fe a, Fe b) {
+    smask_t none = 0;
+    return mont_mul_core<false>(a, b, none);
+}
+__device__ __forceinline__ Fe mont_mul_fast_asm(Fe a, Fe b, smask_t& rare) { return mont_mul_core<true>(a, b, rare); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Two independent Montgomery products, hand-interleaved (A, B, A, B, ...) so that every carry / borrow consumer sits at least two
@@ -209,7 +238,11 @@ struct MulState {       // registers of one product in flight
     smask_t c1, c2, c3, c4, c5, c6, c7, c8, c9, ct, bw, cx;
 };
 
-__device__ __forceinline__ void mont_mul2_asm(Fe xa, Fe wa, Fe xb, Fe wb, Fe& ra, Fe& rb) {
+// FAST: the top-limb correction (field.cuh, fe_fixup_fast_c) instead of the four-limb one: limb 0 takes the borrow as its carry-in,
+// limb 3 gets PH3 by a plain add and a select, limbs 1 and 2 stay, and limb 0's carry-out -- the carry they would have passed on --
+// is ORed into `rare`.  46 four-cycle instructions and one plain add per product instead of 49.
+template <bool FAST>
+__device__ __forceinline__ void mont_mul2_core(Fe xa, Fe wa, Fe xb, Fe wb, Fe& ra, Fe& rb, smask_t& rare) {
     MulState A, B;
     A.a0 = lo32(xa.lo); A.a1 = hi32(xa.lo); A.a2 = lo32(xa.hi); A.a3 = hi32(xa.hi);
     A.b0 = lo32(wa.lo); A.b1 = hi32(wa.lo); A.b2 = lo32(wa.hi); A.b3 = hi32(wa.hi);
@@ -270,6 +303,17 @@ __device__ __forceinline__ void mont_mul2_asm(Fe xa, Fe wa, Fe xb, Fe wb, Fe& ra
     SC_BOTH(SC_V_SUBB(M.r3, M.bw, M.t7, hi32(M.s3), M.bw);)
     SC_V_NOP0();
     // ---- negative -> add p back
+    if constexpr (FAST) {
+        A.ph = A.r3 + PHc;
+        B.ph = B.r3 + PHc;
+        SC_BOTH(SC_V_ADDC(M.o0, M.cx, M.r0, zero32, M.bw);)
+        SC_BOTH(SC_V_CND(M.o3, M.r3, M.ph, M.bw);)
+        rare_or(rare, A.cx);
+        rare_or(rare, B.cx);
+        ra = Fe{((uint64_t)A.r1 << 32) | A.o0, ((uint64_t)A.o3 << 32) | A.r2};
+        rb = Fe{((uint64_t)B.r1 << 32) | B.o0, ((uint64_t)B.o3 << 32) | B.r2};
+        return;
+    }
     SC_BOTH(SC_V_CND(M.ph, zero32, PHc, M.bw);)
     SC_BOTH(SC_V_ADDC(M.o0, M.cx, M.r0, zero32, M.bw);)
     SC_V_NOP0();
@@ -281,6 +325,13 @@ __device__ __forceinline__ void mont_mul2_asm(Fe xa, Fe wa, Fe xb, Fe wb, Fe& ra
 #undef SC_BOTH
     ra = Fe{((uint64_t)A.o1 << 32) | A.o0, ((uint64_t)A.o3 << 32) | A.o2};
     rb = Fe{((uint64_t)B.o1 << 32) | B.o0, ((uint64_t)B.o3 << 32) | B.o2};
+}
+__device__ __forceinline__ void mont_mul2_asm(Fe xa, Fe wa, Fe xb, Fe wb, Fe& ra, Fe& rb) {
+    smask_t none = 0;
+    mont_mul2_core<false>(xa, wa, xb, wb, ra, rb, none);
+}
+__device__ __forceinline__ void mont_mul2_fast_asm(Fe xa, Fe wa, Fe xb, Fe wb, Fe& ra, Fe& rb, smask_t& rare) {
+    mont_mul2_core<true>(xa, wa, xb, wb, ra, rb, rare);
 }
 
 // The sums and differences of TWO butterflies (u0 +- v0, u1 +- v1): four independent carry chains issued round-robin, so every
@@ -349,6 +400,67 @@ __device__ __forceinline__ Fe fe_sub_asm(Fe a, Fe b) {
     uint32_t o2 = a_addc(d2, 0u, c, c);
     uint32_t o3 = a_addc_last(d3, ph, c);
     return Fe{((uint64_t)o1 << 32) | o0, ((uint64_t)o3 << 32) | o2};
+}
+
+__device__ __forceinline__ Fe fe_sub_fast_asm(Fe a, Fe b, smask_t& rare) {
+    smask_t bw;
+    uint32_t d0 = a_sub_co(lo32(a.lo), lo32(b.lo), bw);
+    uint32_t d1 = a_subb(hi32(a.lo), hi32(b.lo), bw, bw);
+    uint32_t d2 = a_subb(lo32(a.hi), lo32(b.hi), bw, bw);
+    uint32_t d3 = a_subb(hi32(a.hi), hi32(b.hi), bw, bw);
+    return a_fixup_fast(d0, d1, d2, d3, bw, rare);
+}
+
+// sum - p where the sum carried out of bit 127 or its top limb reaches PH3 (that decides r >= p except when the low 96 bits are
+// zero -- then limb 0 borrows, which raises the flag): limb 0 takes the select mask as its borrow-in, limb 3 is selected
+__device__ __forceinline__ Fe fe_add_fast_asm(Fe a, Fe b, smask_t& rare) {
+    smask_t ca, cb, bo;
+    uint32_t r0 = a_add_co(lo32(a.lo), lo32(b.lo), ca);
+    uint32_t r1 = a_addc(hi32(a.lo), hi32(b.lo), ca, ca);
+    uint32_t r2 = a_addc(lo32(a.hi), lo32(b.hi), ca, ca);
+    uint32_t r3 = a_addc(hi32(a.hi), hi32(b.hi), ca, ca);
+    uint32_t t3 = a_sub_co(r3, PH3, cb);
+    const smask_t sel = ca | ~cb;
+    uint32_t o0 = a_subb(r0, 0u, sel, bo);
+    uint32_t o3 = a_cnd(r3, t3, sel);
+    rare_or(rare, bo);
+    return Fe{((uint64_t)r1 << 32) | o0, ((uint64_t)o3 << 32) | r2};
+}
+
+// The sums and differences of two butterflies with the top-limb corrections: the four carry chains of fe_addsub2_asm, then per
+// butterfly 3 + 2 four-cycle instructions and one plain add instead of 8 + 5.  Every carry / mask consumer stays at least two VALU
+// instructions behind its producer.
+__device__ __forceinline__ void fe_addsub2_fast_asm(Fe ua, Fe va, Fe ub, Fe vb, Fe& sa, Fe& da, Fe& sb, Fe& db, smask_t& rare) {
+    AddSubState A, B;
+    A.u0 = lo32(ua.lo); A.u1 = hi32(ua.lo); A.u2 = lo32(ua.hi); A.u3 = hi32(ua.hi);
+    A.v0 = lo32(va.lo); A.v1 = hi32(va.lo); A.v2 = lo32(va.hi); A.v3 = hi32(va.hi);
+    B.u0 = lo32(ub.lo); B.u1 = hi32(ub.lo); B.u2 = lo32(ub.hi); B.u3 = hi32(ub.hi);
+    B.v0 = lo32(vb.lo); B.v1 = hi32(vb.lo); B.v2 = lo32(vb.hi); B.v3 = hi32(vb.hi);
+    const uint32_t zero32 = 0, PHc = PH3;
+#define SC_BOTH(STEP) { AddSubState& M = A; STEP } { AddSubState& M = B; STEP }
+    SC_BOTH(SC_V_ADDCO(M.r0, M.ca, M.u0, M.v0); SC_V_SUBCO(M.d0, M.bd, M.u0, M.v0);)
+    SC_BOTH(SC_V_ADDC(M.r1, M.ca, M.u1, M.v1, M.ca); SC_V_SUBB(M.d1, M.bd, M.u1, M.v1, M.bd);)
+    SC_BOTH(SC_V_ADDC(M.r2, M.ca, M.u2, M.v2, M.ca); SC_V_SUBB(M.d2, M.bd, M.u2, M.v2, M.bd);)
+    SC_BOTH(SC_V_ADDC(M.r3, M.ca, M.u3, M.v3, M.ca); SC_V_SUBB(M.d3, M.bd, M.u3, M.v3, M.bd);)
+    // top limb of sum - p (borrow cb: top limb below PH3)  |  top limb of difference + p
+    SC_BOTH(SC_V_SUBCO(M.t3, M.cb, M.r3, PHc);)
+    A.ph = A.d3 + PHc;
+    B.ph = B.d3 + PHc;
+    SC_BOTH(SC_V_ADDC(M.e0, M.ce, M.d0, zero32, M.bd);)
+    SC_BOTH(SC_V_CND(M.e3, M.d3, M.ph, M.bd);)
+    A.sel = A.ca | ~A.cb;
+    B.sel = B.ca | ~B.cb;
+    SC_BOTH(SC_V_SUBB(M.s0, M.cb, M.r0, zero32, M.sel);)
+    SC_BOTH(SC_V_CND(M.s3, M.r3, M.t3, M.sel);)
+#undef SC_BOTH
+    rare_or(rare, A.ce);
+    rare_or(rare, B.ce);
+    rare_or(rare, A.cb);
+    rare_or(rare, B.cb);
+    sa = Fe{((uint64_t)A.r1 << 32) | A.s0, ((uint64_t)A.s3 << 32) | A.r2};
+    da = Fe{((uint64_t)A.d1 << 32) | A.e0, ((uint64_t)A.e3 << 32) | A.d2};
+    sb = Fe{((uint64_t)B.r1 << 32) | B.s0, ((uint64_t)B.s3 << 32) | B.r2};
+    db = Fe{((uint64_t)B.d1 << 32) | B.e0, ((uint64_t)B.e3 << 32) | B.d2};
 }
 
 }  // namespace sc

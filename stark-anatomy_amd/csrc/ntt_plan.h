@@ -486,6 +486,30 @@ inline PassKernel pass_kernel(const NttPassDesc& pd, bool fixed_shapes) {
     return {PK_GENERIC, false, false};
 }
 
+// Does the pass read and write overlapping memory?  (The eight-element kernels repair a flagged tile from the pass's input, which
+// must then still be there.)  Each side's extent is the largest element index any tile reaches, from the strides.
+inline uint64_t pass_extent(const NttPassDesc& pd, bool out_side) {
+    const PassParams& p = pd.p;
+    const uint64_t R = 1ull << p.logR, C = 1ull << p.logC;
+    const uint64_t lo1 = (1ull << p.lo_log) - 1, mid1 = (1ull << p.mid_log) - 1, hi1 = pd.ntiles ? ((uint64_t)(pd.ntiles - 1) >> (p.lo_log + p.mid_log)) : 0;
+    uint64_t e;
+    if (out_side) {
+        e = hi1 * p.out_hi + mid1 * p.out_mid + lo1 * p.out_lo + (R - 1) * p.out_rs + (C - 1) * p.out_cs;
+        if (p.col_enable) e += (uint64_t)(pd.cols - 1) * p.col_stride;
+    } else {
+        e = hi1 * p.in_hi + mid1 * p.in_mid + lo1 * p.in_lo + (C - 1) * p.in_cs;
+        if (p.in_split) e += ((1ull << p.in_split) - 1) * p.in_rs + ((R >> p.in_split) - 1) * p.in_rs_hi;
+        else e += (R - 1) * p.in_rs;
+        if (p.col_enable) e += (uint64_t)(pd.cols - 1) * p.col_stride_in;
+    }
+    return e + 1;
+}
+inline bool pass_in_place(const NttPassDesc& pd) {
+    const uintptr_t a = (uintptr_t)pd.p.in, b = (uintptr_t)pd.p.out;
+    const uint64_t na = pass_extent(pd, false) * sizeof(Fe), nb = pass_extent(pd, true) * sizeof(Fe);
+    return a < b + nb && b < a + na;
+}
+
 // PassParams::prio_balance of a launch: `forced` (>= 0) or by grid size -- 1 for at most one workgroup per CU, 2 for long grids
 // (>= 8 workgroups per CU; >= 2 of 2^10 x 4 tiles), else 0
 inline int pass_prio_balance(const NttPassDesc& pd, int forced, int num_cus) {

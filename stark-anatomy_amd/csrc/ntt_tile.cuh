@@ -238,7 +238,13 @@ struct Round {
     SC_HD static void store_at(Fe* base, uint32_t lane_bytes, Fe v) {
         *reinterpret_cast<gfe*>(reinterpret_cast<gchar*>(sgpr_pin(reinterpret_cast<uint64_t>(base))) + vgpr_pin(lane_bytes)) = v;
     }
+    // a 32-bit word in the same s[base] + v_offset form (the tile flag of the FAST kernels)
+    SC_HD static void store_word_at(uint32_t* base, uint32_t lane_bytes, uint32_t v) {
+        typedef __attribute__((address_space(1))) uint32_t gword;
+        *reinterpret_cast<gword*>(reinterpret_cast<gchar*>(sgpr_pin(reinterpret_cast<uint64_t>(base))) + vgpr_pin(lane_bytes)) = v;
+    }
 #else
+    static void store_word_at(uint32_t* base, uint32_t lane_bytes, uint32_t v) { *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(base) + lane_bytes) = v; }
     static Fe load_at(const Fe* base, uint32_t lane_bytes) { return *reinterpret_cast<const Fe*>(reinterpret_cast<const char*>(base) + lane_bytes); }
     static void store_at(Fe* base, uint32_t lane_bytes, Fe v) { *reinterpret_cast<Fe*>(reinterpret_cast<char*>(base) + lane_bytes) = v; }
 #endif
@@ -290,8 +296,12 @@ struct Round {
         }
     }
     // first round: the multiplications that belong to the load (coset scaling, twiddle-on-load)
-    SC_HD void finish_global(const PassParams& P, int sh, Fe* x, const Fe* tin) const {
-        if (P.coset_enable) {
+    // FAST (here, in butterflies and in scatter_global): the sums, differences and products of the data go through the top-limb
+    // correction forms of field.cuh and OR their flags into *rare; the caller redoes the tile with FAST = false where it is set.
+    template <bool FAST = false>
+    SC_HD void finish_global(const PassParams& P, int sh, Fe* x, const Fe* tin, rare_t* rare = nullptr) const {
+        // (not with FAST, see fast_pass_ok: the zero-padding test is per lane)
+        if (!FAST && P.coset_enable) {
 #pragma unroll
             for (int i = 0; i < E; ++i) {
                 const uint64_t j = in_index(P, i, sh);
@@ -300,9 +310,17 @@ struct Round {
         }
         if (P.twd_in) {
 #pragma unroll
-            for (int i = 0; i + 1 < E; i += 2) mont_mul2(x[i], tin[i], x[i + 1], tin[i + 1], x[i], x[i + 1]);
-            if (E & 1) x[E - 1] = mont_mul(x[E - 1], tin[E - 1]);
+            for (int i = 0; i + 1 < E; i += 2) mul2<FAST>(x[i], tin[i], x[i + 1], tin[i + 1], x[i], x[i + 1], rare);
+            if (E & 1) x[E - 1] = mul1<FAST>(x[E - 1], tin[E - 1], rare);
         }
+    }
+    template <bool FAST> SC_HD static Fe mul1(Fe a, Fe b, rare_t* rare) {
+        if constexpr (FAST) return mont_mul_fast(a, b, *rare);
+        else return mont_mul(a, b);
+    }
+    template <bool FAST> SC_HD static void mul2(Fe a0, Fe b0, Fe a1, Fe b1, Fe& r0, Fe& r1, rare_t* rare) {
+        if constexpr (FAST) mont_mul2_fast(a0, b0, a1, b1, r0, r1, *rare);
+        else mont_mul2(a0, b0, a1, b1, r0, r1);
     }
     SC_HD void gather_lds(int sh, Fe* x, const Fe* lds) const {
 #pragma unroll
@@ -311,7 +329,8 @@ struct Round {
     // S radix-2 DIF stages on the field bits, highest bit first; tw[e << tw_shift] = w_R^e (LDS copy: shift 0).
     // prune_log > 0: stages whose index from the top (0-based) is below it are the degenerate ones of a zero-padded input.
     // last_hint: 1 / 0 when the caller knows whether this is the last round (sh == 0), -1 = look at sh.
-    SC_HD void butterflies(int sh, Fe* x, const Fe* tw, int tw_shift, int prune_log = 0, int last_hint = -1, int prio = 0) const {
+    template <bool FAST = false>
+    SC_HD void butterflies(int sh, Fe* x, const Fe* tw, int tw_shift, int prune_log = 0, int last_hint = -1, int prio = 0, rare_t* rare = nullptr) const {
         const bool last = last_hint < 0 ? (sh == 0) : (last_hint != 0);
         set_prio(prio, 3);
 #pragma unroll
@@ -319,7 +338,7 @@ struct Round {
             const int bit = S - 1 - q;          // field bit
             const int b = sh + bit;             // row bit
             const int tau = logR - 1 - b;       // twiddle exponent scale: w_R^(2^tau * (r mod 2^b)); also the stage index from the top
-            if (tau < prune_log) {
+            if (!FAST && tau < prune_log) {
                 // v = 0 everywhere: (u, 0) -> (u, u * w).  Before this stage row r is non-zero iff (r mod 2^(b+1)) < R >> prune_log.
                 const uint32_t nz = 1u << (logR - prune_log);
 #pragma unroll
@@ -356,11 +375,17 @@ struct Round {
                 if (bf + 1 < E / 2) {
                     const int j0 = (((bf + 1) >> bit) << (bit + 1)) | ((bf + 1) & ((1 << bit) - 1));
                     const int j1 = j0 | (1 << bit);
-                    fe_addsub2(x[i0], x[i1], x[j0], x[j1], x[i0], dd[bf], x[j0], dd[bf + 1]);
+                    if constexpr (FAST) fe_addsub2_fast(x[i0], x[i1], x[j0], x[j1], x[i0], dd[bf], x[j0], dd[bf + 1], *rare);
+                    else fe_addsub2(x[i0], x[i1], x[j0], x[j1], x[i0], dd[bf], x[j0], dd[bf + 1]);
                 } else {
                     Fe u = x[i0], v = x[i1];
-                    x[i0] = fe_add(u, v);
-                    dd[bf] = fe_sub(u, v);
+                    if constexpr (FAST) {
+                        x[i0] = fe_add_fast(u, v, *rare);
+                        dd[bf] = fe_sub_fast(u, v, *rare);
+                    } else {
+                        x[i0] = fe_add(u, v);
+                        dd[bf] = fe_sub(u, v);
+                    }
                 }
             }
 #pragma unroll
@@ -380,13 +405,13 @@ struct Round {
                 if (bf + 1 < E / 2) {
                     const int ib = ((((bf + 1) >> bit) << (bit + 1)) | ((bf + 1) & ((1 << bit) - 1))) | (1 << bit);
                     if (!triv[bf] && !triv[bf + 1]) {
-                        mont_mul2(dd[bf], tw[(uint64_t)ee[bf] << tw_shift], dd[bf + 1], tw[(uint64_t)ee[bf + 1] << tw_shift], x[ia], x[ib]);
+                        mul2<FAST>(dd[bf], tw[(uint64_t)ee[bf] << tw_shift], dd[bf + 1], tw[(uint64_t)ee[bf + 1] << tw_shift], x[ia], x[ib], rare);
                     } else {
-                        x[ia] = triv[bf] ? dd[bf] : mont_mul(dd[bf], tw[(uint64_t)ee[bf] << tw_shift]);
-                        x[ib] = triv[bf + 1] ? dd[bf + 1] : mont_mul(dd[bf + 1], tw[(uint64_t)ee[bf + 1] << tw_shift]);
+                        x[ia] = triv[bf] ? dd[bf] : mul1<FAST>(dd[bf], tw[(uint64_t)ee[bf] << tw_shift], rare);
+                        x[ib] = triv[bf + 1] ? dd[bf + 1] : mul1<FAST>(dd[bf + 1], tw[(uint64_t)ee[bf + 1] << tw_shift], rare);
                     }
                 } else {
-                    x[ia] = triv[bf] ? dd[bf] : mont_mul(dd[bf], tw[(uint64_t)ee[bf] << tw_shift]);
+                    x[ia] = triv[bf] ? dd[bf] : mul1<FAST>(dd[bf], tw[(uint64_t)ee[bf] << tw_shift], rare);
                 }
             }
             if (q == S - 1) set_prio(prio, 0);
@@ -445,8 +470,8 @@ struct Round {
     // ALT: the launch has a destination table (PassParams::out_blk).  A compile-time switch: with the test at run time (inside
     // the store loop, or two loops behind one branch) the plain transforms paid 1-2 % more VALU instructions for index math
     // the compiler hoisted above the branch; the geometry-specialised kernels are instantiated for both values.
-    template <bool ALT>
-    SC_HD void scatter_global(const PassParams& P, const Fe* x, const Fe (&twd_prefetched)[E], bool have_prefetched) const {
+    template <bool ALT, bool FAST = false>
+    SC_HD void scatter_global(const PassParams& P, const Fe* x, const Fe (&twd_prefetched)[E], bool have_prefetched, rare_t* rare = nullptr) const {
         Fe v[E];
 #pragma unroll
         for (int i = 0; i < E; ++i) v[i] = x[i];
@@ -476,12 +501,12 @@ struct Round {
                 if (E & 1) t[E - 1] = mont_mul(a[E - 1], b[E - 1]);
             }
 #pragma unroll
-            for (int i = 0; i + 1 < E; i += 2) mont_mul2(v[i], t[i], v[i + 1], t[i + 1], v[i], v[i + 1]);
-            if (E & 1) v[E - 1] = mont_mul(v[E - 1], t[E - 1]);
+            for (int i = 0; i + 1 < E; i += 2) mul2<FAST>(v[i], t[i], v[i + 1], t[i + 1], v[i], v[i + 1], rare);
+            if (E & 1) v[E - 1] = mul1<FAST>(v[E - 1], t[E - 1], rare);
         }
         if (P.scale_enable) {
 #pragma unroll
-            for (int i = 0; i < E; ++i) v[i] = mont_mul(v[i], P.scale);
+            for (int i = 0; i < E; ++i) v[i] = mul1<FAST>(v[i], P.scale, rare);
         }
         if constexpr (SPLIT_ADDR && !ALT) {
             const uint64_t tile_j = (uint64_t)t_hi * P.out_hi + (uint64_t)t_mid * P.out_mid + (uint64_t)t_lo * P.out_lo;
@@ -513,8 +538,8 @@ struct Round {
 };
 
 // the three steps in order (generic kernel and the CPU emulation)
-template <int LOGE, int S, int GLR = -1, int GLC = -1>
-SC_HD void ntt_round(const PassParams& P, int sh, bool first, uint32_t tile, uint32_t tid, Fe* lds, const Fe* tw) {
+template <int LOGE, int S, int GLR = -1, int GLC = -1, bool FAST = false>
+SC_HD void ntt_round(const PassParams& P, int sh, bool first, uint32_t tile, uint32_t tid, Fe* lds, const Fe* tw, rare_t* rare = nullptr) {
     constexpr int E = 1 << LOGE;
     Round<LOGE, S, GLR, GLC> R;
     R.setup(P, first, tile, tid);
@@ -522,13 +547,18 @@ SC_HD void ntt_round(const PassParams& P, int sh, bool first, uint32_t tile, uin
     if (first) {
         Fe tin[E];
         R.gather_global(P, sh, x, tin);
-        R.finish_global(P, sh, x, tin);
+        R.template finish_global<FAST>(P, sh, x, tin, rare);
     } else {
         R.gather_lds(sh, x, lds);
     }
-    R.butterflies(sh, x, tw, 0, P.prune_log, -1, P.prio_balance);
-    if (sh == 0) R.scatter_global(P, x);
-    else R.scatter_lds(sh, x, lds);
+    R.template butterflies<FAST>(sh, x, tw, 0, P.prune_log, -1, P.prio_balance, rare);
+    if (sh == 0) {
+        Fe none[E];
+        if (P.blk_enable) R.template scatter_global<true, FAST>(P, x, none, false, rare);
+        else R.template scatter_global<false, FAST>(P, x, none, false, rare);
+    } else {
+        R.scatter_lds(sh, x, lds);
+    }
 }
 
 // dispatch on the (runtime) number of stages in this round
@@ -564,7 +594,10 @@ SC_HD void tile_twiddles_to_lds(const PassParams& P, int logR, uint32_t tid, uin
 // (ntt_pass_kernel_fixed) and eight (ntt_pass_kernel_fixed8).  core.hip's launch_pass and the emulator dispatch over these lists.
 #define SC_FIXED4_SHAPES(X) X(8, 3) X(7, 4) X(10, 2) X(6, 5) X(9, 3) X(8, 4)
 #define SC_FIXED8_SHAPES(X) X(10, 2) X(9, 3) X(8, 4)
-template <int LOGE, int GLR, int GLC, int ROUND = 0, bool ALT = false>
+// FAST: the rounds use the top-limb field corrections and accumulate their flags in `rare` (one accumulator through all rounds
+// of the tile); where it ends up non-zero the tile's outputs may be wrong -- also those of other waves, which got this wave's
+// values through LDS -- and the caller has the whole tile transformed again with FAST = false.
+template <int LOGE, int GLR, int GLC, int ROUND = 0, bool ALT = false, bool FAST = false>
 struct FixedRounds {
     static constexpr int E = 1 << LOGE;
     static constexpr int NR = (GLR + LOGE - 1) / LOGE;
@@ -577,6 +610,11 @@ struct FixedRounds {
     // sync(): workgroup barrier; wsync(): wave-level fence; stamp(i): diagnostics hook (no-op in production)
     template <class Sync, class WSync, class Stamp>
     SC_HD static void run(const PassParams& P, uint32_t tile, uint32_t tid, Fe* lds, Fe* tw, Sync sync, WSync wsync, Stamp stamp, bool wave_local) {
+        rare_t none = 0;
+        run(P, tile, tid, lds, tw, sync, wsync, stamp, wave_local, none);
+    }
+    template <class Sync, class WSync, class Stamp>
+    SC_HD static void run(const PassParams& P, uint32_t tile, uint32_t tid, Fe* lds, Fe* tw, Sync sync, WSync wsync, Stamp stamp, bool wave_local, rare_t& rare) {
         Round<LOGE, S, GLR, GLC> R;
         R.setup(P, ROUND == 0, tile, tid);
         Fe x[E];
@@ -591,7 +629,7 @@ struct FixedRounds {
             stamp(1);
             sync();
             stamp(2);
-            R.finish_global(P, SH, x, tin);
+            R.template finish_global<FAST>(P, SH, x, tin, &rare);
         } else {
             R.gather_lds(SH, x, lds);
         }
@@ -605,15 +643,15 @@ struct FixedRounds {
         }
         // the degenerate stages of a zero-padded input lie in the first two rounds (the planner caps prune_log accordingly)
         const int prune = (ROUND <= 1) ? P.prune_log : 0;
-        R.butterflies(SH, x, tw, 0, prune, ROUND + 1 == NR ? 1 : 0, P.prio_balance == 1 ? 1 : 0);
+        R.template butterflies<FAST>(SH, x, tw, 0, prune, ROUND + 1 == NR ? 1 : 0, P.prio_balance == 1 ? 1 : 0, &rare);
         stamp(3 + 2 * ROUND);
         if constexpr (ROUND + 1 < NR) {
             R.scatter_lds(SH, x, lds);
             if (NEXT_WAVE_LOCAL && wave_local) wsync(); else sync();
             stamp(4 + 2 * ROUND);
-            FixedRounds<LOGE, GLR, GLC, ROUND + 1, ALT>::run(P, tile, tid, lds, tw, sync, wsync, stamp, wave_local);
+            FixedRounds<LOGE, GLR, GLC, ROUND + 1, ALT, FAST>::run(P, tile, tid, lds, tw, sync, wsync, stamp, wave_local, rare);
         } else {
-            R.template scatter_global<ALT>(P, x, tpre, prefetched);
+            R.template scatter_global<ALT, FAST>(P, x, tpre, prefetched, &rare);
             stamp(4 + 2 * ROUND);
         }
     }
@@ -629,6 +667,10 @@ inline bool fixed_offsets_fit(const PassParams& P) {
     if (P.tw_enable && P.twd && (r1 * P.tw_row_k * P.twd_stride + (c1 >> P.tw_col_shift)) * sizeof(Fe) >= lim) return false;
     return true;
 }
+
+// Launches the FAST rounds serve: no coset scaling and no pruned stages.  Both sit under per-lane tests (zero padding), and the flag
+// accumulator is a wave-uniform SGPR mask that must not merge behind a divergent branch; the FAST instantiations leave those paths out.
+inline bool fast_pass_ok(const PassParams& P) { return !P.coset_enable && P.prune_log == 0; }
 
 // Round schedule shared by the kernel and the CPU emulation: the short round (if any) goes first.
 struct RoundSched {
