@@ -240,6 +240,9 @@ int sc_pointwise_div_later_dev(const void* d_a, const void* d_b, void* d_out, ui
 int sc_later_wait(sc_later_t* later, int64_t words_out[8]);
 /* Polynomial.degree (code/univariate.py:7-17) of a coefficient vector in HBM: index of the last non-zero entry, -1 if none (synchronous) */
 int sc_vec_degree_dev(const void* d_v, uint64_t n, int64_t* degree_out, void* stream);
+/* The same for `cols` vectors of n entries each, column c at element c * ld of d_v (ld >= n; entries between the columns are not
+ * read): degrees_out[c] as above.  One kernel and one host wait for up to 4 096 columns (synchronous; cols == 0: nothing happens). */
+int sc_vec_degree_columns_dev(const void* d_v, uint64_t n, uint64_t ld, uint64_t cols, int64_t* degrees_out, void* stream);
 
 /* ---- pointwise helpers (ntt.py:61, :172; univariate.py:153-154) ------------------------------ */
 int sc_pointwise_mul_dev(const void* d_a, const void* d_b, void* d_out, uint64_t n, void* stream);
@@ -286,6 +289,12 @@ int sc_geodomain_detect_dev(const void* d_points, uint64_t n, uint64_t first[2],
 int sc_geodomain_zerofier_dev(const sc_geodomain_t* domain, void* d_out, void* stream);          /* n + 1 coefficients */
 int sc_geodomain_evaluate_dev(const sc_geodomain_t* domain, const void* d_coeffs, uint64_t m, void* d_out, void* stream);   /* n values, any m */
 int sc_geodomain_interpolate_dev(const sc_geodomain_t* domain, const void* d_values, void* d_out, void* stream);            /* n coefficients */
+/* The same for `cols` columns in one set of launches: column c's n values start at element c * ld_in of d_values, its n coefficients
+ * go to element c * ld_out of d_out (both strides >= n; elements of d_out between the columns are left alone).  The coefficients are
+ * those of `cols` calls of sc_geodomain_interpolate_dev, bit for bit; every step -- four transforms, five elementwise kernels -- is
+ * issued once for all columns (once per set of at most 2^26 / M and at most 65 536 columns, M the power of two >= 2n - 1).
+ * d_out may NOT overlap d_values.  cols == 0: SC_OK, nothing enqueued; a null pointer or a stride below n: SC_ERR_BAD_ARG, nothing enqueued. */
+int sc_geodomain_interpolate_columns_dev(const sc_geodomain_t* domain, const void* d_values, uint64_t ld_in, uint64_t cols, void* d_out, uint64_t ld_out, void* stream);
 int sc_geodomain_free(sc_geodomain_t* domain);
 
 /* ---- MPolynomial.evaluate_symbolic in the value domain : code/multivariate.py:83-90 (call site fast_stark.py:109-110) ---- */

@@ -179,6 +179,8 @@ struct NttOpts {
     uint32_t cols = 1;       // independent transforms in one set of launches, column c at element c * n of in / out (NttIo::cols)
     uint64_t col_stride_in = 0;   // ... of `in` at c * col_stride_in instead (0 = n)
 };
+// elements one set of column launches covers at most (sc_ntt_columns_dev, sc_coset_evaluate_columns_dev, sc_geodomain_interpolate_columns_dev)
+constexpr uint64_t COLS_ELEMS_PER_LAUNCH = 1ull << 26;
 
 // Climb from level `lvl` (already in the tree, `N >> lvl` nodes) to the root.  Levels wider than FUSE_MAX_W nodes are
 // throughput-bound: launches that fuse merkle_big_nlev (2) levels -- a workgroup's 256 -> 128 -> 64 nodes keep every active

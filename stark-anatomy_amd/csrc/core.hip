@@ -246,6 +246,38 @@ __global__ void __launch_bounds__(256) vec_degree_kernel(const Fe* __restrict__ 
         if (m >= 0) atomicMax(out + (blockIdx.x & (DEGREE_SLOTS - 1)), m);
     }
 }
+// The same for many vectors in one launch: column c is the n elements at v + c * ld, out[c] (preset to -1) its degree.  Workgroup b
+// scans part b % per_col of column b / per_col (a flat grid: a block per column in grid.y stops at 65 535 columns), four rows of
+// 256 elements per step like the kernel above; one atomic per workgroup that saw a non-zero element, on its column's own word.
+__global__ void __launch_bounds__(256) vec_degree_cols_kernel(const Fe* __restrict__ v, uint64_t n, uint64_t ld, uint32_t per_col, long long* out) {
+    const uint64_t col = blockIdx.x / per_col;
+    const uint32_t part = blockIdx.x - (uint32_t)col * per_col;
+    const Fe* __restrict__ w = v + col * ld;
+    const uint64_t step = (uint64_t)per_col * (256 * DEGREE_PER_THREAD);
+    long long best = -1;
+    for (uint64_t base = (uint64_t)part * (256 * DEGREE_PER_THREAD) + threadIdx.x; base - threadIdx.x < n; base += step) {
+        Fe x[DEGREE_PER_THREAD];
+#pragma unroll
+        for (int k = 0; k < DEGREE_PER_THREAD; ++k) {
+            const uint64_t i = base + 256u * k;
+            x[k] = i < n ? w[i] : Fe{0, 0};
+        }
+#pragma unroll
+        for (int k = 0; k < DEGREE_PER_THREAD; ++k) {
+            const unsigned long long lanes = __ballot(!fe_is_zero(x[k]));
+            if (lanes) best = (long long)(base - (threadIdx.x & 63u) + 256u * k + (63 - __clzll((long long)lanes)));
+        }
+    }
+    __shared__ long long wave_best[4];
+    if ((threadIdx.x & 63u) == 0) wave_best[threadIdx.x >> 6] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long long m = wave_best[0];
+#pragma unroll
+        for (int k = 1; k < 4; ++k) m = wave_best[k] > m ? wave_best[k] : m;
+        if (m >= 0) atomicMax(out + col, m);
+    }
+}
 // the maximum of the kernel's DEGREE_SLOTS words (each -1 or an index), read in one polled transfer
 static int degree_read(void* fl, hipStream_t st, long long* deg) {
     long long slots[DEGREE_SLOTS];
@@ -1282,7 +1314,6 @@ int sc_ntt_dev(const void* d_in, void* d_out, uint64_t n, const uint64_t root[2]
 // `cols` independent transforms of length n, column c at element c * n, in ONE set of launches (NttIo::cols): the workgroups of one
 // column start while those of another finish.  A set of launches covers at most COLS_ELEMS_PER_LAUNCH elements (64 columns of 2^20,
 // 4 096 of 2^14: the grid of a set must be long whatever the length of a column), which bounds the intermediate vector at 1 GiB.
-constexpr uint64_t COLS_ELEMS_PER_LAUNCH = 1ull << 26;
 int sc_ntt_columns_dev(const void* d_in, void* d_out, uint64_t n, uint64_t cols, const uint64_t root[2], int inverse, void* stream) {
     std::lock_guard<std::mutex> lk(g_mu);
     SCCHK(ensure_init());
@@ -1635,6 +1666,39 @@ int sc_vec_degree_dev(const void* d_v, uint64_t n, int64_t* degree_out, void* st
         SCCHK(degree_read(fl, st, &deg));
     }
     *degree_out = (int64_t)deg;
+    return SC_OK;
+}
+
+// Polynomial.degree of `cols` vectors, column c at element c * ld: ONE kernel for a set of up to DEGREE_COLS_PER_LAUNCH columns, and the
+// host waits once -- for the first polled read of DEGREE_SLOTS words (what the pinned slot of sc_vec_degree_dev carries); the reads
+// of the set's other words find the kernel finished.
+constexpr uint64_t DEGREE_COLS_PER_LAUNCH = 4096;
+int sc_vec_degree_columns_dev(const void* d_v, uint64_t n, uint64_t ld, uint64_t cols, int64_t* degrees_out, void* stream) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    if (cols == 0) return SC_OK;
+    if (!degrees_out || (n && !d_v) || ld < n) return fail(SC_ERR_BAD_ARG, n && ld < n ? "a column stride below the column length" : "null argument");
+    hipStream_t st = pick_stream(stream);
+    if (n == 0) {
+        for (uint64_t c = 0; c < cols; ++c) degrees_out[c] = -1;
+        return SC_OK;
+    }
+    void* fl;
+    SCCHK(scratch(7, DEGREE_COLS_PER_LAUNCH * sizeof(long long), &fl));
+    const uint64_t rows = (n + 256 * DEGREE_PER_THREAD - 1) / (256 * DEGREE_PER_THREAD);
+    const uint32_t per_col = (uint32_t)(rows < 64 ? rows : 64);
+    for (uint64_t done = 0; done < cols; done += DEGREE_COLS_PER_LAUNCH) {
+        const uint64_t k = cols - done < DEGREE_COLS_PER_LAUNCH ? cols - done : DEGREE_COLS_PER_LAUNCH;
+        const uint64_t words = (k + DEGREE_SLOTS - 1) / DEGREE_SLOTS * DEGREE_SLOTS;
+        HIPCHK(hipMemsetAsync(fl, 0xFF, words * sizeof(long long), st));
+        hipLaunchKernelGGL(vec_degree_cols_kernel, dim3((unsigned)(k * per_col)), dim3(256), 0, st, (const Fe*)d_v + done * ld, n, ld, per_col, (long long*)fl);
+        HIPCHK(hipGetLastError());
+        for (uint64_t w = 0; w < k; w += DEGREE_SLOTS) {
+            long long slots[DEGREE_SLOTS];
+            SCCHK(read_small_polled((const long long*)fl + w, sizeof slots, st, slots));
+            for (uint64_t i = 0; i < DEGREE_SLOTS && w + i < k; ++i) degrees_out[done + w + i] = (int64_t)slots[i];
+        }
+    }
     return SC_OK;
 }
 

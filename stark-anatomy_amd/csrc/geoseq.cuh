@@ -147,6 +147,45 @@ __global__ void __launch_bounds__(256) geo_rev_scale_kernel(const Fe* __restrict
     out[j] = v;
 }
 
+// ---- the interpolation's elementwise steps for MANY COLUMNS in one launch (sc_geodomain_interpolate_columns_dev) ----------------
+// A flat grid over cols * len threads (a block per column in grid.y stops at 65 535 columns); thread t works on position
+// i = t mod len of column c = t / len.  The tables are the domain's, shared by the columns, and are indexed by i; the arithmetic
+// per element is that of the single-column kernels above, so the results are the same bits.
+// out[c * ld_out + i] = in[c * ld_in + i] * tab[i], i < n
+__global__ void __launch_bounds__(256) geo_mul_tab_cols_kernel(const Fe* __restrict__ in, uint64_t ld_in, const Fe* __restrict__ tab_m, Fe* __restrict__ out, uint64_t ld_out,
+                                                              uint64_t n, uint64_t total) {
+    const uint64_t t = GS_INDEX();
+    if (t >= total) return;
+    const uint64_t c = t / n, i = t - c * n;
+    out[c * ld_out + i] = mont_mul(in[c * ld_in + i], tab_m[i]);
+}
+
+// D[c][f] = c_m2 * A[c][-f] * B[f] on [cols][M] buffers, M = 2^logM
+__global__ void __launch_bounds__(256) geo_corr_cols_kernel(const Fe* __restrict__ A, const Fe* __restrict__ B, Fe* __restrict__ D, int logM, uint64_t total, Fe c_m2) {
+    const uint64_t t = GS_INDEX();
+    if (t >= total) return;
+    const uint64_t M = 1ull << logM, f = t & (M - 1), col = t - f;
+    D[t] = mont_mul(mont_mul(A[col + ((M - f) & (M - 1))], B[f]), c_m2);
+}
+
+// D[c][f] = c_m2 * A[c][f] * B[f] on [cols][M] buffers (pt_mul_scaled_kernel with a shared second operand)
+__global__ void __launch_bounds__(256) geo_mul_scaled_cols_kernel(const Fe* __restrict__ A, const Fe* __restrict__ B, Fe* __restrict__ D, int logM, uint64_t total, Fe c_m2) {
+    const uint64_t t = GS_INDEX();
+    if (t >= total) return;
+    D[t] = mont_mul(mont_mul(A[t], B[t & ((1ull << logM) - 1)]), c_m2);
+}
+
+// out[c * ld_out + j] = qrev[c * ld_q + n - 1 - j] * c^-j, j < n (ilo == nullptr: c = 1)
+__global__ void __launch_bounds__(256) geo_rev_scale_cols_kernel(const Fe* __restrict__ qrev, uint64_t ld_q, uint64_t n, uint64_t total, const Fe* __restrict__ ilo,
+                                                                const Fe* __restrict__ ihi, Fe* __restrict__ out, uint64_t ld_out) {
+    const uint64_t t = GS_INDEX();
+    if (t >= total) return;
+    const uint64_t c = t / n, j = t - c * n;
+    Fe v = qrev[c * ld_q + (n - 1 - j)];
+    if (ilo) v = mont_mul(v, pow2level(ilo, ihi, j));
+    out[c * ld_out + j] = v;
+}
+
 // zerofier of {c q^i}: coefficient j = zr[n - j] * c^(n - j), j = 0..n
 __global__ void __launch_bounds__(256) geo_zerofier_out_kernel(const Fe* __restrict__ zr, uint64_t n, const Fe* __restrict__ clo, const Fe* __restrict__ chi, Fe* __restrict__ out) {
     const uint64_t j = GS_INDEX();

@@ -466,6 +466,47 @@ int geodomain_interpolate(const sc_geodomain* d, const Fe* values, Fe* out, hipS
     return SC_OK;
 }
 
+// geodomain_interpolate for `cols` columns: column c's n values at values + c * ld_in, its n coefficients at out + c * ld_out.
+// The same nine steps, each issued ONCE for a set of columns: the four transforms through the column form of ntt_device
+// (NttOpts::cols on [cols][M] work buffers, zero padding above n per column), the five elementwise steps over a flat grid of
+// cols * len threads.  A set holds at most COLS_ELEMS_PER_LAUNCH / M and at most 65 536 columns (as sc_ntt_columns_dev splits),
+// which bounds the two temporaries at 1 GiB each.  Nothing waits.
+int geodomain_interpolate_columns(const sc_geodomain* d, const Fe* values, uint64_t ld_in, uint64_t cols, Fe* out, uint64_t ld_out, hipStream_t st) {
+    const uint64_t n = d->n, M = d->M;
+    uint64_t per = COLS_ELEMS_PER_LAUNCH / M;
+    if (per < 1) per = 1;
+    if (per > 65536) per = 65536;
+    if (per > cols) per = cols;
+    PoolTmpAsync bx, by;
+    SCCHK(bx.get(per * M * sizeof(Fe)));
+    SCCHK(by.get(per * M * sizeof(Fe)));
+    const Fe rt = canonical_root(d->logM), rti = root_inverse(rt, M);
+    const Fe c_m2 = ninv_scaled(d->logM, 2);
+    for (uint64_t done = 0; done < cols; done += per) {
+        const uint64_t k = cols - done < per ? cols - done : per;
+        const Fe* v = values + done * ld_in;
+        Fe* o = out + done * ld_out;
+        int rc;
+        const PowTables* pi = geo_cpow(d, d->c_inv, n, st, &rc);       // (looked up per set: a table in use is a recent lookup)
+        SCCHK(rc);
+        NttOpts padded, whole;
+        padded.cols = whole.cols = (uint32_t)k;
+        padded.in_limit = n;
+        hipLaunchKernelGGL(geo_mul_tab_cols_kernel, dim3(pt_blocks(k * n)), dim3(256), 0, st, v, ld_in, (const Fe*)d->wden_m, bx.fe(), M, n, k * n);
+        SCCHK(ntt_device(bx.fe(), by.fe(), d->logM, rt, false, padded, st));
+        hipLaunchKernelGGL(geo_corr_cols_kernel, dim3(pt_blocks(k * M)), dim3(256), 0, st, (const Fe*)by.fe(), (const Fe*)d->Bf, bx.fe(), d->logM, k * M, c_m2);
+        SCCHK(ntt_device(bx.fe(), by.fe(), d->logM, rti, false, whole, st));
+        hipLaunchKernelGGL(geo_mul_tab_cols_kernel, dim3(pt_blocks(k * n)), dim3(256), 0, st, (const Fe*)by.fe(), M, (const Fe*)d->tinv_m, bx.fe(), M, n, k * n);
+        SCCHK(ntt_device(bx.fe(), by.fe(), d->logM, rt, false, padded, st));
+        hipLaunchKernelGGL(geo_mul_scaled_cols_kernel, dim3(pt_blocks(k * M)), dim3(256), 0, st, (const Fe*)by.fe(), (const Fe*)d->ZRf, bx.fe(), d->logM, k * M, c_m2);
+        SCCHK(ntt_device(bx.fe(), by.fe(), d->logM, rti, false, whole, st));
+        hipLaunchKernelGGL(geo_rev_scale_cols_kernel, dim3(pt_blocks(k * n)), dim3(256), 0, st, (const Fe*)by.fe(), M, n, k * n, pi ? (const Fe*)pi->lo : nullptr,
+                           pi ? (const Fe*)pi->hi : nullptr, o, ld_out);
+        HIPCHK(hipGetLastError());
+    }
+    return SC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -678,6 +719,14 @@ int sc_geodomain_interpolate_dev(const sc_geodomain_t* domain, const void* d_val
     SCCHK(ensure_init());
     if (!domain || !d_values || !d_out) return fail(SC_ERR_BAD_ARG, "null argument");
     return geodomain_interpolate(domain, (const Fe*)d_values, (Fe*)d_out, pick_stream(stream));
+}
+int sc_geodomain_interpolate_columns_dev(const sc_geodomain_t* domain, const void* d_values, uint64_t ld_in, uint64_t cols, void* d_out, uint64_t ld_out, void* stream) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    if (!domain || !d_values || !d_out) return fail(SC_ERR_BAD_ARG, "null argument");
+    if (ld_in < domain->n || ld_out < domain->n) return fail(SC_ERR_BAD_ARG, "a column stride below the number of points");
+    if (cols == 0) return SC_OK;
+    return geodomain_interpolate_columns(domain, (const Fe*)d_values, ld_in, cols, (Fe*)d_out, ld_out, pick_stream(stream));
 }
 int sc_geodomain_free(sc_geodomain_t* domain) {
     std::lock_guard<std::mutex> lk(g_mu);

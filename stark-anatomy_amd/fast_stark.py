@@ -206,6 +206,12 @@ class FastStark:
     DEVICE_MIN = 32
     # True: every commitment waits for its root before the prover goes on (the reference's order of events; A/B of proof_objects.RootLater)
     EAGER_COMMITS = False
+    # Traces of at least this many registers are proved in COLUMN BATCHES on the device data flow: the registers are the rows of one
+    # matrix, and trace interpolation, the trace polynomials' degrees, the boundary-quotient LDEs and the trace's values on the
+    # transition quotients' coset are one library call each for all registers instead of one per register.  Same polynomials, same
+    # codewords, same pushes and draws in the same order: the proofs are byte-identical (tests/test_gpu_wide_stark.py).  Narrower
+    # traces run the per-register code.  (Measured: tools/wide_trace_timing.py, profiles/column_batches/.)
+    COLUMN_BATCH_MIN = 4
 
     def _lde(self, polynomial):
         """Low-degree extension onto the FRI coset  generator * omega^i  (the LDE kernel)."""
@@ -279,13 +285,20 @@ class FastStark:
             # the randomizer polynomial's draws (fast_stark.py:116-117: one os.urandom(17) per coefficient, 36 MB at a 2^24 FRI
             # domain) start now and pass while the GPU works on the trace
             prefetch_random_polynomial(self.max_degree(transition_constraints) + 1)
-            columns = self._randomized_columns(trace, draw_random_bytes(self.num_randomizers * self.num_registers))
+            batched = self.num_registers >= FastStark.COLUMN_BATCH_MIN
+            columns = self._randomized_columns(trace, draw_random_bytes(self.num_randomizers * self.num_registers), batched)
             trace_rows, on_device = len(trace) + self.num_randomizers, True
         else:
             trace = trace + [[field.sample(os.urandom(17)) for s in registers] for _ in range(self.num_randomizers)]
             trace_rows = len(trace)
             on_device = trace_rows >= FastStark.DEVICE_MIN and field.p == Field.P_MAIN
-            if on_device:
+            batched = on_device and self.num_registers >= FastStark.COLUMN_BATCH_MIN
+            if batched:
+                # one upload: the registers are the rows of one matrix, each column a view of its row
+                lists = [[row[s] for row in trace] for s in registers]
+                matrix = DeviceVector.from_bytes(b"".join(_sc.pack(list(map(_sc._value_of, column))) for column in lists))
+                columns = [DeviceCodeword(DeviceVector.wrap(matrix.ptr + 16 * trace_rows * s, trace_rows, matrix), field, elements=lists[s]) for s in registers]
+            elif on_device:
                 columns = [DeviceCodeword.from_list([row[s] for row in trace], field) for s in registers]
         interpolants = self.boundary_interpolants(boundary)
         zerofiers = self.boundary_zerofiers(boundary)
@@ -299,7 +312,13 @@ class FastStark:
             # exactness decided on the device), the AIR substitution in the value domain, the transition quotients, the LDEs and
             # the combination.  The host keeps what byte parity ties to it: os.urandom draws, Fiat-Shamir, the proof stream.
             trace_domain = self._trace_domain(trace_rows)
-            trace_polynomials = [DevicePolynomial.from_codeword(fast_interpolate_device(trace_domain, column)) for column in columns]
+            if batched:
+                # all registers in one set of launches, and their degrees in one host wait: minus() below and the transition
+                # quotients find them known
+                trace_polynomials = [DevicePolynomial.from_codeword(c) for c in fast_interpolate_columns_device(trace_domain, columns)]
+                DevicePolynomial.degrees(trace_polynomials)
+            else:
+                trace_polynomials = [DevicePolynomial.from_codeword(fast_interpolate_device(trace_domain, column)) for column in columns]
             self._mark("trace interpolation")
             zerofiers_dev = [DevicePolynomial.from_polynomial(z, field) for z in zerofiers]
             boundary_quotients = [coset_divide_device(trace_polynomials[s].minus(interpolants[s]), zerofiers_dev[s], self.generator, self.omicron,
@@ -325,9 +344,14 @@ class FastStark:
                 later.add(_po.RootLater(codeword.start_tree()))
             else:
                 proof_stream.push(Merkle.commit(codeword))
-        for s in registers:
-            boundary_quotient_codewords.append(lde(boundary_quotients[s]))
-            commit(boundary_quotient_codewords[s])
+        if on_device and batched:
+            boundary_quotient_codewords = self._lde_columns(boundary_quotients)
+            for s in registers:
+                commit(boundary_quotient_codewords[s])
+        else:
+            for s in registers:
+                boundary_quotient_codewords.append(lde(boundary_quotients[s]))
+                commit(boundary_quotient_codewords[s])
         self._mark("boundary quotient LDEs + commitments")
 
         # transition polynomials: AIR evaluated symbolically in (X, trace(X), trace(omicron X)), then quotients
@@ -335,7 +359,7 @@ class FastStark:
         point = [DevicePolynomial.from_polynomial(x, field) if on_device else x] + trace_polynomials + \
                 [tp.scaled_later(self.omicron) if on_device else tp.scale(self.omicron) for tp in trace_polynomials]
         if on_device:
-            transition_quotients = self._transition_quotients_on_device(transition_constraints, point, self._lift(transition_zerofier), pending)
+            transition_quotients = self._transition_quotients_on_device(transition_constraints, point, self._lift(transition_zerofier), pending, batched)
         else:
             transition_polynomials = [a.evaluate_symbolic(point) for a in transition_constraints]
             transition_quotients = [fast_coset_divide(tp, transition_zerofier, self.generator, self.omicron, self.omicron_domain_length) for tp in transition_polynomials]
@@ -414,7 +438,21 @@ class FastStark:
         self._mark("proof serialization (host pickle)")
         return proof
 
-    def _transition_quotients_on_device(self, constraints, point, tz_dev, pending=None):
+    def _lde_columns(self, polynomials):
+        """[p.coset_evaluate(generator, omega, fri_domain_length) for p in polynomials] as one call: the coefficient vectors are
+        zero-padded to the longest in one matrix (the padding evaluates to the same values) and the codewords are views of the
+        rows of one codeword matrix"""
+        lib, count, order = _sc.lib(), len(polynomials), self.fri_domain_length
+        m = max(max(len(p) for p in polynomials), 1)
+        coefficients = DeviceVector.zeros(count * m)
+        for c, p in enumerate(polynomials):
+            if len(p):
+                _sc._check(lib.sc_memcpy_dev(coefficients.ptr + 16 * m * c, p.vec.ptr, len(p), None))
+        values = DeviceVector(count * order)
+        _sc._check(lib.sc_coset_evaluate_columns_dev(coefficients.ptr, m, count, _sc.fe_bytes(self.generator.value), _sc.fe_bytes(self.omega.value), order, values.ptr, None))
+        return [DeviceCodeword(DeviceVector.wrap(values.ptr + 16 * order * c, order, values), self.field) for c in range(count)]
+
+    def _transition_quotients_on_device(self, constraints, point, tz_dev, pending=None, batched=False):
         """fast_stark.py:107-113 -- `a.evaluate_symbolic(point)` divided by the transition zerofier -- without ever building the
         transition polynomial: on the coset g * <root'> (root' of the order code/ntt.py:155-157 shrinks to, taken from the degree
         BOUND) the point polynomials are evaluated once for all constraints of that order, the AIR is evaluated value by value
@@ -457,8 +495,9 @@ class FastStark:
                         turned[j] = k
             stored = [(used[j] and j not in turned) or j in turned.values() for j in range(nvars)]
             vals = DeviceVector(nvars * order)
+            in_runs = self._evaluate_runs(point, stored, rt, order, vals) if batched else ()
             for j, q in enumerate(point):
-                if stored[j]:
+                if stored[j] and j not in in_runs:
                     source = getattr(q, "scaled_from", None)
                     if source is not None:
                         # q(f X) on g <root> is q on (g f) <root>: the transform's own offset does the scaling, the scaled
@@ -496,6 +535,36 @@ class FastStark:
                 out[i]._degree = degree                                  # just read: the degree check of fast_stark.py:124 need not ask the device again
         return [q if q is not None else reference_way(a) for q, a in zip(out, constraints)]
 
+    def _evaluate_runs(self, point, stored, rt, order, vals):
+        """The stored variables whose coefficient vectors are consecutive rows of one matrix -- trace_s(X) for consecutive s, and
+        trace_s(omicron X) where they are not read off the former -- evaluated into their (consecutive) places of `vals` by ONE
+        sc_coset_evaluate_columns_dev per maximal run of equal length and equal offset (g, or g * omicron: the transform's own
+        offset does the scaling).  Returns the variables served."""
+        lib, done = _sc.lib(), set()
+
+        def place(j):
+            """(where variable j's coefficients are, how many, the offset they are evaluated at), None if they are not plain rows"""
+            source = getattr(point[j], "scaled_from", None)
+            poly, offset = (source[0], self.generator * source[1]) if source is not None else (point[j], self.generator)
+            if type(poly) is not DevicePolynomial or len(poly) == 0:
+                return None                                 # (all len(poly) coefficients go in: those above the degree are zeros)
+            return poly.vec.ptr, len(poly), offset.value
+        j, nvars = 0, len(point)
+        while j < nvars:
+            first = place(j) if stored[j] else None
+            run = 1
+            if first is not None:
+                while j + run < nvars and stored[j + run]:
+                    following = place(j + run)
+                    if following is None or following[1:] != first[1:] or following[0] != first[0] + 16 * first[1] * run:
+                        break
+                    run += 1
+            if first is not None and run >= 2:
+                _sc._check(lib.sc_coset_evaluate_columns_dev(first[0], first[1], run, _sc.fe_bytes(first[2]), rt, order, vals.ptr + 16 * j * order, None))
+                done.update(range(j, j + run))
+            j += run
+        return done
+
     @staticmethod
     def _pointwise_divide(numerator, denominator, count, pending):
         """numerator[i] /= denominator[i] on the device; with a list of pending checks the "divide by zero" verdict is collected, not waited for"""
@@ -513,7 +582,7 @@ class FastStark:
                 return
         _sc._check(lib.sc_pointwise_div_dev(numerator.ptr, denominator.ptr, numerator.ptr, count, None))
 
-    def _randomized_columns(self, trace, raw):
+    def _randomized_columns(self, trace, raw, together=False):
         """the columns of a DeviceTrace with the randomizer rows appended (fast_stark.py:79-81): `raw` holds the draws of
         os.urandom(17) in the reference's order -- row by row, register by register; 4 * num_colinearity_checks rows, sampled on
         the host and written behind each column's copy"""
@@ -522,9 +591,10 @@ class FastStark:
         # Field.sample (algebra.py:116-120: big-endian accumulate, then % p) of every 17-byte draw, without an object per draw
         p, big = self.field.p, int.from_bytes
         columns = []
+        matrix = DeviceVector(width * (rows + extra)) if together else None      # together: the columns are views of the rows of one matrix
         for s in range(width):
             tail = b"".join((big(raw[17 * (r * width + s):17 * (r * width + s) + 17], "big") % p).to_bytes(16, "little") for r in range(extra))
-            column = DeviceVector(rows + extra)
+            column = DeviceVector(rows + extra) if matrix is None else DeviceVector.wrap(matrix.ptr + 16 * (rows + extra) * s, rows + extra, matrix)
             _sc._check(_sc.lib().sc_memcpy_dev(column.ptr, trace.columns[s].ptr, rows, None))
             if extra:
                 _sc._check(_sc.lib().sc_vec_upload(column._h, rows, tail, extra))

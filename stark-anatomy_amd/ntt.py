@@ -83,6 +83,38 @@ def intt(primitive_root, values):
     return _transform(primitive_root, values, 1)
 
 
+def _transform_columns(primitive_root, columns, inverse):
+    columns = list(columns)
+    if not columns:
+        return []
+    n = len(columns[0])
+    assert(all(len(c) == n for c in columns)), "the columns of one call have one length"
+    assert(n & (n - 1) == 0), "cannot compute intt of non-power-of-two sequence" if inverse else "cannot compute ntt of non-power-of-two sequence"
+    if n == 1 or (n == 0 and not inverse):
+        return columns                                    # ntt / intt hand a sequence of this length back as it is
+    field = columns[0][0].field
+    assert(primitive_root ^ n == field.one()), "primitive root must be nth root of unity, where n is len(values)"
+    assert(primitive_root ^ (n // 2) != field.one()), "primitive root is not primitive nth root of unity, where n is len(values)"
+    _require_main_field(field)
+    cols = len(columns)
+    src = DeviceVector.from_bytes(b"".join(_pack(c) for c in columns))
+    out = DeviceVector(cols * n)
+    _sc._check(_sc.lib().sc_ntt_columns_dev(src.ptr, out.ptr, n, cols, _sc.fe_bytes(primitive_root.value), inverse, None))
+    flat = _unpack(out.to_bytes(), cols * n, field)
+    return [flat[c * n:(c + 1) * n] for c in range(cols)]
+
+
+def ntt_columns(primitive_root, columns):
+    """[ntt(primitive_root, c) for c in columns] for equal-length lists, as ONE call (sc_ntt_columns_dev): one upload, one set of
+    launches for all columns, one download"""
+    return _transform_columns(primitive_root, columns, 0)
+
+
+def intt_columns(primitive_root, columns):
+    """[intt(primitive_root, c) for c in columns], likewise"""
+    return _transform_columns(primitive_root, columns, 1)
+
+
 def _shrink_order(root, order, degree):
     # smallest power-of-two transform that still holds `degree+1` coefficients (ntt.py:47-49, :155-157)
     while degree < order // 2:
@@ -274,6 +306,22 @@ class DevicePolynomial:
             self._degree = int(deg.value)
         return self._degree
 
+    @staticmethod
+    def degrees(polynomials):
+        """[p.degree() for p in polynomials], with ONE device call and one host wait (sc_vec_degree_columns_dev) for the members
+        that do not know their degree yet when those are equally spaced rows of one matrix -- the trace polynomials of a wide
+        trace; anything else is asked one by one"""
+        unknown = [p for p in polynomials if p._degree is None and type(p) is DevicePolynomial]
+        if len(unknown) >= 2 and unknown[0].n > 0 and all(p.n == unknown[0].n for p in unknown):
+            n, places = unknown[0].n, [p.vec.ptr for p in unknown]
+            pitch = places[1] - places[0]
+            if pitch >= 16 * n and pitch % 16 == 0 and all(b - a == pitch for a, b in zip(places, places[1:])):
+                found = (ctypes.c_int64 * len(unknown))()
+                _sc._check(_sc.lib().sc_vec_degree_columns_dev(places[0], n, pitch // 16, len(unknown), found, None))
+                for p, degree in zip(unknown, found):
+                    p._degree = int(degree)
+        return [p.degree() for p in polynomials]
+
     def is_zero(self):
         return self.degree() == -1
 
@@ -414,6 +462,53 @@ def fast_interpolate_device(domain, values):
     return DeviceCodeword(domain.tree.interpolate(values.vec), domain.field)
 
 
+def _rows_of(matrix, count, n, field):
+    """the rows of a [count][n] device matrix as DeviceCodewords that are views of it (the matrix lives as long as any of them)"""
+    return [DeviceCodeword(DeviceVector.wrap(matrix.ptr + 16 * n * c, n, matrix), field) for c in range(count)]
+
+
+def fast_interpolate_columns_device(domain, values):
+    """[fast_interpolate_device(domain, v) for v in values] for DeviceCodewords of len(domain) values each.  On a progression
+    domain every step of the interpolation is issued once for all columns (sc_geodomain_interpolate_columns_dev) and the results
+    are views of ONE coefficient matrix [cols][n]; the columns are first copied into one matrix unless they already are the
+    consecutive rows of one.  A tree domain goes column by column through its resident tree."""
+    values = list(values)
+    n = len(domain)
+    for v in values:
+        assert(n == len(v)), "cannot interpolate over domain of different length than values list"
+    if not values:
+        return []
+    if not isinstance(domain.tree, _sc.GeoDomain):
+        return [fast_interpolate_device(domain, v) for v in values]
+    cols = len(values)
+    first = values[0].vec.ptr
+    if all(v.vec.ptr == first + 16 * n * c for c, v in enumerate(values)):
+        matrix = _View(values[0].vec, cols * n)            # (`values` keeps the owner alive for the call; frees are parked behind the stream)
+    else:
+        matrix = DeviceVector(cols * n)
+        for c, v in enumerate(values):
+            _sc._check(_sc.lib().sc_memcpy_dev(matrix.ptr + 16 * n * c, v.vec.ptr, n, None))
+    return _rows_of(domain.tree.interpolate_columns(matrix, cols), cols, n, domain.field)
+
+
+def fast_interpolate_columns(domain, values_list, primitive_root, root_order):
+    """[fast_interpolate(domain, v, primitive_root, root_order) for v in values_list]: on a domain that goes to the device
+    and is a progression, one upload, one column interpolation, one download"""
+    _check_root(primitive_root, root_order)
+    values_list = list(values_list)
+    for values in values_list:
+        assert(len(domain) == len(values)), "cannot interpolate over domain of different length than values list"
+    if not values_list:
+        return []
+    n, cols = len(domain), len(values_list)
+    tables = _device_tree(domain) if n >= DEVICE_TREE_MIN_POINTS else None
+    if not isinstance(tables, _sc.GeoDomain):
+        return [fast_interpolate(domain, values, primitive_root, root_order) for values in values_list]
+    matrix = DeviceVector.from_bytes(b"".join(_pack(values) for values in values_list))
+    flat = _unpack(tables.interpolate_columns(matrix, cols).to_bytes(), cols * n, primitive_root.field)
+    return [Polynomial(flat[c * n:(c + 1) * n]) for c in range(cols)]
+
+
 def fast_coset_evaluate_device(polynomial, offset, generator, order):
     """fast_coset_evaluate with the result left in HBM as a DeviceCodeword."""
     coeffs = polynomial.coefficients
@@ -440,6 +535,28 @@ def fast_coset_evaluate(polynomial, offset, generator, order):
     out = ctypes.create_string_buffer(16 * order)
     _sc._check(_sc.lib().sc_coset_evaluate(_pack(coeffs), m, _sc.fe_bytes(offset.value), _sc.fe_bytes(generator.value), order, out))
     return _unpack(out.raw, order, field)
+
+
+def fast_coset_evaluate_columns(polynomials, offset, generator, order):
+    """[fast_coset_evaluate(p, offset, generator, order) for p in polynomials] as ONE call (sc_coset_evaluate_columns_dev): the
+    coefficient lists are zero-padded to the longest (padding evaluates to the same values), one upload, one download"""
+    polynomials = list(polynomials)
+    if not polynomials:
+        return []
+    lengths = [len(p.coefficients) for p in polynomials]
+    if order <= 1 or max(lengths) > order:
+        return [fast_coset_evaluate(p, offset, generator, order) for p in polynomials]
+    assert(order & (order - 1) == 0), "cannot compute ntt of non-power-of-two sequence"
+    field = offset.field
+    assert(generator ^ order == field.one()), "primitive root must be nth root of unity, where n is len(values)"
+    assert(generator ^ (order // 2) != field.one()), "primitive root is not primitive nth root of unity, where n is len(values)"
+    _require_main_field(field)
+    m, cols = max(max(lengths), 1), len(polynomials)
+    src = DeviceVector.from_bytes(b"".join(_pack(p.coefficients) + bytes(16 * (m - k)) for p, k in zip(polynomials, lengths)))
+    out = DeviceVector(cols * order)
+    _sc._check(_sc.lib().sc_coset_evaluate_columns_dev(src.ptr, m, cols, _sc.fe_bytes(offset.value), _sc.fe_bytes(generator.value), order, out.ptr, None))
+    flat = _unpack(out.to_bytes(), cols * order, field)
+    return [flat[c * order:(c + 1) * order] for c in range(cols)]
 
 
 def fast_coset_divide(lhs, rhs, offset, primitive_root, root_order):  # clean division only!

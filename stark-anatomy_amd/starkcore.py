@@ -87,6 +87,7 @@ SIGNATURES = {
     "sc_coset_divide": (_int, [_vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _u64]),
     "sc_coset_divide_dev": (_int, [_vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _u64, ctypes.POINTER(_int), _vp]),
     "sc_vec_degree_dev": (_int, [_vp, _u64, ctypes.POINTER(ctypes.c_int64), _vp]),
+    "sc_vec_degree_columns_dev": (_int, [_vp, _u64, _u64, _u64, ctypes.POINTER(ctypes.c_int64), _vp]),
     "sc_pointwise_mul_dev": (_int, [_vp, _vp, _vp, _u64, _vp]),
     "sc_pointwise_div_dev": (_int, [_vp, _vp, _vp, _u64, _vp]),
     "sc_coset_divide_later_dev": (_int, [_vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _u64, ctypes.POINTER(_vp), _vp]),
@@ -156,6 +157,7 @@ SIGNATURES = {
     "sc_geodomain_zerofier_dev": (_int, [_vp, _vp, _vp]),
     "sc_geodomain_evaluate_dev": (_int, [_vp, _vp, _u64, _vp, _vp]),
     "sc_geodomain_interpolate_dev": (_int, [_vp, _vp, _vp, _vp]),
+    "sc_geodomain_interpolate_columns_dev": (_int, [_vp, _vp, _u64, _u64, _vp, _u64, _vp]),
     "sc_geodomain_free": (_int, [_vp]),
 }
 
@@ -667,6 +669,14 @@ class GeoDomain:
         assert values.n == self.k
         out = DeviceVector(self.k)
         _check(lib().sc_geodomain_interpolate_dev(self._h, values.ptr, out.ptr, None))
+        return out
+
+    def interpolate_columns(self, values_matrix, cols):
+        """values_matrix: DeviceVector [cols][k], column c's values at element c * k -> DeviceVector [cols][k] of the columns'
+        coefficients; every step of `interpolate` issued once for all columns (sc_geodomain_interpolate_columns_dev)"""
+        assert values_matrix.n >= cols * self.k
+        out = DeviceVector(max(cols * self.k, 1))
+        _check(lib().sc_geodomain_interpolate_columns_dev(self._h, values_matrix.ptr, self.k, cols, out.ptr, self.k, None))
         return out
 
     def free(self):

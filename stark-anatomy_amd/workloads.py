@@ -47,6 +47,37 @@ def synthetic_stark_instance(log_fri, s=40):
     return field, T, [pack(col_a), pack(col_b)], air, boundary
 
 
+def synthetic_wide_columns(rows, registers, p):
+    """the wide workload's trace as one list of ints per register: row 0 is r_i = 7 i + 3, then r_i' = r_i^2 + r_((i+1) mod w) (mod p)"""
+    w = registers
+    row = [7 * i + 3 for i in range(w)]
+    columns = [[v] for v in row]
+    for _ in range(rows - 1):
+        row = [(row[i] * row[i] + row[(i + 1) % w]) % p for i in range(w)]
+        for i in range(w):
+            columns[i].append(row[i])
+    return columns
+
+
+def synthetic_wide_instance(log_fri, registers, s=40):
+    """A trace as wide as real AIRs are: `registers` registers r_0 .. r_(w-1) over T = 2^(log_fri - 4) - 4 s rows with the transition
+    r_i' = r_i^2 + r_((i+1) mod w) (one constraint of degree 2 per register, every register in two of them), row 0 = (7 i + 3);
+    boundary: every register's first cell and register 0's last.  Domains as for synthetic_stark_instance (expansion factor 4, FRI
+    domain 2^log_fri).  Returns (field, T, host rows (lists of FieldElement), packed columns (bytes per register), air, boundary)."""
+    from algebra import Field, FieldElement
+    from multivariate import MPolynomial
+    field = Field.main()
+    w = registers
+    T = (1 << (log_fri - 4)) - 4 * s
+    columns = synthetic_wide_columns(T, w, field.p)
+    pack = lambda col: b"".join(map(int.to_bytes, col, itertools.repeat(16), itertools.repeat("little")))
+    rows = [[FieldElement(columns[i][t], field) for i in range(w)] for t in range(T)]
+    v = MPolynomial.variables(1 + 2 * w, field)           # X, r_0 .. r_(w-1), r_0' .. r_(w-1)'
+    air = [v[1 + w + i] - v[1 + i] * v[1 + i] - v[1 + (i + 1) % w] for i in range(w)]
+    boundary = [(0, i, FieldElement(columns[i][0], field)) for i in range(w)] + [(T - 1, 0, FieldElement(columns[0][T - 1], field))]
+    return field, T, rows, [pack(col) for col in columns], air, boundary
+
+
 def sharded_census(log_fri, rank, world, dev, stream, group=None, checks=40):
     """BASELINE configs[4]: the polynomial-core call census of FastStark.prove (reference code/fast_stark.py:101-151; SURVEY.md
     8(d)) replayed on the SHARDED layout at fri_domain_length 2^log_fri, omicron_domain_length 2^(log_fri-2), 2 registers:
