@@ -62,14 +62,17 @@ int sc_stream(void** stream_out);
 int sc_stream_join(void* other_stream);
 /* tuning knobs for experiments (defaults are the measured optimum; -1 = choose by size where applicable): key in
  * {"max_tile_log","loge","max_col_log","min_tiles_log","single_pass_max_log","max_digit_log","direct_tw_max_log",
- *  "xcd_remap","fixed_shapes","merkle_big_nlev","wave_local","prio_balance","loge_cols","tw_on_load","prune","fast_fixups","fri_tail","fri_tail_stall","small_divisor_direct","verify_stage_kb","forest_four_lane_wgs"}.  Plans are re-derived on the next
+ *  "xcd_remap","fixed_shapes","merkle_big_nlev","wave_local","prio_balance","loge_cols","tw_on_load","prune","fast_fixups","fri_tail","fri_tail_stall","small_divisor_direct","verify_stage_kb","forest_four_lane_wgs","div_cols_chunk","div_cols_launch_log"}.  Plans are re-derived on the next
  * call; results never depend on the tuning ("fri_tail_stall" = k >= 0 is a test hook: the host withholds the challenge after round k of
  * the persistent tail kernel, whose wait then gives up after 2^13 polls; -1 = off; "small_divisor_direct" = 0: sc_coset_divide* transforms a
  * divisor of <= 8 coefficients like any other instead of evaluating it point by point; "verify_stage_kb" = the size of the staging buffer
  * of sc_merkle_verify_batch / sc_fri_colinearity_batch, 65536 by default, at least 16; "forest_four_lane_wgs" = a launch of a Merkle forest of
  * at most this many workgroups runs its narrow levels four lanes per BLAKE2b compression, 0 = never; "fast_fixups" = 1: the eight-element
  * batch kernels correct by +-p on two limbs and an exact kernel redoes the tiles they flag, 0: exact arithmetic on every tile, 2: both
- * kernels on every tile (a test hook) -- see sc_ntt_columns_dev).  Two keys manage the device-memory pool instead (freed vectors and trees are kept
+ * kernels on every tile (a test hook) -- see sc_ntt_columns_dev; "div_cols_chunk" = columns that share one batch inversion in
+ * sc_pointwise_div_columns_later_dev / sc_coset_divide_columns_later_dev with a shared divisor, 0 = chosen by shape; "div_cols_launch_log" = log2 of the values
+ * one set of launches of sc_coset_divide_columns_later_dev takes, 26 by default and at most, at least 1: a test hook that makes the entry
+ * work through a small matrix in several chunks of columns).  Two keys manage the device-memory pool instead (freed vectors and trees are kept
  * on exact-size free lists, by default up to a quarter of the device's memory divided by the processes sharing the device;
  * environment STARKCORE_POOL_CAP_MB): "pool_cap_mb" = what the lists may keep from now on, "pool_trim" = hand everything on them
  * back to the device now (a caller whose own allocator -- torch's -- ran out of memory). */
@@ -238,6 +241,26 @@ int sc_coset_divide_later_dev(const void* d_a, uint64_t na, const void* d_b, uin
                               void* d_out, uint64_t n_out, sc_later_t** later, void* stream);
 int sc_pointwise_div_later_dev(const void* d_a, const void* d_b, void* d_out, uint64_t n, sc_later_t** later, void* stream);
 int sc_later_wait(sc_later_t* later, int64_t words_out[8]);
+/* The two deferred divisions for `cols` COLUMNS of one matrix at once (column c at element c * ld of its operand), with ONE verdict:
+ * whatever `cols`, the call reserves exactly one pinned slot, before anything is enqueued (SC_ERR_UNSUPPORTED: none free, nothing
+ * enqueued, every operand as it was).  Pointwise form: out[c][i] = a[c][i] / b[c][i], i < n; ld_b == 0: ONE divisor row shared by all
+ * columns, inverted once per chunk of columns instead of once per column (sc_set_tuning("div_cols_chunk")); d_out may be d_a
+ * (in place) only with ld_out == ld_a: one matrix with two strides is SC_ERR_BAD_ARG; operands that overlap in any other way are not allowed.
+ * Coset form: column c's quotient is the first n_out[c] coefficients (n_out: host array of `cols` entries) of the interpolant
+ * sc_coset_divide_dev computes for (a_c, b_c) -- a_c: na coefficients, b_c: nb coefficients (a shorter divisor is zero-padded by the
+ * caller), ld_b == 0: one divisor, evaluated once -- and the exactness scan of column c covers [n_out[c], order).
+ * sc_later_wait then returns words_out[2]: the LOWEST column that met a zero divisor or left a remainder, -1 if none; words_out[0],
+ * words_out[1]: that column's zero-divisor flag and remainder index, counted from its n_out[c] -- (0, -1) if no column failed, so the
+ * words keep the meaning they have for a single division; words_out[3]: the number of failing columns.  Quotient values are
+ * unspecified where words_out[0] != 0.  The per-column device words and the value matrices are the call's own (returned to the
+ * pool behind the streams in use), so there is no shared scratch and no one-stream rule: the operands must be complete on `stream`,
+ * and columns-form calls on different streams do not disturb one another beyond sharing the table caches like every transform. */
+int sc_pointwise_div_columns_later_dev(const void* d_a, uint64_t ld_a, const void* d_b, uint64_t ld_b /* 0: one shared row */,
+                                       void* d_out, uint64_t ld_out, uint64_t n, uint64_t cols, sc_later_t** later, void* stream);
+int sc_coset_divide_columns_later_dev(const void* d_a, uint64_t na, uint64_t ld_a, const void* d_b, uint64_t nb, uint64_t ld_b /* 0: shared */,
+                                      uint64_t cols, const uint64_t offset[2], const uint64_t root[2], uint64_t order,
+                                      void* d_out, const uint64_t* n_out /* host, cols entries */, uint64_t ld_out,
+                                      sc_later_t** later, void* stream);
 /* Polynomial.degree (code/univariate.py:7-17) of a coefficient vector in HBM: index of the last non-zero entry, -1 if none (synchronous) */
 int sc_vec_degree_dev(const void* d_v, uint64_t n, int64_t* degree_out, void* stream);
 /* The same for `cols` vectors of n entries each, column c at element c * ld of d_v (ld >= n; entries between the columns are not
@@ -251,6 +274,14 @@ int sc_scale_dev(const void* d_in, void* d_out, uint64_t n, const uint64_t facto
 /* acc[shift + j] += weight * src[j], j < n_src: one term `Polynomial([weight]) * (x ^ shift) * term` of the nonlinear combination
  * of code/fast_stark.py:130-145 on coefficient vectors in HBM (shift + n_src <= n_acc) */
 int sc_axpy_shift_dev(void* d_acc, uint64_t n_acc, const void* d_src, uint64_t n_src, uint64_t shift, const uint64_t weight[2], void* stream);
+/* The whole combination in ONE pass: out[c][i] = sum_t weights[c][t] * src_t[c][i - shift_t] over the terms with
+ * shift_t <= i < shift_t + n_t, for i < n_out and c < cols (term t's column c at element c * ld of d_src; out's at c * ld_out).  Every
+ * element of [0, n_out) of every column is written once -- zero where no term covers it -- so d_out needs no zeroing and may not
+ * alias a source (SC_ERR_BAD_ARG).  weights: host, [cols][nterms], canonical; shift + n <= n_out; any nterms >= 1; cols == 0 or
+ * n_out == 0: nothing happens.  Equal to the chain of sc_axpy_shift_dev calls over a zeroed accumulator, column by column. */
+typedef struct { const void* d_src; uint64_t ld; uint64_t n; uint64_t shift; } sc_combine_term_t;
+int sc_combine_columns_dev(const sc_combine_term_t* terms, uint64_t nterms, const void* weights /* host [cols][nterms] canonical */,
+                           uint64_t cols, void* d_out, uint64_t n_out, uint64_t ld_out, void* stream);
 /* the same scaling (univariate.py:153-154) on one rank's column slab [rows][cols] of a vector viewed as a rows x row_len
  * matrix (multi-GPU fast_coset_evaluate / fast_coset_divide, ntt.py:132-135, :159-176):
  * out[r][c] = in[r][c] * factor^(r * row_len + col_base + c); cols a power of two */

@@ -1,0 +1,262 @@
+// columns.hip -- the kernels of csrc/columns.cuh and their entries: the division of a matrix of polynomial columns (pointwise and on
+// a coset, code/ntt.py:159-176 for every column at once), the nonlinear combination of code/fast_stark.py:130-145 in one pass, and ONE
+// deferred verdict for all columns of a call (the scheme of sc_coset_divide_later_dev: a one-wave kernel behind the work writes the
+// words to a pinned slot, then a sequence number).
+#include "core.h"
+#include "columns.cuh"
+
+namespace sci {
+
+static_assert(sizeof(CombineTerm) == sizeof(sc_combine_term_t), "the device term table is the ABI's term array");
+
+__global__ void __launch_bounds__(256) pointwise_div_cols_kernel(const DivCols D) {
+    div_cols_thread<DIV_COLS_K>(D, blockIdx.x, blockIdx.y, threadIdx.x, gridDim.x);
+}
+
+__global__ void __launch_bounds__(256) short_poly_coset_cols_kernel(const Fe* __restrict__ b, uint64_t ld_b, uint32_t nb, Fe off_m, const Fe* __restrict__ tl,
+                                                                   const Fe* __restrict__ th, Fe* __restrict__ out, uint64_t order) {
+    short_poly_cols_thread(b, ld_b, nb, off_m, tl, th, out, order, blockIdx.y, (uint64_t)blockIdx.x * COLS_WG + threadIdx.x);
+}
+
+// grid (position blocks) x (columns): a wave lies inside one column, so its highest non-zero coefficient above the quotient is one
+// atomic (the lanes are in index order: the highest lane that reports holds the highest index)
+__global__ void __launch_bounds__(256) unscale_cols_kernel(const UnscaleCols U) {
+    const long long r = unscale_cols_thread(U, blockIdx.y, (uint64_t)blockIdx.x * COLS_WG + threadIdx.x);
+    const unsigned long long lanes = __ballot(r >= 0);
+    if (lanes && (threadIdx.x & 63u) == (unsigned)(63 - __clzll((long long)lanes))) cols_word_max(U.rem + blockIdx.y, r);
+}
+
+__global__ void __launch_bounds__(256) combine_cols_kernel(const CombineTerm* __restrict__ terms, uint32_t nterms, const Fe* __restrict__ w_m, Fe* __restrict__ out,
+                                                           uint64_t n_out, uint64_t ld_out) {
+    const uint64_t i = (uint64_t)blockIdx.x * COLS_WG + threadIdx.x;
+    if (i < n_out) out[blockIdx.y * ld_out + i] = combine_cols_elem(terms, nterms, w_m, blockIdx.y, i);
+}
+
+// one wave: the per-column words -> the words of one pinned slot, published like divide_flags_publish_kernel
+__global__ void __launch_bounds__(64) columns_verdict_kernel(const uint32_t* __restrict__ zero, const long long* __restrict__ rem, uint64_t cols,
+                                                            volatile uint64_t* host, uint64_t seq) {
+    __shared__ long long firsts[64];
+    __shared__ uint64_t counts[64];
+    verdict_lane(zero, rem, cols, threadIdx.x, &firsts[threadIdx.x], &counts[threadIdx.x]);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t words[4];
+        verdict_words(zero, rem, firsts, counts, words);
+        for (int k = 0; k < 4; ++k) host[k] = words[k];
+        __threadfence_system();
+        host[8] = seq;
+    }
+}
+
+// Columns per workgroup row of the division with a shared divisor.  A thread's batch inversion costs about 190 + 3 * 15 = 235
+// products and every column of its chunk 16 more, so a chunk of c columns costs (235 + 16 c) / (16 c) products per element: 15.7 at
+// c = 1, 2.8 at c = 8, 1.9 at c = 16, 1.5 at c = 32 -- against one product per 32 bytes moved at which the kernel would be bound by
+// memory, gains flatten past 16.  Short columns need the opposite: a 2^10-point column is ONE workgroup of positions, and only the
+// chunk rows spread it over the CUs.  So: the largest chunk up to 16 that still leaves two workgroups per CU, else the largest that
+// leaves as many workgroups as the columns allow.  (Reasoned, not measured; sc_set_tuning("div_cols_chunk", c > 0) forces c.)
+static uint32_t div_cols_chunk_for(uint64_t n, uint64_t cols) {
+    if (g.div_cols_chunk > 0) return (uint32_t)g.div_cols_chunk;
+    const uint64_t gx = div_cols_grid_x(n), want = 2ull * (uint64_t)g.num_cus;
+    uint32_t chunk = 16;
+    while (chunk > 1 && gx * ((cols + chunk - 1) / chunk) < want) chunk >>= 1;
+    return chunk;
+}
+
+static int div_cols_enqueue(const Fe* a, uint64_t ld_a, const Fe* b, uint64_t ld_b, Fe* out, uint64_t ld_out, uint64_t n, uint64_t cols, uint32_t* zero, hipStream_t st) {
+    uint64_t chunk = ld_b == 0 ? div_cols_chunk_for(n, cols) : 1;
+    if (chunk > cols) chunk = cols;
+    while ((cols + chunk - 1) / chunk > 65535) chunk *= 2;               // (grid.y)
+    const DivCols D{a, ld_a, b, ld_b, out, ld_out, n, cols, (uint32_t)chunk, zero};
+    hipLaunchKernelGGL(pointwise_div_cols_kernel, dim3(div_cols_grid_x(n), (unsigned)((cols + chunk - 1) / chunk)), dim3(COLS_WG), 0, st, D);
+    HIPCHK(hipGetLastError());
+    return SC_OK;
+}
+
+// the per-column device words of one call: cols remainder words (preset to -1), then cols zero-divisor words (preset to 0); they go
+// back to the pool behind the streams in use once the call has enqueued its publish kernel
+struct ColumnWords {
+    PoolTmpAsync mem;
+    long long* rem = nullptr;
+    uint32_t* zero = nullptr;
+    int get(uint64_t cols) {
+        SCCHK(mem.get(cols * (sizeof(long long) + sizeof(uint32_t))));
+        rem = (long long*)mem.p;
+        zero = (uint32_t*)(rem + cols);
+        return SC_OK;
+    }
+    int preset(uint64_t cols, hipStream_t st) {
+        HIPCHK(hipMemsetAsync(rem, 0xFF, cols * sizeof(long long), st));
+        HIPCHK(hipMemsetAsync(zero, 0, cols * sizeof(uint32_t), st));
+        return SC_OK;
+    }
+};
+static int columns_verdict_later(int slot, const ColumnWords& w, bool with_rem, uint64_t cols, hipStream_t st, sc_later** out) {
+    const uint64_t seq = ++g.root_seq;
+    volatile uint64_t* host = (volatile uint64_t*)(g.root_slots + ROOT_SLOT_BYTES * slot);
+    hipLaunchKernelGGL(columns_verdict_kernel, dim3(1), dim3(64), 0, st, (const uint32_t*)w.zero, with_rem ? (const long long*)w.rem : nullptr, cols, host, seq);
+    HIPCHK(hipGetLastError());
+    *out = new sc_later{slot, seq, st};
+    return SC_OK;
+}
+// a deferred entry that failed after reserving its slot: nothing enqueued may still write the slot when it is reused
+static int columns_abandon(int slot, hipStream_t st, int rc) {
+    (void)hipStreamSynchronize(st);
+    g.free_root_slots.push_back(slot);
+    return rc;
+}
+// host words -> device memory of the call's own: as kernel arguments when few (nothing to wait for), else by a copy that is waited for
+static int upload_words(void* d_dst, const void* host, size_t bytes, hipStream_t st) {
+    if (upload_small(d_dst, host, bytes, st)) return SC_OK;
+    (void)hipGetLastError();
+    SCCHK(upload(d_dst, host, bytes, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return SC_OK;
+}
+
+}  // namespace sci
+
+int sc_pointwise_div_columns_later_dev(const void* d_a, uint64_t ld_a, const void* d_b, uint64_t ld_b, void* d_out, uint64_t ld_out, uint64_t n, uint64_t cols,
+                                       sc_later_t** later, void* stream) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    if (!later || !d_a || !d_b || !d_out || !n || !cols) return fail(SC_ERR_BAD_ARG, "null argument");
+    if (ld_a < n || ld_out < n || (ld_b != 0 && ld_b < n)) return fail(SC_ERR_BAD_ARG, "a column stride below the column length");
+    if (d_out == d_a && ld_out != ld_a && cols > 1) return fail(SC_ERR_BAD_ARG, "in place needs the numerator's column stride");
+    hipStream_t st = pick_stream(stream);
+    const int slot = root_slot_get();
+    if (slot < 0) return fail(SC_ERR_UNSUPPORTED, "no pinned slot free for a deferred check (nothing enqueued)");
+    ColumnWords w;
+    if (int rc = w.get(cols)) { g.free_root_slots.push_back(slot); return rc; }      // (nothing enqueued yet)
+    const int rc = [&]() -> int {
+        SCCHK(w.preset(cols, st));
+        SCCHK(div_cols_enqueue((const Fe*)d_a, ld_a, (const Fe*)d_b, ld_b, (Fe*)d_out, ld_out, n, cols, w.zero, st));
+        return columns_verdict_later(slot, w, false, cols, st, later);
+    }();
+    return rc == SC_OK ? SC_OK : columns_abandon(slot, st, rc);
+}
+
+int sc_coset_divide_columns_later_dev(const void* d_a, uint64_t na, uint64_t ld_a, const void* d_b, uint64_t nb, uint64_t ld_b, uint64_t cols,
+                                      const uint64_t offset[2], const uint64_t root[2], uint64_t order, void* d_out, const uint64_t* n_out, uint64_t ld_out,
+                                      sc_later_t** later, void* stream) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    if (!later || !d_a || !d_b || !n_out || !cols || !offset || !root) return fail(SC_ERR_BAD_ARG, "null argument");
+    if (!is_pow2(order) || order < 2) return fail(SC_ERR_NOT_POW2, "cannot compute ntt of non-power-of-two sequence");
+    if (na > order || nb > order || na == 0 || nb == 0) return fail(SC_ERR_BAD_ARG, "operand longer than the transform order");
+    if (ld_a < na || (ld_b != 0 && ld_b < nb)) return fail(SC_ERR_BAD_ARG, "a column stride below the column length");
+    uint64_t longest = 0;
+    for (uint64_t c = 0; c < cols; ++c) {
+        if (n_out[c] > order) return fail(SC_ERR_BAD_ARG, "operand longer than the transform order");
+        longest = n_out[c] > longest ? n_out[c] : longest;
+    }
+    if (ld_out < longest || (longest && !d_out)) return fail(SC_ERR_BAD_ARG, "a column stride below the column length");
+    const Fe rt = fe_from(root), off = fe_from(offset);
+    SCCHK(check_root(rt, order));
+    if (fe_is_zero(off) || fe_ge_p(off)) return fail(SC_ERR_BAD_ARG, "bad coset offset");
+    hipStream_t st = pick_stream(stream);
+    const int slot = root_slot_get();
+    if (slot < 0) return fail(SC_ERR_UNSUPPORTED, "no pinned slot free for a deferred check (nothing enqueued)");
+    // one set of launches takes COLS_ELEMS_PER_LAUNCH values (and grid.y 65 535 columns): more columns go in chunks that report into
+    // the same per-column words.  The value matrices are this call's own.  (sc_set_tuning("div_cols_launch_log") lowers the limit so
+    // that a test reaches the chunk loop with small matrices.)
+    static_assert(COLS_ELEMS_PER_LAUNCH == 1ull << 26, "div_cols_launch_log's default and upper end");
+    const bool shared = ld_b == 0;
+    uint64_t per = (1ull << g.div_cols_launch_log) / order;
+    if (per < 1) per = 1;
+    if (per > 65535) per = 65535;
+    if (per > cols) per = cols;
+    ColumnWords w;
+    PoolTmpAsync va, vb, vd, keep;
+    const int got = [&]() -> int {
+        SCCHK(w.get(cols));
+        SCCHK(va.get(per * order * sizeof(Fe)));
+        SCCHK(vb.get(per * order * sizeof(Fe)));
+        SCCHK(vd.get((shared ? 1 : per) * order * sizeof(Fe)));
+        return keep.get(cols * sizeof(uint64_t));
+    }();
+    if (got != SC_OK) { g.free_root_slots.push_back(slot); return got; }           // (nothing enqueued yet)
+    const int rc = [&]() -> int {
+        const int logn = ilog2(order);
+        SCCHK(w.preset(cols, st));
+        SCCHK(upload_words(keep.p, n_out, cols * sizeof(uint64_t), st));
+        PowTables *pw, *pinv;
+        SCCHK(get_pow(off, order, st, &pw));
+        SCCHK(get_pow(from_mont(mont_inv(to_mont(off))), order, st, &pinv));       // unscale by offset^-1 (ntt.py:176)
+        const bool direct = nb <= SMALL_DIVISOR && g.small_divisor_direct;
+        PlanTables* pt = nullptr;
+        if (direct) SCCHK(get_plan(rt, logn, false, st, &pt));
+        const unsigned xblocks = (unsigned)((order + COLS_WG - 1) / COLS_WG);
+        // the divisors' values on the coset: `k` rows from `b` (a shared divisor: one row, once)
+        auto divisor_values = [&](const Fe* b, uint64_t k) -> int {
+            if (direct) {
+                hipLaunchKernelGGL(short_poly_coset_cols_kernel, dim3(xblocks, (unsigned)k), dim3(COLS_WG), 0, st, b, ld_b, (uint32_t)nb, to_mont(off), (const Fe*)pt->tl,
+                                   (const Fe*)pt->th, vd.fe(), order);
+                HIPCHK(hipGetLastError());
+                return SC_OK;
+            }
+            NttOpts o;
+            o.coset = pw;
+            o.in_limit = nb;
+            o.cols = (uint32_t)k;
+            o.col_stride_in = ld_b;
+            return ntt_device(b, vd.fe(), logn, rt, false, o, st);
+        };
+        if (shared) SCCHK(divisor_values((const Fe*)d_b, 1));
+        for (uint64_t done = 0; done < cols; done += per) {
+            const uint64_t k = cols - done < per ? cols - done : per;
+            NttOpts o;
+            o.coset = pw;
+            o.in_limit = na;
+            o.cols = (uint32_t)k;
+            o.col_stride_in = ld_a;
+            SCCHK(ntt_device((const Fe*)d_a + done * ld_a, va.fe(), logn, rt, false, o, st));
+            if (!shared) SCCHK(divisor_values((const Fe*)d_b + done * ld_b, k));
+            SCCHK(div_cols_enqueue(va.fe(), order, vd.fe(), shared ? 0 : order, va.fe(), order, order, k, w.zero + done, st));
+            NttOpts back;
+            back.cols = (uint32_t)k;
+            SCCHK(ntt_device(va.fe(), vb.fe(), logn, root_inverse(rt, order), true, back, st));
+            const UnscaleCols U{vb.fe(), order, (Fe*)d_out + done * ld_out, ld_out, (const uint64_t*)keep.p + done, pinv->lo, pinv->hi, w.rem + done};
+            hipLaunchKernelGGL(unscale_cols_kernel, dim3(xblocks, (unsigned)k), dim3(COLS_WG), 0, st, U);
+            HIPCHK(hipGetLastError());
+        }
+        return columns_verdict_later(slot, w, true, cols, st, later);
+    }();
+    return rc == SC_OK ? SC_OK : columns_abandon(slot, st, rc);
+}
+
+int sc_combine_columns_dev(const sc_combine_term_t* terms, uint64_t nterms, const void* weights, uint64_t cols, void* d_out, uint64_t n_out, uint64_t ld_out, void* stream) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    if (cols == 0 || n_out == 0) return SC_OK;
+    if (!terms || !weights || !d_out || nterms == 0 || nterms > 0xFFFFFFFFull) return fail(SC_ERR_BAD_ARG, nterms ? "null argument" : "a combination of no terms");
+    if (ld_out < n_out || cols > 65535) return fail(SC_ERR_BAD_ARG, cols > 65535 ? "more than 65 535 columns" : "a column stride below the column length");
+    hipStream_t st = pick_stream(stream);
+    const uintptr_t out_lo = (uintptr_t)d_out, out_hi = out_lo + ((cols - 1) * ld_out + n_out) * sizeof(Fe);
+    // the table as the kernel reads it: the terms, then the weights in Montgomery form
+    const size_t tbytes = nterms * sizeof(CombineTerm), wbytes = cols * nterms * sizeof(Fe);
+    std::vector<uint8_t> table(tbytes + wbytes);
+    CombineTerm* T = (CombineTerm*)table.data();
+    Fe* W = (Fe*)(table.data() + tbytes);
+    for (uint64_t t = 0; t < nterms; ++t) {
+        const sc_combine_term_t& s = terms[t];
+        if (s.shift + s.n > n_out || s.shift + s.n < s.shift) return fail(SC_ERR_BAD_ARG, "shifted term does not fit the output");
+        if (s.n) {
+            if (!s.d_src || s.ld < s.n) return fail(SC_ERR_BAD_ARG, s.d_src ? "a column stride below the column length" : "null argument");
+            const uintptr_t lo = (uintptr_t)s.d_src, hi = lo + ((cols - 1) * s.ld + s.n) * sizeof(Fe);
+            if (lo < out_hi && out_lo < hi) return fail(SC_ERR_BAD_ARG, "the output may not alias a source");
+        }
+        T[t] = CombineTerm{(const Fe*)s.d_src, s.ld, s.n, s.shift};
+    }
+    const Fe* w = (const Fe*)weights;
+    for (uint64_t k = 0; k < cols * nterms; ++k) {
+        if (fe_ge_p(w[k])) return fail(SC_ERR_BAD_ARG, "weight is not a canonical residue");
+        W[k] = to_mont(w[k]);
+    }
+    PoolTmpAsync d_table;
+    SCCHK(d_table.get(table.size() + 8));
+    SCCHK(upload_words(d_table.p, table.data(), table.size(), st));
+    hipLaunchKernelGGL(combine_cols_kernel, dim3((unsigned)((n_out + COLS_WG - 1) / COLS_WG), (unsigned)cols), dim3(COLS_WG), 0, st,
+                       (const CombineTerm*)d_table.p, (uint32_t)nterms, (const Fe*)((const uint8_t*)d_table.p + tbytes), (Fe*)d_out, n_out, ld_out);
+    HIPCHK(hipGetLastError());
+    return SC_OK;
+}

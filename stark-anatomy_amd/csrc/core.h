@@ -7,6 +7,7 @@
 //   polytree_geo.hip  subproduct trees and geometric progressions (fast_zerofier / fast_evaluate / fast_interpolate)
 //   fourstep.hip      batched transforms, the sharded four-step plan, the RCCL communicator, the direct-store corner turn
 //   rescue.hip        the Rescue-Prime permutation (hash and trace) over many inputs
+//   columns.hip       division, combination and one deferred verdict over a matrix of polynomial columns (csrc/columns.cuh)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -126,6 +127,8 @@ struct Ctx {
     uint64_t tick = 0;       // bumped by every table lookup
     bool foreign_streams = false;   // a caller-owned stream has been used (see pick_stream)
     int small_divisor_direct = 1;    // coset_divide_core evaluates a divisor of <= 8 coefficients point by point instead of transforming it (sc_set_tuning("small_divisor_direct", 0): A/B and tests)
+    int div_cols_launch_log = 26;    // sc_coset_divide_columns_later_dev: log2 of the values one set of launches takes (COLS_ELEMS_PER_LAUNCH); smaller: a test hook for the chunk loop
+    int div_cols_chunk = 0;          // columns that share one batch inversion in pointwise_div_cols_kernel; 0: chosen by shape (columns.hip div_cols_chunk_for)
     std::vector<hipStream_t> seen_streams;   // those streams, most recent last (at most SEEN_STREAMS; more: device-wide waits)
     DevBuf scratch[8];       // 0: ntt work, 1..3: poly temporaries, 4: misc small, 5: merkle staging, 6: uploaded operands, 7: degree / exactness flag
     std::map<hipStream_t, DevBuf> ntt_work;   // the work buffer of a multi-pass transform, one per stream: transforms on DIFFERENT streams may be in flight together
@@ -181,6 +184,8 @@ struct NttOpts {
 };
 // elements one set of column launches covers at most (sc_ntt_columns_dev, sc_coset_evaluate_columns_dev, sc_geodomain_interpolate_columns_dev)
 constexpr uint64_t COLS_ELEMS_PER_LAUNCH = 1ull << 26;
+// a divisor of at most this many coefficients is evaluated point by point on the coset instead of being transformed (small_divisor_direct)
+constexpr uint64_t SMALL_DIVISOR = 8;
 
 // Climb from level `lvl` (already in the tree, `N >> lvl` nodes) to the root.  Levels wider than FUSE_MAX_W nodes are
 // throughput-bound: launches that fuse merkle_big_nlev (2) levels -- a workgroup's 256 -> 128 -> 64 nodes keep every active
@@ -235,6 +240,7 @@ int pointwise_div_device(const Fe* a, const Fe* b, Fe* out, uint64_t n, hipStrea
 int pointwise_div_enqueue(const Fe* a, const Fe* b, Fe* out, uint64_t n, hipStream_t st, uint32_t* flag);
 int gather_device(const Fe* v, const uint64_t* d_idx, uint64_t k, Fe* d_out, hipStream_t st);
 int read_small_polled(const void* d_src, size_t bytes, hipStream_t st, void* host_out);
+bool upload_small(void* d_dst, const void* host, size_t bytes, hipStream_t st);
 
 // ---- merkle_fri.hip
 int merkle_climb(uint64_t* levels, uint64_t N, int lvl, hipStream_t st, volatile uint64_t* host = nullptr, uint64_t seq = 0, bool* published = nullptr);

@@ -175,7 +175,6 @@ __global__ void __launch_bounds__(256) pointwise_div_kernel(const Fe* __restrict
 // out[i] = b(offset * root^i) for a SHORT polynomial b (nb <= SMALL_DIVISOR coefficients, canonical): what ntt(scale(b)) computes with
 // three passes over `order` elements, by Horner at every point -- the two- and three-coefficient boundary zerofiers of
 // fast_stark.py:93-98 are divided by on a 2^21-point coset twice per proof.  Same values (exact arithmetic), same place in the flow.
-constexpr uint64_t SMALL_DIVISOR = 8;
 __global__ void __launch_bounds__(256) short_poly_coset_kernel(const Fe* __restrict__ b, uint32_t nb, Fe off_m, const Fe* __restrict__ tl, const Fe* __restrict__ th, Fe* __restrict__ out, uint64_t order) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= order) return;
@@ -1036,6 +1035,8 @@ int sc_set_tuning(const char* key, int value) {
     else if (k == "forest_four_lane_wgs") g.forest_four_lane_wgs = value < 0 ? 0 : value;
     else if (k == "fri_tail") g.fri_tail = value ? 1 : 0;
     else if (k == "small_divisor_direct") g.small_divisor_direct = value ? 1 : 0;
+    else if (k == "div_cols_chunk") g.div_cols_chunk = value < 0 ? 0 : (value > 65535 ? 65535 : value);      // columns per workgroup row of pointwise_div_cols_kernel, 0 = by shape (csrc/columns.hip)
+    else if (k == "div_cols_launch_log") g.div_cols_launch_log = value < 1 ? 1 : (value > 26 ? 26 : value);        // tests only: more chunks per call, never larger ones (csrc/columns.hip)
     else if (k == "verify_stage_kb") g.verify_stage_bytes = (size_t)(value < 16 ? 16 : value) << 10;           // (a chunk must hold one row of any depth)
     else if (k == "fri_tail_stall") g.fri_tail_stall = value;                               // tests only: see core.h
     else if (k == "pool_cap_mb") g_pool_cap = (size_t)(value < 0 ? 0 : value) << 20;       // what the free lists may keep from now on
@@ -1093,6 +1094,8 @@ int sc_vec_zero(sc_vec_t* v) {
     if (v->n) HIPCHK(hipMemsetAsync(v->d, 0, v->n * sizeof(Fe), g.stream));
     return SC_OK;
 }
+}  // extern "C"
+namespace sci {
 // a few hundred bytes travel as a KERNEL ARGUMENT: the launch copies them, nothing is staged, nothing is waited for -- a pageable
 // hipMemcpyAsync has to be followed by a wait for the stream (the host buffer is the caller's), and in the middle of a proof that
 // wait is for everything the GPU still has queued (boundary zerofiers of three coefficients, 160 randomizer rows: 40 us each)
@@ -1101,7 +1104,7 @@ __global__ void __launch_bounds__(256) small_upload_kernel(uint64_t* __restrict_
     if (threadIdx.x < nwords) dst[threadIdx.x] = p.w[threadIdx.x];
 }
 // `bytes` (any number, at most 4 payloads) from host memory to 8-byte aligned device memory with room for the last word, as kernel arguments
-static bool upload_small(void* d_dst, const void* host, size_t bytes, hipStream_t st) {
+bool upload_small(void* d_dst, const void* host, size_t bytes, hipStream_t st) {
     if (bytes > 4 * sizeof(SmallPayload)) return false;
     const uint8_t* src = (const uint8_t*)host;
     uint64_t* dst = (uint64_t*)d_dst;
@@ -1115,6 +1118,8 @@ static bool upload_small(void* d_dst, const void* host, size_t bytes, hipStream_
     }
     return hipGetLastError() == hipSuccess;
 }
+}  // namespace sci
+extern "C" {
 int sc_vec_upload(sc_vec_t* v, uint64_t offset, const void* host, uint64_t count) {
     std::lock_guard<std::mutex> lk(g_mu);
     SCCHK(ensure_init());

@@ -212,6 +212,15 @@ class FastStark:
     # codewords, same pushes and draws in the same order: the proofs are byte-identical (tests/test_gpu_wide_stark.py).  Narrower
     # traces run the per-register code.  (Measured: tools/wide_trace_timing.py, profiles/column_batches/.)
     COLUMN_BATCH_MIN = 4
+    # Two further steps of the column-batched path, each with its per-register form kept for comparison (tools/wide_trace_timing.py).
+    # COLUMN_DIVIDE: the boundary quotients of all registers are one combination (trace_s - interpolant_s for every s) and one
+    # columns-form coset division with ONE pending verdict, instead of a dozen launches and a pinned slot per register.
+    # COLUMN_COMBINE: the nonlinear combination is one pass (sc_combine_columns_dev) instead of one axpy launch per term.
+    # Same polynomials, same pushes and draws, same assertion messages: the proofs are byte-identical (tests/test_gpu_wide_stark_columns.py).
+    # Both are on: with both, the 16-register proof's median is below the median with neither at FRI 2^16 and 2^20 (DESIGN.md 3.8b,
+    # profiles/column_batches/).  False is the code as it was before them.
+    COLUMN_DIVIDE = True
+    COLUMN_COMBINE = True
 
     def _lde(self, polynomial):
         """Low-degree extension onto the FRI coset  generator * omega^i  (the LDE kernel)."""
@@ -320,9 +329,11 @@ class FastStark:
             else:
                 trace_polynomials = [DevicePolynomial.from_codeword(fast_interpolate_device(trace_domain, column)) for column in columns]
             self._mark("trace interpolation")
-            zerofiers_dev = [DevicePolynomial.from_polynomial(z, field) for z in zerofiers]
-            boundary_quotients = [coset_divide_device(trace_polynomials[s].minus(interpolants[s]), zerofiers_dev[s], self.generator, self.omicron,
-                                                      self.omicron_domain_length, exact=True, later=pending) for s in registers]
+            boundary_quotients = self._boundary_quotients_columns(trace_polynomials, interpolants, zerofiers, pending) if batched and FastStark.COLUMN_DIVIDE else None
+            if boundary_quotients is None:
+                zerofiers_dev = [DevicePolynomial.from_polynomial(z, field) for z in zerofiers]
+                boundary_quotients = [coset_divide_device(trace_polynomials[s].minus(interpolants[s]), zerofiers_dev[s], self.generator, self.omicron,
+                                                          self.omicron_domain_length, exact=True, later=pending) for s in registers]
             lde = lambda poly: poly.coset_evaluate(self.generator, self.omega, self.fri_domain_length)
         else:
             # trace polynomials through {omicron^i}
@@ -391,7 +402,7 @@ class FastStark:
         for i in registers:
             shifted.append((boundary_quotients[i], max_degree - bq_bounds[i]))
         if on_device:
-            combined_codeword = self._combine_on_device(shifted, weights, max_degree)
+            combined_codeword = self._combine_on_device(shifted, weights, max_degree, batched and FastStark.COLUMN_COMBINE)
             self._mark("weights, degree checks, nonlinear combination + its LDE")
         else:
             terms = []
@@ -601,13 +612,35 @@ class FastStark:
             columns.append(DeviceCodeword(column, self.field))
         return columns
 
-    def _combine_on_device(self, shifted, weights, max_degree):
+    def _boundary_quotients_columns(self, trace_polynomials, interpolants, zerofiers, pending):
+        """(trace_s - interpolant_s) / zerofier_s for every register s in two library calls: the differences as one combination with
+        weights 1 and p - 1 (the interpolants uploaded as one zero-padded matrix), then one columns-form coset division with a
+        zerofier and a quotient length per register and ONE pending verdict.  None where the shape is not the batched call's -- an
+        interpolant not of lower degree than its trace polynomial, trace polynomials of different degrees -- and the caller's
+        per-register loop runs instead."""
+        field = self.field
+        degree = trace_polynomials[0].degree()
+        short = [p.degree() for p in interpolants]
+        if degree < 0 or any(t.degree() != degree for t in trace_polynomials) or max(short) >= degree:
+            return None
+        width = max(len(t) for t in trace_polynomials)
+        subtrahends = DevicePolynomial.rows_from_polynomials(interpolants, field)
+        numerators = combine_columns_device([(trace_polynomials, None), (subtrahends, None)], [[1, field.p - 1]] * len(interpolants), width)
+        for numerator in numerators:
+            numerator._degree = degree                     # a subtrahend of lower degree leaves the degree alone (DevicePolynomial.minus)
+        divisors = DevicePolynomial.rows_from_polynomials(zerofiers, field)       # one matrix, one upload: the division reads it in place
+        return coset_divide_columns_device(numerators, divisors, self.generator, self.omicron, self.omicron_domain_length, later=pending)
+
+    def _combine_on_device(self, shifted, weights, max_degree, one_pass=False):
         """sum_i weights[i] * terms[i] (fast_stark.py:130-145) as axpys over coefficient vectors in HBM, then the LDE straight from
         the accumulator: `Polynomial([w]) * t` scales t, `(x ^ k) * t` shifts it by k places.  The combination never visits the host."""
-        return self._combination_on_device(shifted, weights, max_degree).coset_evaluate(self.generator, self.omega, self.fri_domain_length)
+        return self._combination_on_device(shifted, weights, max_degree, one_pass).coset_evaluate(self.generator, self.omega, self.fri_domain_length)
 
-    def _combination_on_device(self, shifted, weights, max_degree):
+    def _combination_on_device(self, shifted, weights, max_degree, one_pass=False):
         width = max(max_degree + 1, max(len(p) + (k or 0) for p, k in shifted))
+        if one_pass:
+            # every term in one launch that writes each coefficient once (COLUMN_COMBINE): no zeroed accumulator, no launch per term
+            return combine_columns_device([([poly], shift) for poly, shift in shifted], [weights], width)[0]
         acc = DeviceVector.zeros(width)
         w = iter(weights)
         for poly, shift in shifted:

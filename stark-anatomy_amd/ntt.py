@@ -290,6 +290,21 @@ class DevicePolynomial:
         return out
 
     @classmethod
+    def rows_from_polynomials(cls, polynomials, field):
+        """host Polynomials -> DevicePolynomials that are the rows of ONE zero-padded matrix (one upload): every row holds as many
+        coefficients as the longest polynomial has up to its degree (at least one), and knows its degree"""
+        _require_main_field(field)
+        degrees = [p.degree() for p in polynomials]
+        m = max(max(degrees) + 1, 1)
+        matrix = DeviceVector.from_bytes(b"".join(_pack(p.coefficients[:d + 1]) + bytes(16 * (m - d - 1)) for p, d in zip(polynomials, degrees)))
+        rows = []
+        for c, d in enumerate(degrees):
+            row = cls(DeviceVector.wrap(matrix.ptr + 16 * m * c, m, matrix), field, m)
+            row._degree = d
+            rows.append(row)
+        return rows
+
+    @classmethod
     def from_codeword(cls, codeword):
         return cls(codeword.vec, codeword.field)
 
@@ -444,6 +459,156 @@ def coset_divide_device(lhs, rhs, offset, primitive_root, root_order, exact=Fals
         assert(flag.value == 1), "cannot perform polynomial division because remainder is not zero"
         quotient._degree = dl - dr                         # an exact quotient's leading coefficient is lhs's over rhs's: not zero
     return quotient
+
+
+def _pitch_of(vectors, n):
+    """element pitch of DeviceVectors that are equally spaced rows (of at least n elements) of one matrix, else None; one vector: n"""
+    places = [v.ptr for v in vectors]
+    if len(places) == 1:
+        return n
+    pitch = places[1] - places[0]
+    if pitch >= 16 * n and pitch % 16 == 0 and all(b - a == pitch for a, b in zip(places, places[1:])):
+        return pitch // 16
+    return None
+
+
+def _as_matrix(polynomials, n):
+    """(holder of the device pointer, pitch) of a matrix whose row c holds the first n coefficients of polynomials[c] (zero beyond its
+    length): the polynomials' own memory when they are equally spaced rows of one matrix already and all hold n coefficients,
+    else a zero-padded copy, as fast_interpolate_columns_device copies its columns"""
+    if all(len(p) >= n for p in polynomials):
+        pitch = _pitch_of([p.vec for p in polynomials], n)
+        if pitch is not None:
+            return polynomials[0].vec, pitch
+    full = all(len(p) >= n for p in polynomials)
+    matrix = DeviceVector(len(polynomials) * n) if full else DeviceVector.zeros(len(polynomials) * n)
+    for c, p in enumerate(polynomials):
+        if min(len(p), n):
+            _sc._check(_sc.lib().sc_memcpy_dev(matrix.ptr + 16 * n * c, p.vec.ptr, min(len(p), n), None))
+    return matrix, n
+
+
+def _columns_verdict(handle):
+    """the check of a columns-form division (sc_*_columns_later_dev): raises what the first failing check of the per-column loop raises"""
+    check = _sc.Later(handle)
+
+    def verdict():
+        zero_divisor, remainder = check.wait()             # the words of the lowest failing column
+        assert(not zero_divisor), "divide by zero"
+        assert(not remainder), "cannot perform polynomial division because remainder is not zero"
+    return verdict
+
+
+def coset_divide_columns_device(lhs_list, rhs, offset, primitive_root, root_order, later=None):
+    """[coset_divide_device(l, r_c, offset, primitive_root, root_order, exact=True, later=later) for l in lhs_list], r_c = rhs (one
+    DevicePolynomial for every column) or rhs[c], as ONE library call (sc_coset_divide_columns_later_dev) with ONE verdict: appended to
+    `later`, or waited for on the spot with later=None; it raises "divide by zero" or the non-zero remainder, whichever the lowest
+    failing column met.  The quotients are views of one matrix.  The batched call serves numerators of one known degree, at least every
+    divisor's, in the main field -- equally spaced rows of one matrix, or copied into one; anything else, and a library without a
+    free slot for the verdict, goes column by column."""
+    lhs_list = list(lhs_list)
+    shared = isinstance(rhs, DevicePolynomial)
+    divisors = [rhs] * len(lhs_list) if shared else list(rhs)
+    assert(len(divisors) == len(lhs_list)), "one divisor, or one per column"
+    one_by_one = lambda: [coset_divide_device(l, r, offset, primitive_root, root_order, exact=True, later=later) for l, r in zip(lhs_list, divisors)]
+    if not lhs_list:
+        return []
+    _check_root(primitive_root, root_order)
+    field = lhs_list[0].field
+    dl = lhs_list[0]._degree
+    if field.p != Field.P_MAIN or dl is None or dl < 0 or any(l._degree != dl for l in lhs_list):
+        return one_by_one()
+    drs = [r.degree() for r in ([rhs] if shared else divisors)]
+    if min(drs) < 0 or max(drs) > dl:
+        return one_by_one()                                # (raises what the reference raises)
+    cols, na, nb = len(lhs_list), dl + 1, max(drs) + 1
+    root, order = _shrink_order(primitive_root, root_order, dl)
+    numerators, ld_a = _as_matrix(lhs_list, na)
+    divisor_rows, ld_b = (rhs.vec, 0) if shared else _as_matrix(divisors, nb)
+    n_out = [dl - dr + 1 for dr in (drs * cols if shared else drs)]
+    ld_out = max(n_out)
+    out = DeviceVector(cols * ld_out)
+    handle = ctypes.c_void_p()
+    rc = _sc.lib().sc_coset_divide_columns_later_dev(numerators.ptr, na, ld_a, divisor_rows.ptr, nb, ld_b, cols, _sc.fe_bytes(offset.value), _sc.fe_bytes(root.value),
+                                                     order, out.ptr, (ctypes.c_uint64 * cols)(*n_out), ld_out, ctypes.byref(handle), None)
+    if rc == _sc.SC_ERR_UNSUPPORTED:
+        return one_by_one()
+    _sc._check(rc)
+    verdict = _columns_verdict(handle)
+    if later is not None:
+        later.append(verdict)
+    else:
+        verdict()
+    quotients = []
+    for c in range(cols):
+        quotient = DevicePolynomial(DeviceVector.wrap(out.ptr + 16 * ld_out * c, n_out[c], out), field, n_out[c])
+        quotient._degree = n_out[c] - 1                    # what an exact division leaves, which the verdict confirms
+        quotients.append(quotient)
+    return quotients
+
+
+def fast_coset_divide_columns(lhs_list, rhs, offset, primitive_root, root_order):
+    """[fast_coset_divide(l, r_c, offset, primitive_root, root_order) for l in lhs_list] on host Polynomials, r_c = rhs (one Polynomial)
+    or rhs[c]: one upload, one columns-form division, one download.  Degenerate shapes (a zero numerator, degree < 8, numerators of
+    different degrees) go column by column through fast_coset_divide."""
+    lhs_list = list(lhs_list)
+    shared = isinstance(rhs, Polynomial)
+    divisors = [rhs] * len(lhs_list) if shared else list(rhs)
+    assert(len(divisors) == len(lhs_list)), "one divisor, or one per column"
+    one_by_one = lambda: [fast_coset_divide(l, r, offset, primitive_root, root_order) for l, r in zip(lhs_list, divisors)]
+    if not lhs_list:
+        return []
+    _check_root(primitive_root, root_order)
+    dls, drs = [l.degree() for l in lhs_list], [r.degree() for r in divisors]
+    dl = dls[0]
+    if dl < 8 or any(d != dl for d in dls) or min(drs) < 0 or max(drs) > dl or offset.field.p != Field.P_MAIN:
+        return one_by_one()
+    field = offset.field
+    cols, na, nb = len(lhs_list), dl + 1, max(drs) + 1
+    root, order = _shrink_order(primitive_root, root_order, dl)
+    numerators = DeviceVector.from_bytes(b"".join(_pack(l.coefficients[:na]) for l in lhs_list))
+    rows = [rhs] if shared else divisors
+    divisor_rows = DeviceVector.from_bytes(b"".join(_pack(r.coefficients[:dr + 1]) + bytes(16 * (nb - dr - 1)) for r, dr in zip(rows, drs)))
+    n_out = [dl - dr + 1 for dr in drs]
+    ld_out = max(n_out)
+    out = DeviceVector(cols * ld_out)
+    handle = ctypes.c_void_p()
+    rc = _sc.lib().sc_coset_divide_columns_later_dev(numerators.ptr, na, na, divisor_rows.ptr, nb, 0 if shared else nb, cols, _sc.fe_bytes(offset.value),
+                                                     _sc.fe_bytes(root.value), order, out.ptr, (ctypes.c_uint64 * cols)(*n_out), ld_out, ctypes.byref(handle), None)
+    if rc == _sc.SC_ERR_UNSUPPORTED:
+        return one_by_one()
+    _sc._check(rc)
+    zero_divisor, _ = _sc.Later(handle).wait()             # (fast_coset_divide does not look at the remainder either: "clean division only")
+    assert(not zero_divisor), "divide by zero"
+    flat = _unpack(out.to_bytes(), cols * ld_out, field)
+    return [Polynomial(flat[c * ld_out:c * ld_out + n_out[c]]) for c in range(cols)]
+
+
+def combine_columns_device(terms, weights, width):
+    """The nonlinear combination of code/fast_stark.py:130-145 for every column at once, in ONE pass (sc_combine_columns_dev).
+    terms: [([DevicePolynomial per column], shift)]; shift None: the polynomials as they are (one weight), an int: as they are and
+    shifted up by `shift` places (two weights, in that order).  weights: one list per column (FieldElements or ints), in the terms'
+    order.  -> one DevicePolynomial of `width` coefficients per column, rows of one matrix: column c is what
+    FastStark._combination_on_device builds from column c's terms and weights."""
+    cols = len(weights)
+    field = terms[0][0][0].field
+    table, keep = [], []
+    for polynomials, shift in terms:
+        assert(len(polynomials) == cols), "one polynomial per column in every term"
+        n = max(len(p) for p in polynomials)
+        source, ld = _as_matrix(polynomials, n) if n else (None, 0)
+        keep.append(source)
+        for k in ([0] if shift is None else [0, shift]):
+            assert(n + k <= width), "a shifted term does not fit the output"
+            table.append(_sc.CombineTerm(source.ptr if n else None, ld, n, k))
+    for row in weights:
+        assert(len(row) == len(table)), "one weight per term (two for a shifted one)"
+    out = DeviceVector(cols * width if cols * width else 1)
+    packed = _sc.pack([getattr(w, "value", w) for row in weights for w in row])
+    _sc._check(_sc.lib().sc_combine_columns_dev((_sc.CombineTerm * len(table))(*table), len(table), packed, cols, out.ptr, width, width, None))
+    if cols == 1:
+        return [DevicePolynomial(out, field, width)]
+    return [DevicePolynomial(DeviceVector.wrap(out.ptr + 16 * width * c, width, out), field, width) for c in range(cols)]
 
 
 def fast_zerofier_device(domain):

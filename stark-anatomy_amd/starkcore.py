@@ -93,6 +93,9 @@ SIGNATURES = {
     "sc_coset_divide_later_dev": (_int, [_vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _u64, ctypes.POINTER(_vp), _vp]),
     "sc_pointwise_div_later_dev": (_int, [_vp, _vp, _vp, _u64, ctypes.POINTER(_vp), _vp]),
     "sc_later_wait": (_int, [_vp, ctypes.POINTER(ctypes.c_int64)]),
+    "sc_pointwise_div_columns_later_dev": (_int, [_vp, _u64, _vp, _u64, _vp, _u64, _u64, _u64, ctypes.POINTER(_vp), _vp]),
+    "sc_coset_divide_columns_later_dev": (_int, [_vp, _u64, _u64, _vp, _u64, _u64, _u64, _vp, _vp, _u64, _vp, ctypes.POINTER(_u64), _u64, ctypes.POINTER(_vp), _vp]),
+    "sc_combine_columns_dev": (_int, [_vp, _u64, _vp, _u64, _vp, _u64, _u64, _vp]),
     "sc_scale_dev": (_int, [_vp, _vp, _u64, _vp, _vp]),
     "sc_axpy_shift_dev": (_int, [_vp, _u64, _vp, _u64, _u64, _vp, _vp]),
     "sc_scale_slab_dev": (_int, [_vp, _vp, _u64, _u64, _u64, _u64, _vp, _vp]),
@@ -415,6 +418,11 @@ class _HostMemory:
         p, self.ptr = getattr(self, "ptr", None), None
         if p is not None and _lib is not None:
             _lib.sc_host_free(p)
+
+
+class CombineTerm(ctypes.Structure):
+    """sc_combine_term_t: one term of sc_combine_columns_dev -- column c of the source at element c * ld, n coefficients, shifted up by `shift`"""
+    _fields_ = [("d_src", ctypes.c_void_p), ("ld", ctypes.c_uint64), ("n", ctypes.c_uint64), ("shift", ctypes.c_uint64)]
 
 
 class Later:
