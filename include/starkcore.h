@@ -346,6 +346,30 @@ int sc_mpoly_eval_ex_dev(void* d_vals, uint64_t nvars, uint64_t n, const uint8_t
 int sc_mpoly_eval_rot_dev(void* d_vals, uint64_t nvars, uint64_t n, const uint8_t* exps, const void* coefs, uint64_t nterms, void* d_out, int vals_converted,
                           const uint32_t* var_src, const uint64_t* var_rot, void* stream);
 
+/* The same for `members` point sets over one n-point domain and `ncons` constraints in ONE launch (the AIR of a batch of proofs).
+ * d_vals is only READ, in canonical form, and stays usable: nothing is converted in place.  Variable j of member m lies at element
+ * var_base[j] + m * var_ld[j] of d_vals (host arrays of nvars <= 255 entries; var_ld[j] == 0: one row shared by all members, such as
+ * the values of X; the trace variables are rows of the one matrix sc_coset_evaluate_columns_dev writes).  var_src / var_rot (both or
+ * NULL) as above: a turned variable is read off a stored one of the same member, var_rot places on (n a power of two when anything
+ * is turned, any count otherwise); SC_MPOLY_ABSENT: no term may use it.  Constraint c has nterms[c] terms (host array); exps holds the
+ * constraints' [nterms[c]][nvars] exponent bytes one after the other, coefs their packed canonical coefficients likewise.
+ * d_out[(m * ncons + c) * ld_out + i] = constraint c at point i of member m, canonical, ld_out >= n; a constraint of no terms gives
+ * zeros.  Bit for bit what sc_mpoly_eval_rot_dev gives per member and constraint, from fewer products: each constraint is a Horner
+ * walk in its variable of highest exponent (csrc/mpoly_plan.h).  Enqueued on `stream`.
+ * members == 0 or ncons == 0: SC_OK, nothing happens.  SC_ERR_BAD_ARG (nothing enqueued): a null pointer, nvars 0 or above 255,
+ * ld_out < n, an output that overlaps the values of a used variable, a coefficient not below p, a term that uses an absent variable, a
+ * turned variable that does not point at a stored one; SC_ERR_NOT_POW2: turned variables with n not a power of two. */
+int sc_mpoly_eval_columns_dev(const void* d_vals, uint64_t nvars, uint64_t n, uint64_t members, const uint64_t* var_base, const uint64_t* var_ld,
+                              const uint32_t* var_src, const uint64_t* var_rot, uint64_t ncons, const uint64_t* nterms, const uint8_t* exps, const void* coefs,
+                              void* d_out, uint64_t ld_out, void* stream);
+
+/* Polynomial.scale (sc_scale_dev) for the rows of a matrix in one launch: d_out[c * ld_out + i] = d_in[c * ld_in + i] * factor^i, i < n,
+ * c < cols (both strides >= n; elements between the rows are left alone; d_out may be d_in with the same stride: every element is
+ * read by the thread that writes it.  No other overlap of the two matrices: it is not detected, and the result is undefined).  Bit for bit what
+ * `cols` calls of sc_scale_dev give.  Enqueued on `stream`.  n == 0 or cols == 0: SC_OK, nothing happens; SC_ERR_BAD_ARG (nothing
+ * enqueued): a null pointer, a stride below n, in place with another stride, a factor not below p. */
+int sc_scale_columns_dev(const void* d_in, uint64_t ld_in, void* d_out, uint64_t ld_out, uint64_t n, uint64_t cols, const uint64_t factor[2], void* stream);
+
 /* ---- Rescue-Prime : code/rescue_prime.py:25-60 (hash), :62-104 (trace) ----------------------- */
 /* The permutation of the tutorial's hash over n inputs, one lane each.  The state width is fixed: m = 2 (rate 1, capacity 1), alpha = 3.
  * d_in: n elements (reduced mod p on load).  params: HOST pointer to 4 + 4 * rounds packed canonical residues -- the MDS matrix

@@ -173,4 +173,71 @@ SC_HD void verdict_words(const uint32_t* zero, const long long* rem, const long 
     words[3] = n;
 }
 
+// ---- out[(m * ncons + c) * ld_out + i] = constraint c at point i of member m: multivariate polynomials evaluated pointwise on the
+// values of `members` point sets, every member and every constraint in one launch (mpoly_eval_kernel takes one of each).  Grid
+// (point blocks) x (pairs (m, c), `pair0` on in a launch that is not the first): the pair, and with it every table entry a lane
+// reads, is the same in all lanes of a workgroup, so the tables come in through scalar loads and the loops over terms, variables and
+// exponents are scalar control flow.  The plan (csrc/mpoly_plan.h) is a Horner walk in the constraint's variable of highest
+// exponent: v_h is loaded once, and a term costs the products of its other variables only.  Values are read in canonical form and
+// never converted: the powers of R that the Montgomery products take out are in the plan's coefficients.  No value is modified.
+constexpr uint32_t MPOLY_NO_VAR = 0xFFFFFFFFu;       // MpolyCons::h of a constraint that uses no variable (the value of SC_MPOLY_ABSENT)
+struct MpolyCons {           // one constraint
+    uint32_t h;              // the Horner variable, MPOLY_NO_VAR: none
+    uint32_t first, nterms;  // its terms: [first, first + nterms) of coef / drop / exps
+    uint32_t tail;           // e_h of its last term
+};
+struct MpolyVar {            // a variable's value at point i of member m: element base + m * ld + ((i + rot) mod n) of `vals`
+    uint64_t base, ld, rot;  // (rot != 0 only with n a power of two)
+};
+struct MpolyCols {
+    const Fe* vals;
+    const MpolyVar* vars;    // [nvars]
+    const MpolyCons* cons;   // [ncons]
+    const Fe* coef;          // [terms] coef_t * R^(products the term goes through)
+    const uint32_t* drop;    // [terms] products with v_h before the term is added
+    const uint32_t* exps;    // [terms][nvw]: byte j = e_tj, the Horner variable's byte 0
+    uint32_t nvw, ncons;
+    uint64_t n;
+    Fe* out; uint64_t ld_out;
+    uint32_t pair0;
+};
+SC_HD Fe mpoly_cols_value(const MpolyCols& D, uint32_t j, uint64_t m, uint64_t i) {
+    const MpolyVar V = D.vars[j];
+    return D.vals[V.base + m * V.ld + (V.rot ? ((i + V.rot) & (D.n - 1)) : i)];
+}
+SC_HD void mpoly_cols_thread(const MpolyCols& D, uint32_t wg_x, uint32_t wg_y, uint32_t tid) {
+    const uint64_t i = (uint64_t)wg_x * COLS_WG + tid;
+    if (i >= D.n) return;
+    const uint32_t pair = D.pair0 + wg_y;
+    const uint32_t m = pair / D.ncons;
+    const MpolyCons C = D.cons[pair - m * D.ncons];
+    const Fe vh = C.h != MPOLY_NO_VAR ? mpoly_cols_value(D, C.h, m, i) : fe_zero();
+    Fe acc = fe_zero();
+    for (uint32_t t = C.first; t < C.first + C.nterms; ++t) {
+        for (uint32_t k = D.drop[t]; k; --k) acc = mont_mul(acc, vh);
+        Fe p = D.coef[t];
+        const uint32_t* e = D.exps + (uint64_t)t * D.nvw;
+        for (uint32_t w = 0; w < D.nvw; ++w) {
+            uint32_t word = e[w];
+            for (uint32_t j = 4 * w; word; ++j, word >>= 8) {
+                uint32_t k = word & 255u;
+                if (!k) continue;
+                const Fe v = mpoly_cols_value(D, j, m, i);
+                for (; k; --k) p = mont_mul(p, v);
+            }
+        }
+        acc = fe_add(acc, p);
+    }
+    for (uint32_t k = C.tail; k; --k) acc = mont_mul(acc, vh);
+    D.out[(uint64_t)pair * D.ld_out + i] = acc;
+}
+// ---- out[c][i] = in[c][i] * factor^i, i < n, c < cols (lo / hi: the two-level power table of `factor`): scale_pow_kernel -- Polynomial.scale
+// -- for the rows of a matrix, grid (position blocks) x (columns).  `out` may be `in` (with the same stride).
+SC_HD void scale_cols_thread(const Fe* in, uint64_t ld_in, Fe* out, uint64_t ld_out, uint64_t n, const Fe* lo, const Fe* hi, uint64_t c, uint64_t i) {
+    if (i < n) out[c * ld_out + i] = mont_mul(in[c * ld_in + i], pow2level(lo, hi, i));
+}
+
+// rows of a grid (pairs of mpoly_eval_columns_kernel, columns of scale_cols_kernel) per launch: gridDim.y takes 65 535
+constexpr uint32_t COLS_GRID_ROWS = 65535;
+
 }  // namespace sc

@@ -4,6 +4,7 @@
 // words to a pinned slot, then a sequence number).
 #include "core.h"
 #include "columns.cuh"
+#include "mpoly_plan.h"
 
 namespace sci {
 
@@ -30,6 +31,16 @@ __global__ void __launch_bounds__(256) combine_cols_kernel(const CombineTerm* __
                                                            uint64_t n_out, uint64_t ld_out) {
     const uint64_t i = (uint64_t)blockIdx.x * COLS_WG + threadIdx.x;
     if (i < n_out) out[blockIdx.y * ld_out + i] = combine_cols_elem(terms, nterms, w_m, blockIdx.y, i);
+}
+
+// grid (point blocks) x (pairs of member and constraint): the pair is uniform in a workgroup, the tables are read with scalar loads
+__global__ void __launch_bounds__(256) mpoly_eval_columns_kernel(const MpolyCols D) {
+    mpoly_cols_thread(D, blockIdx.x, blockIdx.y, threadIdx.x);
+}
+
+__global__ void __launch_bounds__(256) scale_cols_kernel(const Fe* in, uint64_t ld_in, Fe* out, uint64_t ld_out, uint64_t n,
+                                                         const Fe* __restrict__ lo, const Fe* __restrict__ hi) {
+    scale_cols_thread(in, ld_in, out, ld_out, n, lo, hi, blockIdx.y, (uint64_t)blockIdx.x * COLS_WG + threadIdx.x);
 }
 
 // one wave: the per-column words -> the words of one pinned slot, published like divide_flags_publish_kernel
@@ -258,5 +269,77 @@ int sc_combine_columns_dev(const sc_combine_term_t* terms, uint64_t nterms, cons
     hipLaunchKernelGGL(combine_cols_kernel, dim3((unsigned)((n_out + COLS_WG - 1) / COLS_WG), (unsigned)cols), dim3(COLS_WG), 0, st,
                        (const CombineTerm*)d_table.p, (uint32_t)nterms, (const Fe*)((const uint8_t*)d_table.p + tbytes), (Fe*)d_out, n_out, ld_out);
     HIPCHK(hipGetLastError());
+    return SC_OK;
+}
+
+// MPolynomial.evaluate_symbolic in the value domain for `members` point sets and `ncons` constraints in one launch
+int sc_mpoly_eval_columns_dev(const void* d_vals, uint64_t nvars, uint64_t n, uint64_t members, const uint64_t* var_base, const uint64_t* var_ld, const uint32_t* var_src,
+                              const uint64_t* var_rot, uint64_t ncons, const uint64_t* nterms, const uint8_t* exps, const void* coefs, void* d_out, uint64_t ld_out,
+                              void* stream) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    if (members == 0 || ncons == 0) return SC_OK;
+    if (!d_vals || !d_out || !var_base || !var_ld || !nterms) return fail(SC_ERR_BAD_ARG, "null argument");
+    if ((var_src == nullptr) != (var_rot == nullptr)) return fail(SC_ERR_BAD_ARG, "var_src and var_rot come together");
+    if (nvars == 0 || nvars > 255) return fail(SC_ERR_BAD_ARG, "between 1 and 255 variables");
+    if (ld_out < n) return fail(SC_ERR_BAD_ARG, "a column stride below the column length");
+    if (members > 0xFFFFFFFFull / ncons) return fail(SC_ERR_BAD_ARG, "more than 2^32 - 1 results");
+    uint64_t total = 0;
+    for (uint64_t c = 0; c < ncons; ++c) total += nterms[c];
+    if (total && (!exps || !coefs)) return fail(SC_ERR_BAD_ARG, "null argument");
+    MpolyPlan P;
+    if (const char* what = mpoly_plan_build((uint32_t)nvars, ncons, nterms, exps, (const Fe*)coefs, P)) return fail(SC_ERR_BAD_ARG, what);
+    std::vector<MpolyVar> vars;
+    const char* what = nullptr;
+    if (const int bad = mpoly_vars_resolve((uint32_t)nvars, n, var_base, var_ld, var_src, var_rot, P.used, vars, &what)) return fail(bad == 2 ? SC_ERR_NOT_POW2 : SC_ERR_BAD_ARG, what);
+    if (n == 0) return SC_OK;
+    const uint64_t pairs = members * ncons;
+    const uintptr_t out_lo = (uintptr_t)d_out, out_hi = out_lo + ((pairs - 1) * ld_out + n) * sizeof(Fe);
+    for (uint64_t j = 0; j < nvars; ++j) {
+        if (!P.used[j]) continue;
+        const uintptr_t lo = (uintptr_t)d_vals + vars[j].base * sizeof(Fe), hi = lo + ((members - 1) * vars[j].ld + n) * sizeof(Fe);
+        if (lo < out_hi && out_lo < hi) return fail(SC_ERR_BAD_ARG, "the output may not overlap the values");
+    }
+    hipStream_t st = pick_stream(stream);
+    // the tables as the kernel reads them: coefficients (16-byte elements first), variables, constraints, drops, exponent words
+    const size_t b_coef = P.coef.size() * sizeof(Fe), b_vars = vars.size() * sizeof(MpolyVar), b_cons = P.cons.size() * sizeof(MpolyCons),
+                 b_drop = P.drop.size() * sizeof(uint32_t), b_exps = P.exps.size() * sizeof(uint32_t);
+    std::vector<uint8_t> table(b_coef + b_vars + b_cons + b_drop + b_exps);
+    uint8_t* at = table.data();
+    auto put = [&](const void* src, size_t bytes) { if (bytes) memcpy(at, src, bytes); at += bytes; return (size_t)(at - bytes - table.data()); };
+    const size_t o_coef = put(P.coef.data(), b_coef), o_vars = put(vars.data(), b_vars), o_cons = put(P.cons.data(), b_cons), o_drop = put(P.drop.data(), b_drop),
+                 o_exps = put(P.exps.data(), b_exps);
+    PoolTmpAsync d_table;
+    SCCHK(d_table.get(table.size() + 8));
+    SCCHK(upload_words(d_table.p, table.data(), table.size(), st));
+    const uint8_t* T = (const uint8_t*)d_table.p;
+    for (uint64_t pair0 = 0; pair0 < pairs; pair0 += COLS_GRID_ROWS) {
+        const uint64_t rows = pairs - pair0 < COLS_GRID_ROWS ? pairs - pair0 : COLS_GRID_ROWS;
+        const MpolyCols D{(const Fe*)d_vals, (const MpolyVar*)(T + o_vars), (const MpolyCons*)(T + o_cons), (const Fe*)(T + o_coef), (const uint32_t*)(T + o_drop),
+                          (const uint32_t*)(T + o_exps), P.nvw, (uint32_t)ncons, n, (Fe*)d_out, ld_out, (uint32_t)pair0};
+        hipLaunchKernelGGL(mpoly_eval_columns_kernel, dim3((unsigned)((n + COLS_WG - 1) / COLS_WG), (unsigned)rows), dim3(COLS_WG), 0, st, D);
+        HIPCHK(hipGetLastError());
+    }
+    return SC_OK;
+}
+
+// Polynomial.scale for the rows of a matrix: out[c][i] = in[c][i] * factor^i
+int sc_scale_columns_dev(const void* d_in, uint64_t ld_in, void* d_out, uint64_t ld_out, uint64_t n, uint64_t cols, const uint64_t factor[2], void* stream) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    if (n == 0 || cols == 0) return SC_OK;
+    if (!d_in || !d_out || !factor) return fail(SC_ERR_BAD_ARG, "null argument");
+    if (ld_in < n || ld_out < n) return fail(SC_ERR_BAD_ARG, "a column stride below the column length");
+    if (d_out == d_in && ld_out != ld_in && cols > 1) return fail(SC_ERR_BAD_ARG, "in place needs the input's column stride");
+    if (fe_ge_p(fe_from(factor))) return fail(SC_ERR_BAD_ARG, "factor is not a canonical residue");
+    hipStream_t st = pick_stream(stream);
+    PowTables* pw;
+    SCCHK(get_pow(fe_from(factor), n, st, &pw));
+    for (uint64_t done = 0; done < cols; done += COLS_GRID_ROWS) {
+        const uint64_t k = cols - done < COLS_GRID_ROWS ? cols - done : COLS_GRID_ROWS;
+        hipLaunchKernelGGL(scale_cols_kernel, dim3((unsigned)((n + COLS_WG - 1) / COLS_WG), (unsigned)k), dim3(COLS_WG), 0, st, (const Fe*)d_in + done * ld_in, ld_in,
+                           (Fe*)d_out + done * ld_out, ld_out, n, (const Fe*)pw->lo, (const Fe*)pw->hi);
+        HIPCHK(hipGetLastError());
+    }
     return SC_OK;
 }

@@ -546,6 +546,156 @@ class FastStark:
                 out[i]._degree = degree                                  # just read: the degree check of fast_stark.py:124 need not ask the device again
         return [q if q is not None else reference_way(a) for q, a in zip(out, constraints)]
 
+    def transition_quotients_batch(self, transition_constraints, points, transition_zerofier, pending=None):
+        """[self._transition_quotients_on_device(transition_constraints, point, zerofier, pending) for point in points] -- the same
+        DevicePolynomials, coefficient for coefficient and degree for degree -- for the members of a batch of proofs (points[m]: X, the
+        trace polynomials, their scaled_later(omicron) copies, as `prove` builds them), with the work of each value-domain order done
+        for all members together: the stored variables evaluated by one sc_coset_evaluate_columns_dev per run of consecutive
+        equal-length coefficient rows (ONE call for all members when their trace polynomials are the rows of one matrix), X -- the
+        same object in every point -- and the zerofier once, the AIR of all members and constraints in ONE launch
+        (sc_mpoly_eval_columns_dev), ONE pointwise division with one verdict (appended to `pending`, or waited for on the spot: "divide
+        by zero"), ONE inverse transform, ONE scaling by g^-i and ONE degree call with one host wait.  The quotients are views of the
+        rows of one matrix.  What the batched calls do not serve goes through the per-member method, unchanged: a (member, constraint)
+        whose interpolant is longer than bound - deg Z (a false witness), a constraint of a shape or bound the value domain does not
+        take, and members whose points differ in length or structure; members of different degrees are batched among their likes."""
+        constraints, points = list(transition_constraints), [list(point) for point in points]
+        tz_dev = self._lift(transition_zerofier)
+        in_runs = self.num_registers >= FastStark.COLUMN_BATCH_MIN          # (as `prove` decides it)
+        one_member = lambda m, some: self._transition_quotients_on_device(some, points[m], tz_dev, pending, in_runs)
+        DevicePolynomial.degrees([q for point in points for q in point if type(q) is DevicePolynomial])      # one wait for those not known yet
+        out, alike = [None] * len(points), {}
+        for m, point in enumerate(points):
+            degrees = tuple(q.degree() for q in point)
+            # where every variable comes from: (index of its unscaled source in the point, the factor), None for a polynomial of its own
+            structure = []
+            for q in point:
+                source = getattr(q, "scaled_from", None)
+                k = next((k for k, other in enumerate(point) if other is source[0]), None) if source is not None else None
+                if source is not None and (k is None or getattr(point[k], "scaled_from", None) is not None):
+                    structure = None                     # scaled off something outside the point: the per-member method knows what to do
+                    break
+                structure.append(None if source is None else (k, source[1].value))
+            if structure is None or self.field.p != Field.P_MAIN:
+                out[m] = one_member(m, constraints)
+            else:
+                alike.setdefault((degrees, tuple(structure)), []).append(m)
+        for (degrees, structure), members in alike.items():
+            for m, quotients in zip(members, self._transition_quotients_alike(constraints, points, members, degrees, structure, tz_dev, pending, one_member)):
+                out[m] = quotients
+        return out
+
+    def _transition_quotients_alike(self, constraints, points, members, degrees, structure, tz_dev, pending, one_member):
+        """transition_quotients_batch for members whose points have the same degrees and the same structure"""
+        field, lib, gen = self.field, _sc.lib(), _sc.fe_bytes(self.generator.value)
+        dr = tz_dev.degree()
+        K, nvars = len(members), len(degrees)
+        out, groups = [[None] * len(constraints) for _ in members], {}
+        for i, a in enumerate(constraints):
+            plan = a.value_domain_terms(list(degrees))
+            if plan is NotImplemented or dr < 0 or plan[0] < max(dr, MPolynomial.VALUE_DOMAIN_MIN_DEGREE):
+                continue
+            bound, terms = plan
+            root, order = _shrink_order(self.omicron, self.omicron_domain_length, max(bound, dr))
+            if len(tz_dev) > order or any(len(q) > order for m in members for q in points[m]):
+                continue
+            groups.setdefault(order, (root, []))[1].append((i, bound, terms))
+        for order, (root, group) in groups.items():
+            rt, C = _sc.fe_bytes(root.value), len(group)
+            used = [any(k[j] for _, _, terms in group for k, _ in terms) for j in range(nvars)]
+            # a variable scaled by the coset's own root is its source's codeword, one place on (see _transition_quotients_on_device)
+            turned = {j: s[0] for j, s in enumerate(structure) if used[j] and s is not None and s[1] == root.value}
+            stored = [(used[j] and j not in turned) or j in turned.values() for j in range(nvars)]
+            # a stored variable that is the same object in every point (X) has ONE row; the others a row per member, member after
+            # member, so that coefficient rows that are consecutive in memory are evaluated into consecutive rows
+            shared = [stored[j] and all(points[m][j] is points[members[0]][j] for m in members) for j in range(nvars)]
+            own = [j for j in range(nvars) if stored[j] and not shared[j]]
+            common = [j for j in range(nvars) if shared[j]]
+            vals = DeviceVector((K * len(own) + len(common)) * order)
+            row_of = lambda t, j: t * len(own) + own.index(j) if not shared[j] else K * len(own) + common.index(j)
+            self._evaluate_rows([(row_of(t, j), points[m][j], degrees[j]) for t, m in enumerate(members) for j in own] +
+                                [(row_of(0, j), points[members[0]][j], degrees[j]) for j in common], rt, order, vals)
+            var_base = (ctypes.c_uint64 * nvars)(*[row_of(0, j) * order if stored[j] else 0 for j in range(nvars)])
+            var_ld = (ctypes.c_uint64 * nvars)(*[len(own) * order if stored[j] and not shared[j] else 0 for j in range(nvars)])
+            var_src = (ctypes.c_uint32 * nvars)(*[turned.get(j, j if stored[j] else 0xFFFFFFFF) for j in range(nvars)])
+            var_rot = (ctypes.c_uint64 * nvars)(*[1 if j in turned else 0 for j in range(nvars)])
+            kept = self._zerofier_values.get(order)
+            if kept is not None and kept[0] is tz_dev:
+                zvals = kept[1]
+            else:
+                zvals = DeviceVector(order)
+                _sc._check(lib.sc_coset_evaluate_dev(tz_dev.vec.ptr, dr + 1, gen, rt, order, zvals.ptr, None))
+                if len(self._zerofier_values) >= 4:
+                    self._zerofier_values.clear()
+                self._zerofier_values[order] = (tz_dev, zvals)
+            cols = K * C
+            tvals, whole = DeviceVector(cols * order), DeviceVector(cols * order)
+            nterms = (ctypes.c_uint64 * C)(*[len(terms) for _, _, terms in group])
+            exps = bytes(e for _, _, terms in group for k, _ in terms for e in k)
+            coefs = b"".join(v.to_bytes(16, "little") for _, _, terms in group for _, v in terms)
+            _sc._check(lib.sc_mpoly_eval_columns_dev(vals.ptr, nvars, order, K, var_base, var_ld, var_src, var_rot, C, nterms, exps, coefs, tvals.ptr, order, None))
+            handle = ctypes.c_void_p()
+            rc = lib.sc_pointwise_div_columns_later_dev(tvals.ptr, order, zvals.ptr, 0, tvals.ptr, order, order, cols, ctypes.byref(handle), None)
+            if rc == _sc.SC_ERR_UNSUPPORTED:
+                continue                                     # no pinned slot for the verdict: these constraints go member by member below
+            _sc._check(rc)
+            check = _sc.Later(handle)
+
+            def verdict(check=check):
+                assert(not check.wait()[0]), "divide by zero"       # like algebra.py:92
+            if pending is not None:
+                pending.append(verdict)
+            else:
+                verdict()
+            _sc._check(lib.sc_ntt_columns_dev(tvals.ptr, whole.ptr, order, cols, rt, 1, None))
+            _sc._check(lib.sc_scale_columns_dev(whole.ptr, order, whole.ptr, order, order, cols, _sc.fe_bytes(self.generator.inverse().value), None))
+            found = (ctypes.c_int64 * cols)()
+            _sc._check(lib.sc_vec_degree_columns_dev(whole.ptr, order, order, cols, found, None))
+            for t in range(K):
+                for c, (i, bound, _) in enumerate(group):
+                    degree = int(found[t * C + c])
+                    if degree > bound - dr:
+                        continue                             # not exact: the per-member method decides what comes out
+                    if degree >= 0:
+                        out[t][i] = DevicePolynomial(DeviceVector.wrap(whole.ptr + 16 * order * (t * C + c), degree + 1, whole), field, degree + 1)
+                    else:
+                        out[t][i] = DevicePolynomial(DeviceVector(1), field, 0)
+                    out[t][i]._degree = degree
+        for t, m in enumerate(members):
+            left = [i for i in range(len(constraints)) if out[t][i] is None]
+            if left:
+                for i, quotient in zip(left, one_member(m, [constraints[i] for i in left])):
+                    out[t][i] = quotient
+        return out
+
+    def _evaluate_rows(self, rows, rt, order, vals):
+        """rows: [(row of `vals`, polynomial, its degree)] in the order of the rows.  Every polynomial -- q, or for q = source(f X)
+        its source at the offset g f: the transform's own offset does the scaling -- is evaluated on the coset g <root> of `order`
+        points into its row: ONE sc_coset_evaluate_columns_dev per maximal run of coefficient vectors of one length and one offset
+        that lie one behind the other in memory and go to consecutive rows (what _evaluate_runs does inside one point)."""
+        lib = _sc.lib()
+
+        def place(q, degree):
+            source = getattr(q, "scaled_from", None)
+            poly, offset = (source[0], self.generator * source[1]) if source is not None else (q, self.generator)
+            if type(poly) is DevicePolynomial and len(poly):
+                return poly.vec.ptr, len(poly), offset.value       # (all len(poly) coefficients go in: those above the degree are zeros)
+            return poly.vec.ptr, degree + 1, offset.value
+        at = 0
+        while at < len(rows):
+            row, q, degree = rows[at]
+            first = place(q, degree)
+            run = 1
+            while at + run < len(rows) and rows[at + run][0] == row + run:
+                following = place(rows[at + run][1], rows[at + run][2])
+                if following[1:] != first[1:] or following[0] != first[0] + 16 * first[1] * run:
+                    break
+                run += 1
+            if run >= 2:
+                _sc._check(lib.sc_coset_evaluate_columns_dev(first[0], first[1], run, _sc.fe_bytes(first[2]), rt, order, vals.ptr + 16 * row * order, None))
+            else:
+                _sc._check(lib.sc_coset_evaluate_dev(first[0], first[1], _sc.fe_bytes(first[2]), rt, order, vals.ptr + 16 * row * order, None))
+            at += run
+
     def _evaluate_runs(self, point, stored, rt, order, vals):
         """The stored variables whose coefficient vectors are consecutive rows of one matrix -- trace_s(X) for consecutive s, and
         trace_s(omicron X) where they are not read off the former -- evaluated into their (consecutive) places of `vals` by ONE

@@ -33,6 +33,49 @@ class AlsoOpen:
         self.position_arrays = None                        # per codeword: its opened positions as a uint64 array next to the answers
 
 
+class AlsoOpenForests:
+    """What AlsoOpen is to `prove`, for `prove_batch`: committed codewords that live in Merkle forests -- matrices of rows of the
+    domain's length N -- opened per member at the sorted positions {i, i + shift, i + N/2, i + shift + N/2 (mod N)}, duplicates kept,
+    over that member's top-level indices i (fast_stark.py:154-158).  forests: MerkleForests; owners[p][m]: the tree numbers of
+    forests[p] that belong to member m of the batch -- m R ... m R + R - 1 for a forest of R boundary-quotient codewords per member,
+    [m] for one codeword per member, [0] for every member of a forest over ONE codeword all members share (the transition
+    zerofier's: its root is Merkle.commit's of that codeword).  After prove_batch: positions[m] = member m's positions, answers[m] =
+    [(int residues, paths)] at them, one pair per (forest, tree) in the order of `owners`.  On the forest path the openings travel in
+    the launch that fetches the members' FRI openings."""
+
+    def __init__(self, forests, owners, shift):
+        self.forests, self.owners, self.shift = list(forests), list(owners), shift
+        self.answers, self.positions = None, None
+
+    def _check(self, N, members):
+        for forest in self.forests:
+            assert(forest.n == N), "a forest opened with a FRI batch has rows of the domain's length"
+        assert(len(self.owners) == len(self.forests)), "one list of owners per forest"
+        for of_forest in self.owners:
+            assert(isinstance(of_forest, (list, tuple)) and len(of_forest) == members and all(isinstance(trees, (list, tuple)) for trees in of_forest)), \
+                "owners: per forest one list of tree numbers per member"
+
+    def _positions(self, indices, N):
+        duplicated = list(indices) + [(i + self.shift) % N for i in indices]
+        return sorted(duplicated + [(i + N // 2) % N for i in duplicated])
+
+    def _requests(self, members):
+        """per forest, the (tree, position) pairs of the given members (numbers in the batch), whose positions are known"""
+        return [[(tree, position) for m in members for tree in of_forest[m] for position in self.positions[m]] for of_forest in self.owners]
+
+    def _take(self, members, fetched):
+        """fetched: per forest (values, paths) in the order of _requests(members)"""
+        at = [0] * len(self.forests)
+        for m in members:
+            self.answers[m] = []
+            k = len(self.positions[m])
+            for p, of_forest in enumerate(self.owners):
+                values, paths = fetched[p]
+                for _ in of_forest[m]:
+                    self.answers[m].append((values[at[p]:at[p] + k], paths[at[p]:at[p] + k]))
+                    at[p] += k
+
+
 def library_transcript(proof_stream, rounds):
     """The byte strings in `proof_stream` if the library may run `rounds` rounds of the commit phase on it itself
     (sc_fri_commit_dev computes SHAKE-256(pickle(objects)) on its own), else None.  Only a plain ProofStream: a subclass may derive
@@ -356,29 +399,41 @@ class Fri:
                 return False
         return True
 
-    def prove_batch(self, codewords, proof_streams):
+    def prove_batch(self, codewords, proof_streams, also_open=None):
         """[self.prove(codeword, stream) for ...] -- the same top-level indices, and after it every stream holds exactly what `prove`
         would have pushed (serialize() is byte-identical, member by member) -- with the members' work on the device done together:
         per round ONE Merkle forest over all members' codewords (csrc/merkle_forest.cuh; from the second round on its leaf stage
         computes every member's fold with that member's alpha) and ONE wait for all roots; then one kernel for every opening of
         every member.  The Fiat-Shamir step goes through each stream's own push / prover_fiat_shamir, so any ProofStream subclass
-        and streams that already hold objects are served.  Shapes the forest path does not serve go member by member through `prove`."""
+        and streams that already hold objects are served.  Shapes the forest path does not serve go member by member through `prove`.
+        also_open (optional, an AlsoOpenForests): committed codewords in forests of their own, opened per member at the positions
+        its sampled indices give -- in the launch that fetches a chunk's FRI openings; member by member, in one launch of their own.
+        The streams hold what they hold without it."""
         codewords, proof_streams = list(codewords), list(proof_streams)
         assert(len(codewords) == len(proof_streams)), "prove_batch needs one proof stream per codeword"
         for codeword in codewords:
             assert(self.domain_length == len(codeword)), "initial codeword length does not match length of initial codeword"
+        if also_open is not None:
+            also_open._check(self.domain_length, len(codewords))  # (before any work)
+            also_open.answers, also_open.positions = [None] * len(codewords), [None] * len(codewords)
         if not codewords:
             return []
         if not self._batchable(codewords):
-            return [self.prove(codeword, stream) for codeword, stream in zip(codewords, proof_streams)]
+            indices = [self.prove(codeword, stream) for codeword, stream in zip(codewords, proof_streams)]
+            if also_open is not None:
+                everyone = range(len(codewords))
+                also_open.positions = [also_open._positions(top, self.domain_length) for top in indices]
+                also_open._take(everyone, _sc.query_forests(also_open.forests, also_open._requests(everyone)))
+            return indices
         self._check_omega_order(self.domain_length)              # (before anything is enqueued)
         step = max(1, _sc.FOREST_MAX_LEAVES // self.domain_length)
         indices = []
         for lo in range(0, len(codewords), step):
-            indices += self._prove_forest(codewords[lo:lo + step], proof_streams[lo:lo + step])
+            indices += self._prove_forest(codewords[lo:lo + step], proof_streams[lo:lo + step], also_open, lo)
         return indices
 
-    def _prove_forest(self, members, streams):
+    def _prove_forest(self, members, streams, also_open=None, member0=0):
+        """members / streams: a chunk of the batch, whose member 0 is member `member0` of the batch (also_open counts in the batch)"""
         rounds, s, N, K = self.num_rounds(), self.num_colinearity_tests, self.domain_length, len(members)
         # commit phase (fri.py:66-94) for all members: forest r holds the members' r-th codewords
         forests = [_sc.MerkleForest.build(_sc.CodewordMatrix.from_members(members))]
@@ -419,7 +474,16 @@ class Fri:
                 if j > 0:
                     request += mine[j - 1]
                 requests[j] += [(m, index) for index in request]
-        fetched = _sc.query_forests(forests, requests)           # ONE launch for every opening of every member
+        extra = []
+        if also_open is not None:
+            chunk = range(member0, member0 + K)
+            for m in chunk:
+                also_open.positions[m] = also_open._positions(top[m - member0], N)
+            extra = also_open._requests(chunk)
+        # ONE launch for every opening of every member, the further forests' included
+        fetched = _sc.query_forests(forests + (also_open.forests if also_open is not None else []), requests + extra)
+        if also_open is not None:
+            also_open._take(chunk, fetched[rounds:])
         for m, stream in enumerate(streams):
             opened = []
             for j in range(rounds):

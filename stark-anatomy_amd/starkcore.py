@@ -97,6 +97,7 @@ SIGNATURES = {
     "sc_coset_divide_columns_later_dev": (_int, [_vp, _u64, _u64, _vp, _u64, _u64, _u64, _vp, _vp, _u64, _vp, ctypes.POINTER(_u64), _u64, ctypes.POINTER(_vp), _vp]),
     "sc_combine_columns_dev": (_int, [_vp, _u64, _vp, _u64, _vp, _u64, _u64, _vp]),
     "sc_scale_dev": (_int, [_vp, _vp, _u64, _vp, _vp]),
+    "sc_scale_columns_dev": (_int, [_vp, _u64, _vp, _u64, _u64, _u64, _vp, _vp]),
     "sc_axpy_shift_dev": (_int, [_vp, _u64, _vp, _u64, _u64, _vp, _vp]),
     "sc_scale_slab_dev": (_int, [_vp, _vp, _u64, _u64, _u64, _u64, _vp, _vp]),
     "sc_fri_fold": (_int, [_vp, _u64, _vp, _vp, _vp, _vp]),
@@ -144,6 +145,7 @@ SIGNATURES = {
     "sc_mpoly_eval_dev": (_int, [_vp, _u64, _u64, _vp, _vp, _u64, _vp, _vp]),
     "sc_mpoly_eval_ex_dev": (_int, [_vp, _u64, _u64, _vp, _vp, _u64, _vp, _int, _vp]),
     "sc_mpoly_eval_rot_dev": (_int, [_vp, _u64, _u64, _vp, _vp, _u64, _vp, _int, _vp, _vp, _vp]),
+    "sc_mpoly_eval_columns_dev": (_int, [_vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp]),
     "sc_zerofier": (_int, [_vp, _u64, _vp]),
     "sc_evaluate": (_int, [_vp, _u64, _vp, _u64, _vp]),
     "sc_interpolate": (_int, [_vp, _vp, _u64, _vp]),
