@@ -87,8 +87,18 @@ int sc_debug_trace(void* d_buf);
 
 /* diagnostics: out[i] = op(a[i], b[i]) computed by the device field routines the kernels use.
  * op 0: a*b*2^-128 (Montgomery product, b < p), 1: a+b, 2: a-b, 3: a*b, 4: a/2, 5: a^-1, 6: portable Montgomery product,
- * 7: the same product through the two-at-a-time routine of the butterflies (all ones if its two halves disagree) */
+ * 7: the same product through the two-at-a-time routine of the butterflies with a, b in BOTH of its slots (all ones if its two
+ * halves disagree; distinct operands per slot: sc_field_selftest2) */
 int sc_field_selftest(int op, const void* a, const void* b, void* out, uint64_t n);
+/* diagnostics: the two-slot and the top-limb-correction ("fast") forms of the field routines, through the same dispatchers the kernels
+ * call.  Per element i: operands a[i], b[i] (slot 0) and c[i], d[i] (slot 1; read but unused by the one-slot ops), up to four results
+ * out[k*n + i] (k = 0..3, unused ones 0) and word[i]: bit 0 = this lane's own bit of the routine's `rare` mask (started at 0),
+ * bit 1 = whether any lane of its wave raised it (0 for the exact ops).  The launch has 256 threads per workgroup with element i on
+ * thread i, so a wave is the 64 consecutive elements 64w .. 64w+63; the last wave may be partial.  The value of a flagged lane is undefined.
+ * op 0: mont_mul2 -> a*b*2^-128, c*d*2^-128 (a, c < 2^128; b, d < p)      1: fe_addsub2 -> a+b, a-b, c+d, c-d
+ *    2: fe_add_fast -> a+b   3: fe_sub_fast -> a-b   4: mont_mul_fast -> a*b*2^-128
+ *    5: mont_mul2_fast -> as op 0   6: fe_addsub2_fast -> as op 1   7: fe_neg -> -a */
+int sc_field_selftest2(int op, const void* a, const void* b, const void* c, const void* d, void* out, uint32_t* word, uint64_t n);
 
 /* ---- device vectors ----------------------------------------------------------------------- */
 int sc_vec_alloc(uint64_t n, sc_vec_t** out);

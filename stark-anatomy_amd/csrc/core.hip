@@ -332,8 +332,8 @@ __global__ void __launch_bounds__(256) field_selftest_kernel(int op, const Fe* _
         case 3: r = fe_mul(x, y); break;
         case 4: r = fe_half(x); break;
         case 5: r = from_mont(mont_inv(to_mont(x))); break;
-        case 7: {                                           // the interleaved pair of products the butterflies use: both halves
-            Fe r0, r1;                                      // must agree with each other (operand pairs swapped between the lanes' roles)
+        case 7: {                                           // the interleaved pair of products the butterflies use, the SAME operands in
+            Fe r0, r1;                                      // both slots: the halves must agree (distinct operands: field_selftest2_kernel)
             mont_mul2(x, y, x, y, r0, r1);
             r = fe_eq(r0, r1) ? r0 : Fe{~0ull, ~0ull};
             break;
@@ -341,6 +341,36 @@ __global__ void __launch_bounds__(256) field_selftest_kernel(int op, const Fe* _
         default: r = mont_mul_c(x, y); break;               // portable reference implementation
     }
     out[i] = r;
+}
+
+// diagnostics: the two-slot and the top-limb-correction forms through the dispatchers of field.cuh, distinct operands per slot.
+// Element i runs on thread i of 256-thread workgroups, so a wave is 64 consecutive elements; out holds four planes of n elements.
+// word[i] bit 0 = lane i's own bit of `rare` (started at 0) after the call, bit 1 = rare_any(rare) as its wave saw it.
+// The device forms keep `rare` as a 64-lane mask; the portable twins (SC_ASM_* = 0) keep 0 / 1 per lane.
+template <bool MASK> __device__ __forceinline__ uint32_t selftest_word(rare_t rare) {
+    const uint32_t own = MASK ? (uint32_t)((rare >> (threadIdx.x & 63u)) & 1u) : (uint32_t)(rare != 0);
+    return own | (rare_any(rare) ? 2u : 0u);
+}
+__global__ void __launch_bounds__(256) field_selftest2_kernel(int op, const Fe* __restrict__ a, const Fe* __restrict__ b, const Fe* __restrict__ c,
+                                                             const Fe* __restrict__ d, Fe* __restrict__ out, uint32_t* __restrict__ word, uint64_t n) {
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const Fe x = a[i], y = b[i], z = c[i], w = d[i];
+    Fe r0{0, 0}, r1{0, 0}, r2{0, 0}, r3{0, 0};
+    rare_t rare = 0;
+    uint32_t flags = 0;
+    switch (op) {
+        case 0: mont_mul2(x, y, z, w, r0, r1); break;
+        case 1: fe_addsub2(x, y, z, w, r0, r1, r2, r3); break;
+        case 2: r0 = fe_add_fast(x, y, rare); flags = selftest_word<SC_ASM_ADDSUB != 0>(rare); break;
+        case 3: r0 = fe_sub_fast(x, y, rare); flags = selftest_word<SC_ASM_ADDSUB != 0>(rare); break;
+        case 4: r0 = mont_mul_fast(x, y, rare); flags = selftest_word<SC_ASM_MUL != 0>(rare); break;
+        case 5: mont_mul2_fast(x, y, z, w, r0, r1, rare); flags = selftest_word<SC_ASM_MUL != 0>(rare); break;
+        case 6: fe_addsub2_fast(x, y, z, w, r0, r1, r2, r3, rare); flags = selftest_word<SC_ASM_ADDSUB != 0>(rare); break;
+        default: r0 = fe_neg(x); break;
+    }
+    out[i] = r0; out[n + i] = r1; out[2 * n + i] = r2; out[3 * n + i] = r3;
+    word[i] = flags;
 }
 
 // Field.sample (code/algebra.py:116-120) of `count` byte strings of `width` <= 32 bytes each: the big-endian integer mod p.
@@ -1307,6 +1337,27 @@ int sc_field_selftest(int op, const void* a, const void* b, void* out, uint64_t 
     hipLaunchKernelGGL(field_selftest_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g.stream, op, (const Fe*)da, (const Fe*)db, (Fe*)dc, n);
     HIPCHK(hipGetLastError());
     return download(out, dc, n * sizeof(Fe), g.stream);
+}
+
+int sc_field_selftest2(int op, const void* a, const void* b, const void* c, const void* d, void* out, uint32_t* word, uint64_t n) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    if (op < 0 || op > 7) return fail(SC_ERR_BAD_ARG, "unknown field self-test op");
+    if (!n) return SC_OK;
+    if (!a || !b || !c || !d || !out || !word) return fail(SC_ERR_BAD_ARG, "null argument");
+    void *din, *dout, *dword;
+    const size_t plane = n * sizeof(Fe);
+    SCCHK(scratch(1, 4 * plane, &din));
+    SCCHK(scratch(2, 4 * plane, &dout));
+    SCCHK(scratch(3, n * sizeof(uint32_t), &dword));
+    const void* src[4] = {a, b, c, d};
+    for (int k = 0; k < 4; ++k) SCCHK(upload((char*)din + k * plane, src[k], plane, g.stream));
+    const Fe* in = (const Fe*)din;
+    hipLaunchKernelGGL(field_selftest2_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g.stream, op, in, in + n, in + 2 * n, in + 3 * n,
+                       (Fe*)dout, (uint32_t*)dword, n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, dout, 4 * plane, hipMemcpyDeviceToHost, g.stream));
+    return download(word, dword, n * sizeof(uint32_t), g.stream);
 }
 
 // ---- ntt

@@ -37,6 +37,7 @@ SIGNATURES = {
     "sc_ntt_num_passes": (_int, [_u64]),
     "sc_debug_trace": (_int, [_vp]),
     "sc_field_selftest": (_int, [_int, _vp, _vp, _vp, _u64]),
+    "sc_field_selftest2": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _u64]),
     "sc_vec_alloc": (_int, [_u64, ctypes.POINTER(_vp)]),
     "sc_vec_free": (_int, [_vp]),
     "sc_vec_wrap": (_int, [_vp, _u64, ctypes.POINTER(_vp)]),

@@ -9,6 +9,7 @@ import subprocess
 import pytest
 
 from conftest import REPO
+import field_cases
 from oracle import py_oracle as po
 
 P = po.P
@@ -34,17 +35,7 @@ def emu():
     return lib
 
 
-def _values():
-    """canonical values: 25 edge values, 300 random ones, 120 that are small, near p or multiples of 2^96"""
-    edge = [0, 1, 2, P - 1, P - 2, P - 3, PH3 << 96, (PH3 << 96) - 1, (PH3 - 1) << 96, ((PH3 - 1) << 96) + M96, 1 << 32, M32, 1 << 64, (1 << 64) - 1,
-            1 << 96, M96, P - (1 << 32), P - (1 << 96), 1 << 127, (1 << 127) - 1, (P + 1) // 2, (P - 1) // 2, (1 << 32) + 1, P - (1 << 64), (1 << 127) + 1]
-    assert len(edge) == 25 and all(0 <= v < P for v in edge)
-    rng = random.Random(20240611)
-    rand = [rng.randrange(P) for _ in range(300)]
-    special = [rng.randrange(1 << 33) for _ in range(40)] + [P - 1 - rng.randrange(1 << 33) for _ in range(40)] + \
-              [rng.randrange(PH3 + 1) << 96 for _ in range(40)]
-    special = [v % P for v in special]
-    return edge, rand, special
+_values = field_cases.values      # the operand lists live in field_cases.py, shared with the model and the device test
 
 
 def _pack(vals):
@@ -100,25 +91,13 @@ def test_known_cases_are_flagged(emu):
     flag, fast, exact = _one(emu, 0, P - 1, 1 << 32)
     assert flag == 1 and exact == (1 << 32) - 1 and fast != exact
     # a product whose pre-correction difference R = (T - m' p) / 2^128 is negative with low limb 0xFFFFFFFF (its correction carries
-    # out of limb 0): searched among the products a * R~ = a with a = k * 2^32, modelled here with Python integers
-    pinv = pow(P, -1, 1 << 128)
-    r_m = (1 << 128) % P
+    # out of limb 0): searched among the products a * R~ = a with a = k * 2^32, modelled with Python integers (field_cases.flagged_products)
     found = 0
-    for k in range(1, 4000):
-        a = (k * 0x9E3779B97F4A7C15 % (1 << 96)) << 32
-        if a >= P:
-            continue
-        t = a * r_m
-        m = (t & M128) * pinv & M128
-        assert (t - m * P) % (1 << 128) == 0
-        r = (t - m * P) >> 128
-        assert -P < r < P
-        if r < 0 and (r & M32) == M32:
-            flag, fast, exact = _one(emu, 2, a, r_m)
-            assert exact == a and flag == 1, hex(a)
-            found += 1
-            if found == 5:
-                break
+    for a, r_m in field_cases.flagged_products(5):
+        assert r_m == (1 << 128) % P and a < P and a % (1 << 32) == 0
+        flag, fast, exact = _one(emu, 2, a, r_m)
+        assert exact == a and flag == 1, hex(a)
+        found += 1
     assert found == 5
 
 
