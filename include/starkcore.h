@@ -468,6 +468,16 @@ int sc_pickle_proof(const void* ops, uint64_t ops_len, const void* moduli, uint3
  * randomizer polynomial of FastStark.prove (fast_stark.py:117: one os.urandom(17) draw per coefficient) without a Python object
  * per coefficient.  Synchronous (the bytes are the caller's host memory). */
 int sc_sample_bytes_dev(const void* bytes, uint64_t count, uint32_t width, void* d_out, void* stream);
+/* The randomized trace matrix of a batch of proofs (fast_stark.py:79-81 for every member in one launch): column c = m * registers
+ * + s of d_out (at element c * ld_out) is the trace column at element c * ld_trace of d_trace (`rows` elements) followed by `extra`
+ * randomizer values; element rows + r is Field.sample of the `width` (1..32) bytes at draws + m * draws_stride + (r * registers + s)
+ * * width -- the reference's draw order, row by row, register by register.  `draws` is HOST memory, draws_stride the bytes from one
+ * member's block to the next (at least extra * registers * width when members > 1).  rows == 0 (d_trace may be NULL) with
+ * registers == 1 samples one polynomial of `extra` coefficients per member.  ld_out >= rows + extra, ld_trace >= rows; the output
+ * may not overlap the trace.  members == 0, registers == 0 or rows + extra == 0: nothing happens.  Synchronous when there are
+ * draws (the bytes are the caller's host memory), else enqueued on `stream`. */
+int sc_randomized_columns_dev(const void* d_trace, uint64_t rows, uint64_t ld_trace, uint64_t members, uint64_t registers, const void* draws, uint64_t draws_stride,
+                              uint64_t extra, uint32_t width, void* d_out, uint64_t ld_out, void* stream);
 /* The same with the draws made by the library: `count` times getrandom(width bytes) -- what os.urandom(width) is -- split over
  * host threads into a pinned staging buffer, one asynchronous copy, Field.sample on the device.  Enqueued on `stream`.  For
  * callers whose os.urandom is the operating system's (a patched, seeded os.urandom must go through sc_sample_bytes_dev, whose

@@ -237,6 +237,34 @@ SC_HD void scale_cols_thread(const Fe* in, uint64_t ld_in, Fe* out, uint64_t ld_
     if (i < n) out[c * ld_out + i] = mont_mul(in[c * ld_in + i], pow2level(lo, hi, i));
 }
 
+// ---- the randomized trace matrix of a batch of proofs (code/fast_stark.py:79-81 for every member at once): column c = m * registers
+// + s of `out` (at element c * ld_out) is the trace column at element c * ld_trace of `trace`, rows elements, then `extra` randomizer
+// values: element rows + r is Field.sample (fe_sample_bytes) of the `width` bytes at draws + m * draws_stride + (r * registers + s) *
+// width -- the reference's draw order, row by row, register by register.  Grid (position blocks) x (columns, `col0` on in a launch
+// that is not the first); one thread per output element.  rows == 0: nothing is read from `trace` (it may be null), and with
+// registers == 1 the call samples one polynomial of `extra` coefficients per member.
+struct RandomizedCols {
+    const Fe* trace; uint64_t rows, ld_trace;
+    uint64_t registers;
+    const uint8_t* draws; uint64_t draws_stride;
+    uint64_t extra; uint32_t width;
+    Fe* out; uint64_t ld_out;
+    uint64_t col0;
+};
+SC_HD void randomized_cols_thread(const RandomizedCols& D, uint32_t wg_x, uint32_t wg_y, uint32_t tid) {
+    const uint64_t i = (uint64_t)wg_x * COLS_WG + tid;
+    if (i >= D.rows + D.extra) return;
+    const uint64_t c = D.col0 + wg_y;
+    Fe v;
+    if (i < D.rows) {
+        v = D.trace[c * D.ld_trace + i];
+    } else {
+        const uint64_t m = c / D.registers, s = c - m * D.registers, r = i - D.rows;
+        v = fe_sample_bytes(D.draws + m * D.draws_stride + (r * D.registers + s) * D.width, D.width);
+    }
+    D.out[c * D.ld_out + i] = v;
+}
+
 // rows of a grid (pairs of mpoly_eval_columns_kernel, columns of scale_cols_kernel) per launch: gridDim.y takes 65 535
 constexpr uint32_t COLS_GRID_ROWS = 65535;
 

@@ -43,6 +43,11 @@ __global__ void __launch_bounds__(256) scale_cols_kernel(const Fe* in, uint64_t 
     scale_cols_thread(in, ld_in, out, ld_out, n, lo, hi, blockIdx.y, (uint64_t)blockIdx.x * COLS_WG + threadIdx.x);
 }
 
+// grid (position blocks) x (columns of the batch): one thread per element of the randomized trace matrix
+__global__ void __launch_bounds__(256) randomized_cols_kernel(const RandomizedCols D) {
+    randomized_cols_thread(D, blockIdx.x, blockIdx.y, threadIdx.x);
+}
+
 // one wave: the per-column words -> the words of one pinned slot, published like divide_flags_publish_kernel
 __global__ void __launch_bounds__(64) columns_verdict_kernel(const uint32_t* __restrict__ zero, const long long* __restrict__ rem, uint64_t cols,
                                                             volatile uint64_t* host, uint64_t seq) {
@@ -341,5 +346,46 @@ int sc_scale_columns_dev(const void* d_in, uint64_t ld_in, void* d_out, uint64_t
                            (Fe*)d_out + done * ld_out, ld_out, n, (const Fe*)pw->lo, (const Fe*)pw->hi);
         HIPCHK(hipGetLastError());
     }
+    return SC_OK;
+}
+
+// the randomized trace matrix of a batch of proofs: every member's trace columns with the randomizer rows sampled behind them
+int sc_randomized_columns_dev(const void* d_trace, uint64_t rows, uint64_t ld_trace, uint64_t members, uint64_t registers, const void* draws, uint64_t draws_stride,
+                              uint64_t extra, uint32_t width, void* d_out, uint64_t ld_out, void* stream) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    if (members == 0 || registers == 0 || (rows == 0 && extra == 0)) return SC_OK;
+    if (width == 0 || width > 32) return fail(SC_ERR_BAD_ARG, "byte strings of 1..32 bytes expected");
+    if (rows + extra < rows || ld_out < rows + extra || ld_trace < rows) return fail(SC_ERR_BAD_ARG, "a column stride below the column length");
+    if (!d_out || (rows && !d_trace) || (extra && !draws)) return fail(SC_ERR_BAD_ARG, "null argument");
+    if (members > (1ull << 32) / registers || extra > (1ull << 40) / (registers * width)) return fail(SC_ERR_BAD_ARG, "more than 2^32 columns or 2^40 bytes of draws per member");
+    const uint64_t block = extra * registers * width, cols = members * registers, n = rows + extra;
+    if (members > 1 && draws_stride < block) return fail(SC_ERR_BAD_ARG, "the members' draws overlap");
+    if (rows) {
+        const uintptr_t out_lo = (uintptr_t)d_out, out_hi = out_lo + ((cols - 1) * ld_out + n) * sizeof(Fe);
+        const uintptr_t lo = (uintptr_t)d_trace, hi = lo + ((cols - 1) * ld_trace + rows) * sizeof(Fe);
+        if (lo < out_hi && out_lo < hi) return fail(SC_ERR_BAD_ARG, "the output may not overlap the trace");
+    }
+    hipStream_t st = pick_stream(stream);
+    // the draws as the kernel reads them: the members' blocks one behind the other (pooled scratch, like sc_sample_bytes_dev)
+    void* buf = nullptr;
+    std::vector<uint8_t> packed;
+    if (block) {
+        SCCHK(scratch(6, members * block + 256, &buf));
+        const uint8_t* src = (const uint8_t*)draws;
+        if (members > 1 && draws_stride != block) {
+            packed.resize(members * block);
+            for (uint64_t m = 0; m < members; ++m) memcpy(packed.data() + m * block, src + m * draws_stride, block);
+            src = packed.data();
+        }
+        SCCHK(upload(buf, src, members * block, st));
+    }
+    for (uint64_t done = 0; done < cols; done += COLS_GRID_ROWS) {
+        const uint64_t k = cols - done < COLS_GRID_ROWS ? cols - done : COLS_GRID_ROWS;
+        const RandomizedCols D{(const Fe*)d_trace, rows, ld_trace, registers, (const uint8_t*)buf, block, extra, width, (Fe*)d_out, ld_out, done};
+        hipLaunchKernelGGL(randomized_cols_kernel, dim3((unsigned)((n + COLS_WG - 1) / COLS_WG), (unsigned)k), dim3(COLS_WG), 0, st, D);
+        HIPCHK(hipGetLastError());
+    }
+    if (block) HIPCHK(hipStreamSynchronize(st));    // `draws` is the caller's host memory
     return SC_OK;
 }

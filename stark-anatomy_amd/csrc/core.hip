@@ -373,21 +373,12 @@ __global__ void __launch_bounds__(256) field_selftest2_kernel(int op, const Fe* 
     word[i] = flags;
 }
 
-// Field.sample (code/algebra.py:116-120) of `count` byte strings of `width` <= 32 bytes each: the big-endian integer mod p.
-// value = hi * 2^128 + lo with hi, lo < 2^128 < 2p: one conditional subtraction each, hi * 2^128 = to_mont(hi).
+// Field.sample (code/algebra.py:116-120) of `count` byte strings of `width` <= 32 bytes each: the big-endian integer mod p
+// (fe_sample_bytes of field.cuh, which randomized_cols_kernel of columns.hip shares)
 __global__ void __launch_bounds__(256) sample_bytes_kernel(const uint8_t* __restrict__ bytes, uint64_t count, uint32_t width, Fe* __restrict__ out) {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
-    const uint8_t* b = bytes + i * width;
-    uint64_t w[4] = {0, 0, 0, 0};                      // little-endian 64-bit words of the integer
-    for (uint32_t k = 0; k < width; ++k) {
-        const uint32_t pos = width - 1 - k;            // byte k has weight 256^pos
-        w[pos >> 3] |= (uint64_t)b[k] << (8 * (pos & 7));
-    }
-    Fe lo{w[0], w[1]}, hi{w[2], w[3]};
-    if (fe_ge_p(lo)) lo = fe_sub(lo, Fe{P_LO, P_HI});
-    if (fe_ge_p(hi)) hi = fe_sub(hi, Fe{P_LO, P_HI});
-    out[i] = fe_add(lo, to_mont(hi));
+    out[i] = fe_sample_bytes(bytes + i * width, width);
 }
 
 __global__ void __launch_bounds__(256) gather_kernel(const Fe* __restrict__ v, const uint64_t* __restrict__ idx, uint64_t k, Fe* __restrict__ out) {

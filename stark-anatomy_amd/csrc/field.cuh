@@ -344,4 +344,24 @@ SC_HD void fe_addsub2_fast(Fe u0, Fe v0, Fe u1, Fe v1, Fe& s0, Fe& d0, Fe& s1, F
     s1 = fe_add_fast(u1, v1, rare); d1 = fe_sub_fast(u1, v1, rare);
 #endif
 }
+
+// Field.sample (code/algebra.py:116-120) of one byte string of `width` <= 32 bytes: the big-endian integer mod p.
+// value = hi * 2^128 + lo with hi, lo < 2^128 < 2p: one conditional subtraction each, hi * 2^128 = to_mont(hi).  The four words
+// are named, not indexed: a word picked by a run-time index would put the array into scratch memory.
+SC_HD Fe fe_sample_bytes(const uint8_t* b, uint32_t width) {
+    uint64_t w0 = 0, w1 = 0, w2 = 0, w3 = 0;           // little-endian 64-bit words of the integer
+    for (uint32_t k = 0; k < width; ++k) {
+        const uint32_t pos = width - 1 - k;            // byte k has weight 256^pos
+        const uint64_t v = (uint64_t)b[k] << (8 * (pos & 7));
+        const uint32_t word = pos >> 3;
+        w0 |= word == 0 ? v : 0;
+        w1 |= word == 1 ? v : 0;
+        w2 |= word == 2 ? v : 0;
+        w3 |= word == 3 ? v : 0;
+    }
+    Fe lo{w0, w1}, hi{w2, w3};
+    if (fe_ge_p(lo)) lo = fe_sub(lo, Fe{P_LO, P_HI});
+    if (fe_ge_p(hi)) hi = fe_sub(hi, Fe{P_LO, P_HI});
+    return fe_add(lo, to_mont(hi));
+}
 }  // namespace sc

@@ -7,7 +7,7 @@ prefixed by the document's BLAKE2s digest.  With the same os.urandom the signatu
 
 Added: `sign` computes the trace and the public output with one launch of the Rescue-Prime kernel (RescuePrime.trace_device);
 `keygen_batch` / `keygen_batch_device` make many key pairs with one hash launch; `verify_batch` checks many signatures with one
-FastStark.verify_batch call.
+FastStark.verify_batch call; `sign_batch` / `stark_prove_batch` make many signatures with one FastStark.prove_batch call.
 """
 import os
 import pickle
@@ -104,6 +104,34 @@ class FastRPSSS:
             return self.stark_prove(sk, sps)
         trace = self.rp.trace_device(sk)
         return self._prove(trace, trace.entry(self.rp.N, 0), sps)
+
+    def sign_batch(self, sks, documents):
+        """[self.sign(sk, document) for ...] -- the same signatures under the same os.urandom -- with one launch of the Rescue-Prime
+        kernel for all traces, one gather of the public outputs and one FastStark.prove_batch"""
+        sks, documents = list(sks), list(documents)
+        assert len(sks) == len(documents), "one document per secret key"
+        return self.stark_prove_batch(sks, [SignatureProofStream(document) for document in documents])
+
+    def stark_prove_batch(self, input_elements, proof_streams):
+        """the proofs of sign_batch on the caller's proof streams, one per input element"""
+        import starkcore as sc
+        from algebra import FieldElement
+        from fast_stark import DeviceTrace
+        input_elements, proof_streams = list(input_elements), list(proof_streams)
+        assert len(input_elements) == len(proof_streams), "one proof stream per input element"
+        if not input_elements:
+            return []
+        rows, m = self.rp.N + 1, self.rp.m
+        # register s of input k's trace is column (m k + s) of one matrix: prove_batch reads the traces where they lie
+        whole = self.rp.trace_batch_device(sc.DeviceVector.from_bytes(sc.pack([e.value % self.rp.p for e in input_elements])))
+        base = whole.ptr
+        traces = [DeviceTrace([sc.DeviceVector.wrap(base + 16 * rows * (m * k + s), rows, whole) for s in range(m)], self.field)
+                  for k in range(len(input_elements))]
+        outputs = whole.gather([rows * m * k + self.rp.N for k in range(len(input_elements))])      # register 0 at cycle N
+        transition_constraints = self.rp.transition_constraints(self.stark.omicron)
+        boundaries = [self.rp.boundary_constraints(FieldElement(v, self.field)) for v in outputs]
+        return self.stark.prove_batch(traces, transition_constraints, boundaries, self.transition_zerofier, self.transition_zerofier_codeword,
+                                      proof_streams)
 
     def verify(self, pk, document, signature):
         sps = SignatureProofStream(document)

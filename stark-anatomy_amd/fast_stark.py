@@ -104,6 +104,15 @@ def _collect_verdicts(pending):
                 pass
 
 
+def _drop_verdicts(pending):
+    """wait for collected checks nobody will read any more (something else has failed), their verdicts dropped"""
+    for verdict in pending:
+        try:
+            verdict()
+        except Exception:                      # noqa: BLE001
+            pass
+
+
 def device_powers(base, count):
     """base^i, i < count, as a DeviceVector (Polynomial.scale of the all-ones vector: no host loop)"""
     ones = DeviceVector.from_bytes((1).to_bytes(16, "little") * count)
@@ -448,6 +457,192 @@ class FastStark:
         proof = proof_stream.serialize()
         self._mark("proof serialization (host pickle)")
         return proof
+
+    # -- batched prover ----------------------------------------------------------------------------
+    def _batch_served(self, traces, boundaries):
+        """does prove_batch serve this batch with the members' work done together?  Decided from shapes alone, before any draw:
+        the main field, traces of one length (long enough for the device data flow) and of one column per register, boundaries that
+        name the same (cycle, register) pairs, an FRI shape the forest path serves, and a member's codewords within one forest"""
+        if self.field.p != Field.P_MAIN:
+            return False
+        rows = len(traces[0])
+        if any(len(trace) != rows for trace in traces) or rows < 1 or rows + self.num_randomizers < FastStark.DEVICE_MIN:
+            return False
+        for trace in traces:
+            if isinstance(trace, DeviceTrace):
+                if len(trace.columns) != self.num_registers or trace.field.p != Field.P_MAIN:
+                    return False
+            elif any(len(row) != self.num_registers for row in trace):
+                return False
+        layout = [(cycle, register) for cycle, register, _ in boundaries[0]]
+        if any([(cycle, register) for cycle, register, _ in boundary] != layout for boundary in boundaries):
+            return False
+        if self.num_registers * self.fri_domain_length > _sc.FOREST_MAX_LEAVES:
+            return False
+        return self.fri._batchable([])
+
+    def prove_batch(self, traces, transition_constraints, boundaries, transition_zerofier, transition_zerofier_codeword, proof_streams=None):
+        """[self.prove(traces[m], transition_constraints, boundaries[m], transition_zerofier, transition_zerofier_codeword,
+        proof_streams[m]) for m ...] -- byte for byte under the same os.urandom, and afterwards every stream holds exactly the objects
+        `prove` would have pushed -- with the members' work on the device done together: the randomized traces of all members are the
+        K R columns of one matrix (sc_randomized_columns_dev: one launch copies the traces and samples the randomizer rows), and
+        interpolation, the boundary quotients, the LDEs, the AIR, the nonlinear combination and FRI are one call each for all members
+        (fast_interpolate_columns_device, combine_columns_device, coset_divide_columns_device, transition_quotients_batch,
+        Fri.prove_batch with AlsoOpenForests); every commitment is a Merkle forest.  traces[m]: a DeviceTrace or the reference's list of
+        rows; proof_streams None: fresh ProofStreams.  The draws are made first, in the order of K sequential `prove` calls (per member
+        num_randomizers * num_registers draws for the randomizer rows, then max_degree + 1 for the randomizer polynomial); with the
+        operating system's os.urandom they are ONE os.urandom call.  A batch whose shape is not served (_batch_served) goes member by
+        member through `prove`, before any draw.  A false witness raises what `prove` raises for the lowest-numbered failing member; no
+        proofs are returned, and every stream then holds a prefix of what `prove` would have pushed.  COLUMN_BATCH_MIN is not consulted:
+        K R columns always form a matrix."""
+        traces, boundaries = list(traces), list(boundaries)
+        proof_streams = [None] * len(traces) if proof_streams is None else list(proof_streams)
+        assert(len(traces) == len(boundaries) == len(proof_streams)), "prove_batch needs one boundary and one proof stream per trace"
+        if not traces:
+            return []
+        proof_streams = [ProofStream() if stream is None else stream for stream in proof_streams]
+        if not self._batch_served(traces, boundaries):
+            return [self.prove(trace, transition_constraints, boundary, transition_zerofier, transition_zerofier_codeword, stream)
+                    for trace, boundary, stream in zip(traces, boundaries, proof_streams)]
+        K, R = len(traces), self.num_registers
+        for_rows, for_polynomial = self.num_randomizers * R, self.max_degree(transition_constraints) + 1
+        block = 17 * (for_rows + for_polynomial)
+        if os_urandom_is_genuine():
+            raw = os.urandom(K * block)
+        else:
+            raw = b"".join(draw_random_bytes(for_rows) + draw_random_bytes(for_polynomial) for _ in range(K))
+        draws = (ctypes.c_char * (K * block)).from_buffer_copy(raw)
+        step = max(1, _sc.FOREST_MAX_LEAVES // (R * self.fri_domain_length))
+        proofs = []
+        for lo in range(0, K, step):
+            proofs += self._prove_chunk(traces[lo:lo + step], transition_constraints, boundaries[lo:lo + step], transition_zerofier,
+                                        transition_zerofier_codeword, proof_streams[lo:lo + step], ctypes.addressof(draws) + lo * block, block)
+        return proofs
+
+    def _trace_matrix(self, traces, rows):
+        """the traces of a chunk as one device matrix of K R columns: (holder of the device pointer, column pitch in elements).
+        DeviceTraces whose columns already are equally spaced rows of one matrix (RescuePrime.trace_batch_device's output) are used where
+        they lie; other DeviceTraces are copied into one matrix; host rows are packed and uploaded once."""
+        R, lib = self.num_registers, _sc.lib()
+        if all(isinstance(trace, DeviceTrace) for trace in traces):
+            vectors = [column for trace in traces for column in trace.columns]
+            places = [v.ptr for v in vectors]
+            pitch = places[1] - places[0] if len(places) > 1 else 16 * rows
+            if pitch >= 16 * rows and pitch % 16 == 0 and all(b - a == pitch for a, b in zip(places, places[1:])):
+                return vectors[0], pitch // 16
+        value = lambda x: int(getattr(x, "value", x))
+        if not any(isinstance(trace, DeviceTrace) for trace in traces):
+            return DeviceVector.from_bytes(b"".join(_sc.pack([value(row[s]) for row in trace]) for trace in traces for s in range(R))), rows
+        matrix = DeviceVector(len(traces) * R * rows)
+        for m, trace in enumerate(traces):
+            if isinstance(trace, DeviceTrace):
+                for s, column in enumerate(trace.columns):
+                    _sc._check(lib.sc_memcpy_dev(matrix.ptr + 16 * rows * (m * R + s), column.ptr, rows, None))
+            else:
+                _sc._check(lib.sc_vec_upload(matrix._h, rows * m * R, b"".join(_sc.pack([value(row[s]) for row in trace]) for s in range(R)), rows * R))
+        return matrix, rows
+
+    def _zerofier_forest(self, codeword):
+        """the count-1 Merkle forest over the transition zerofier's codeword (its root is Merkle.commit's), built once per codeword object"""
+        kept = getattr(self, "_zerofier_forest_kept", None)
+        if kept is None or kept[0] is not codeword:
+            kept = self._zerofier_forest_kept = (codeword, _sc.MerkleForest.build(_sc.CodewordMatrix.from_members([codeword])))
+        return kept[1]
+
+    def _prove_chunk(self, traces, transition_constraints, boundaries, transition_zerofier, transition_zerofier_codeword, streams, draws, draws_stride):
+        """prove_batch for members that share every forest.  draws: address of the first member's block of draws (host memory)"""
+        field, lib, K, R = self.field, _sc.lib(), len(traces), self.num_registers
+        rows, extra = len(traces[0]), self.num_randomizers
+        trace_rows, cols, N = rows + extra, K * R, self.fri_domain_length
+        max_degree = self.max_degree(transition_constraints)
+        self._mark(None)
+        pending = []
+        try:
+            # the randomized traces of all members as one matrix [K R][trace_rows], the randomizer polynomials as one [K][max_degree + 1]
+            source, ld_trace = self._trace_matrix(traces, rows)
+            randomized = DeviceVector(cols * trace_rows)
+            _sc._check(lib.sc_randomized_columns_dev(source.ptr, rows, ld_trace, K, R, draws, draws_stride, extra, 17, randomized.ptr, trace_rows, None))
+            sampled = DeviceVector(K * (max_degree + 1))
+            _sc._check(lib.sc_randomized_columns_dev(None, 0, 0, K, 1, draws + 17 * extra * R, draws_stride, max_degree + 1, 17, sampled.ptr, max_degree + 1, None))
+            randomizer_polynomials = [DevicePolynomial(DeviceVector.wrap(sampled.ptr + 16 * (max_degree + 1) * m, max_degree + 1, sampled), field, max_degree + 1)
+                                      for m in range(K)]
+            columns = [DeviceCodeword(DeviceVector.wrap(randomized.ptr + 16 * trace_rows * c, trace_rows, randomized), field) for c in range(cols)]
+            trace_polynomials = [DevicePolynomial.from_codeword(c) for c in fast_interpolate_columns_device(self._trace_domain(trace_rows), columns)]
+            DevicePolynomial.degrees(trace_polynomials)
+            self._mark("trace interpolation")
+
+            # boundary quotients of all K R columns: one combination, one columns-form division, one verdict
+            interpolants = [interpolant for boundary in boundaries for interpolant in self.boundary_interpolants(boundary)]
+            zerofiers = self.boundary_zerofiers(boundaries[0])
+            boundary_quotients = self._boundary_quotients_columns(trace_polynomials, interpolants, zerofiers * K, pending)
+            if boundary_quotients is None:
+                zerofiers_dev = [DevicePolynomial.from_polynomial(z, field) for z in zerofiers]
+                boundary_quotients = [coset_divide_device(trace_polynomials[c].minus(interpolants[c]), zerofiers_dev[c % R], self.generator, self.omicron,
+                                                          self.omicron_domain_length, exact=True, later=pending) for c in range(cols)]
+            self._mark("boundary quotients (division)")
+
+            # commitments: one forest over the K R boundary-quotient codewords, one over the K randomizer codewords, the zerofier's own
+            bq_forest = _sc.MerkleForest.build(self._lde_matrix(boundary_quotients))
+            self._mark("boundary quotient LDEs + commitments")
+            x = DevicePolynomial.from_polynomial(Polynomial([field.zero(), field.one()]), field)
+            points = [[x] + trace_polynomials[m * R:(m + 1) * R] + [tp.scaled_later(self.omicron) for tp in trace_polynomials[m * R:(m + 1) * R]] for m in range(K)]
+            transition_quotients = self.transition_quotients_batch(transition_constraints, points, transition_zerofier, pending)
+            self._mark("AIR substitution + transition quotients (value domain)")
+            randomizer_forest = _sc.MerkleForest.build(self._lde_matrix(randomizer_polynomials))
+            zerofier_forest = self._zerofier_forest(transition_zerofier_codeword)
+            self._mark("randomizer polynomial: LDE, commitment")
+
+            # per member: the commitments, the collected checks (once: they speak for the whole chunk), the weights, the degree check
+            tq_bounds = self.transition_quotient_degree_bounds(transition_constraints)
+            bq_bounds = self.boundary_quotient_degree_bounds(trace_rows, boundaries[0])
+            bq_roots, randomizer_roots = bq_forest.roots, randomizer_forest.roots
+            weights = []
+            for m, stream in enumerate(streams):
+                for s in range(R):
+                    stream.push(bq_roots[m * R + s])
+                stream.push(randomizer_roots[m])
+                checks, pending = pending, []
+                _collect_verdicts(checks)
+                weights.append(self.sample_weights(1 + 2 * len(transition_quotients[m]) + 2 * R, stream.prover_fiat_shamir()))
+                assert([tq.degree() for tq in transition_quotients[m]] == tq_bounds), "transition quotient degrees do not match with expectation"
+        except BaseException:
+            _drop_verdicts(pending)                      # no check is left unread: none keeps its pinned slot
+            raise
+
+        # nonlinear combination of every member in one pass: every term is a K-row matrix, the weight row is the member's
+        terms = [(randomizer_polynomials, None)]
+        for i in range(len(transition_constraints)):
+            terms.append(([transition_quotients[m][i] for m in range(K)], max_degree - tq_bounds[i]))
+        for s in range(R):
+            terms.append(([boundary_quotients[m * R + s] for m in range(K)], max_degree - bq_bounds[s]))
+        width = max(max_degree + 1, max(len(p) + (shift or 0) for polynomials, shift in terms for p in polynomials))
+        combined = self._lde_matrix(combine_columns_device(terms, weights, width))
+        combined_codewords = [DeviceCodeword(DeviceVector.wrap(combined.vec.ptr + 16 * N * m, N, combined.vec), field) for m in range(K)]
+        self._mark("weights, degree checks, nonlinear combination + its LDE")
+
+        # FRI on all members; the committed codewords' openings travel in the launch that fetches the FRI openings
+        owners = [[list(range(m * R, (m + 1) * R)) for m in range(K)], [[m] for m in range(K)], [[0] for _ in range(K)]]
+        also = AlsoOpenForests([bq_forest, randomizer_forest, zerofier_forest], owners, shift=self.expansion_factor)
+        self.fri.prove_batch(combined_codewords, streams, also_open=also)
+        self._mark("FRI: commit + query phases, openings fetched with them")
+
+        # openings in `committed` order; entries are made once per (member, codeword, index): the transcript is pickled by object identity
+        proofs = []
+        shared_elements = None if isinstance(transition_zerofier_codeword, DeviceCodeword) else list(transition_zerofier_codeword)
+        for m, stream in enumerate(streams):
+            holders = [DeviceCodeword(None, field) for _ in range(R + 1)] + [DeviceCodeword(None, field, elements=shared_elements)]
+            for holder, (values, paths) in zip(holders, also.answers[m]):
+                self._push_openings(holder._entries(also.positions[m], values), paths, stream)
+        self._mark("openings of the committed codewords")
+        for stream in streams:
+            proofs.append(stream.serialize())
+        self._mark("proof serialization (host pickle)")
+        return proofs
+
+    def _lde_matrix(self, polynomials):
+        """the codewords of _lde_columns as the rows of one CodewordMatrix (no copy: what a MerkleForest is built over)"""
+        codewords = self._lde_columns(polynomials)
+        return _sc.CodewordMatrix(len(codewords), self.fri_domain_length, codewords[0].vec._keep)
 
     def _lde_columns(self, polynomials):
         """[p.coset_evaluate(generator, omega, fri_domain_length) for p in polynomials] as one call: the coefficient vectors are

@@ -49,6 +49,7 @@ SIGNATURES = {
     "sc_vec_gather": (_int, [_vp, _vp, _u64, _vp]),
     "sc_memcpy_dev": (_int, [_vp, _vp, _u64, _vp]),
     "sc_sample_bytes_dev": (_int, [_vp, _u64, ctypes.c_uint32, _vp, _vp]),
+    "sc_randomized_columns_dev": (_int, [_vp, _u64, _u64, _u64, _u64, _vp, _u64, _u64, ctypes.c_uint32, _vp, _u64, _vp]),
     "sc_sample_urandom_dev": (_int, [_u64, ctypes.c_uint32, _vp, _vp]),
     "sc_urandom_prefetch": (_int, [_u64, ctypes.c_uint32]),
     "sc_rescue_prime_hash_dev": (_int, [_vp, _u64, _vp, _u64, _vp, _vp]),
