@@ -62,7 +62,7 @@ int sc_stream(void** stream_out);
 int sc_stream_join(void* other_stream);
 /* tuning knobs for experiments (defaults are the measured optimum; -1 = choose by size where applicable): key in
  * {"max_tile_log","loge","max_col_log","min_tiles_log","single_pass_max_log","max_digit_log","direct_tw_max_log",
- *  "xcd_remap","fixed_shapes","merkle_big_nlev","wave_local","prio_balance","loge_cols","tw_on_load","prune","fast_fixups","fri_tail","fri_tail_stall","small_divisor_direct","verify_stage_kb","forest_four_lane_wgs","div_cols_chunk","div_cols_launch_log"}.  Plans are re-derived on the next
+ *  "xcd_remap","fixed_shapes","merkle_big_nlev","wave_local","prio_balance","loge_cols","tw_on_load","prune","fast_fixups","fri_tail","fri_tail_stall","small_divisor_direct","verify_stage_kb","forest_four_lane_wgs","div_cols_chunk","div_cols_launch_log","tree_cols_launch_log"}.  Plans are re-derived on the next
  * call; results never depend on the tuning ("fri_tail_stall" = k >= 0 is a test hook: the host withholds the challenge after round k of
  * the persistent tail kernel, whose wait then gives up after 2^13 polls; -1 = off; "small_divisor_direct" = 0: sc_coset_divide* transforms a
  * divisor of <= 8 coefficients like any other instead of evaluating it point by point; "verify_stage_kb" = the size of the staging buffer
@@ -72,7 +72,9 @@ int sc_stream_join(void* other_stream);
  * kernels on every tile (a test hook) -- see sc_ntt_columns_dev; "div_cols_chunk" = columns that share one batch inversion in
  * sc_pointwise_div_columns_later_dev / sc_coset_divide_columns_later_dev with a shared divisor, 0 = chosen by shape; "div_cols_launch_log" = log2 of the values
  * one set of launches of sc_coset_divide_columns_later_dev takes, 26 by default and at most, at least 1: a test hook that makes the entry
- * work through a small matrix in several chunks of columns).  Two keys manage the device-memory pool instead (freed vectors and trees are kept
+ * work through a small matrix in several chunks of columns; "tree_cols_launch_log" = log2 of the elements one temporary of a set of columns of
+ * sc_polytree_evaluate_columns_dev / sc_polytree_interpolate_columns_dev holds, 26 by default and at most, at least 1: a test hook that
+ * makes those entries work through their columns in several sets).  Two keys manage the device-memory pool instead (freed vectors and trees are kept
  * on exact-size free lists, by default up to a quarter of the device's memory divided by the processes sharing the device;
  * environment STARKCORE_POOL_CAP_MB): "pool_cap_mb" = what the lists may keep from now on, "pool_trim" = hand everything on them
  * back to the device now (a caller whose own allocator -- torch's -- ran out of memory). */
@@ -314,6 +316,20 @@ int sc_polytree_zerofier_dev(const sc_polytree_t* tree, void* d_out, void* strea
 /* d_points: the tree's points again, only read when m exceeds the padded domain size (chunked evaluation); may be NULL otherwise */
 int sc_polytree_evaluate_dev(sc_polytree_t* tree, const void* d_coeffs, uint64_t m, const void* d_points, void* d_out, void* stream);
 int sc_polytree_interpolate_dev(sc_polytree_t* tree, const void* d_values, void* d_out, void* stream);
+/* The same two for `cols` polynomials in one call: column c's m coefficients (k values) start at element c * ld_in of the input, its
+ * k results go to element c * ld_out of d_out; elements between a column's end and the next pitch are neither read nor written.  m
+ * is common to the call (shorter polynomials are zero-padded by the caller; m == 0 gives zeros).  The results are those of `cols`
+ * calls of the single entries, bit for bit.  A set of C' = 2^j columns goes through the tree with the column index innermost (a level
+ * is [2^l][K >> l][C'], K the power of two >= k), so every step -- the batched transforms of a level, the elementwise kernels -- is
+ * issued once per set; a set's temporaries hold 2K * C' elements, at most 2^26 (sc_set_tuning "tree_cols_launch_log"); more columns go set
+ * after set, a last set of fewer columns is padded to the next power of two with lanes of zeros that are never stored.  Interpolation
+ * keeps 1 / Z'(d_i) in the tree (built by the first call, which waits for it: a repeated point is SC_ERR_DIV_ZERO "divide by zero", and
+ * nothing is kept); evaluation builds the tree's inverse series on first use as the single entry does.  Apart from those first-use
+ * builds the calls only ENQUEUE on `stream`: results are valid in stream order, temporaries are returned behind the stream.
+ * d_points is read only when m > K (NULL there: SC_ERR_BAD_ARG).  cols == 0: SC_OK, nothing enqueued; with cols > 1 a pitch below the
+ * column's length (ld_in < m, ld_in < k, ld_out < k): SC_ERR_BAD_ARG.  d_out may NOT overlap the input. */
+int sc_polytree_evaluate_columns_dev(sc_polytree_t* tree, const void* d_coeffs, uint64_t m, uint64_t ld_in, uint64_t cols, const void* d_points, void* d_out, uint64_t ld_out, void* stream);
+int sc_polytree_interpolate_columns_dev(sc_polytree_t* tree, const void* d_values, uint64_t ld_in, uint64_t cols, void* d_out, uint64_t ld_out, void* stream);
 int sc_polytree_free(sc_polytree_t* tree);
 
 /* ---- the same three functions on a GEOMETRIC PROGRESSION  x_i = first * ratio^i, i < n : code/ntt.py:66-130 as called by
@@ -336,6 +352,12 @@ int sc_geodomain_interpolate_dev(const sc_geodomain_t* domain, const void* d_val
  * issued once for all columns (once per set of at most 2^26 / M and at most 65 536 columns, M the power of two >= 2n - 1).
  * d_out may NOT overlap d_values.  cols == 0: SC_OK, nothing enqueued; a null pointer or a stride below n: SC_ERR_BAD_ARG, nothing enqueued. */
 int sc_geodomain_interpolate_columns_dev(const sc_geodomain_t* domain, const void* d_values, uint64_t ld_in, uint64_t cols, void* d_out, uint64_t ld_out, void* stream);
+/* Multipoint evaluation for `cols` polynomials of m coefficients each (any m; m == 0 gives zeros): column c's coefficients at element
+ * c * ld_in of d_coeffs, its n values to element c * ld_out of d_out, those of sc_geodomain_evaluate_dev bit for bit.  The two transforms
+ * and three elementwise kernels of an evaluation are issued once per set of columns (sets as above); m > n runs the same Horner over
+ * chunks of n coefficients with the chunk powers shared by the columns.  Only enqueues.  cols == 0: SC_OK; with cols > 1, ld_in < m or
+ * ld_out < n: SC_ERR_BAD_ARG.  d_out may NOT overlap d_coeffs. */
+int sc_geodomain_evaluate_columns_dev(const sc_geodomain_t* domain, const void* d_coeffs, uint64_t m, uint64_t ld_in, uint64_t cols, void* d_out, uint64_t ld_out, void* stream);
 int sc_geodomain_free(sc_geodomain_t* domain);
 
 /* ---- MPolynomial.evaluate_symbolic in the value domain : code/multivariate.py:83-90 (call site fast_stark.py:109-110) ---- */

@@ -128,6 +128,7 @@ struct Ctx {
     bool foreign_streams = false;   // a caller-owned stream has been used (see pick_stream)
     int small_divisor_direct = 1;    // coset_divide_core evaluates a divisor of <= 8 coefficients point by point instead of transforming it (sc_set_tuning("small_divisor_direct", 0): A/B and tests)
     int div_cols_launch_log = 26;    // sc_coset_divide_columns_later_dev: log2 of the values one set of launches takes (COLS_ELEMS_PER_LAUNCH); smaller: a test hook for the chunk loop
+    int tree_cols_launch_log = 26;   // sc_polytree_*_columns_dev: log2 of the elements one temporary of a set of columns holds (COLS_ELEMS_PER_LAUNCH); smaller: a test hook for the set loop
     int div_cols_chunk = 0;          // columns that share one batch inversion in pointwise_div_cols_kernel; 0: chosen by shape (columns.hip div_cols_chunk_for)
     std::vector<hipStream_t> seen_streams;   // those streams, most recent last (at most SEEN_STREAMS; more: device-wide waits)
     DevBuf scratch[8];       // 0: ntt work, 1..3: poly temporaries, 4: misc small, 5: merkle staging, 6: uploaded operands, 7: degree / exactness flag

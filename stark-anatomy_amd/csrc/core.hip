@@ -1058,6 +1058,7 @@ int sc_set_tuning(const char* key, int value) {
     else if (k == "small_divisor_direct") g.small_divisor_direct = value ? 1 : 0;
     else if (k == "div_cols_chunk") g.div_cols_chunk = value < 0 ? 0 : (value > 65535 ? 65535 : value);      // columns per workgroup row of pointwise_div_cols_kernel, 0 = by shape (csrc/columns.hip)
     else if (k == "div_cols_launch_log") g.div_cols_launch_log = value < 1 ? 1 : (value > 26 ? 26 : value);        // tests only: more chunks per call, never larger ones (csrc/columns.hip)
+    else if (k == "tree_cols_launch_log") g.tree_cols_launch_log = value < 1 ? 1 : (value > 26 ? 26 : value);      // tests only: more sets per call, never larger ones (csrc/polytree_geo.hip)
     else if (k == "verify_stage_kb") g.verify_stage_bytes = (size_t)(value < 16 ? 16 : value) << 10;           // (a chunk must hold one row of any depth)
     else if (k == "fri_tail_stall") g.fri_tail_stall = value;                               // tests only: see core.h
     else if (k == "pool_cap_mb") g_pool_cap = (size_t)(value < 0 ? 0 : value) << 20;       // what the free lists may keep from now on

@@ -186,6 +186,37 @@ __global__ void __launch_bounds__(256) geo_rev_scale_cols_kernel(const Fe* __res
     out[c * ld_out + j] = v;
 }
 
+// ---- the evaluation's steps for many columns (sc_geodomain_evaluate_columns_dev): the same flat grid; geo_corr_cols_kernel and
+// geo_mul_tab_cols_kernel above serve its correlation and its final division by t_i
+// out[c * ld_out + j] = p[c * ld_in + j] * c^j / t_j, j < m  (clo == nullptr: c = 1)
+__global__ void __launch_bounds__(256) geo_eval_in_cols_kernel(const Fe* __restrict__ p, uint64_t ld_in, uint64_t m, uint64_t total, const Fe* __restrict__ clo,
+                                                              const Fe* __restrict__ chi, const Fe* __restrict__ tinv_m, Fe* __restrict__ out, uint64_t ld_out) {
+    const uint64_t t = GS_INDEX();
+    if (t >= total) return;
+    const uint64_t c = t / m, j = t - c * m;
+    Fe v = mont_mul(p[c * ld_in + j], tinv_m[j]);
+    if (clo) v = mont_mul(v, pow2level(clo, chi, j));
+    out[c * ld_out + j] = v;
+}
+
+// out[c * ld_out + i] = 0, i < n (a polynomial without coefficients)
+__global__ void __launch_bounds__(256) geo_zero_cols_kernel(Fe* __restrict__ out, uint64_t ld_out, uint64_t n, uint64_t total) {
+    const uint64_t t = GS_INDEX();
+    if (t >= total) return;
+    const uint64_t c = t / n;
+    out[c * ld_out + (t - c * n)] = Fe{0, 0};
+}
+
+// Horner step over chunks of n coefficients for many columns: acc[c * ld_acc + i] = acc[c * ld_acc + i] * y[i] + e[c * ld_e + i]
+__global__ void __launch_bounds__(256) geo_horner_cols_kernel(Fe* __restrict__ acc, uint64_t ld_acc, const Fe* __restrict__ y_m, const Fe* __restrict__ e, uint64_t ld_e,
+                                                             uint64_t n, uint64_t total) {
+    const uint64_t t = GS_INDEX();
+    if (t >= total) return;
+    const uint64_t c = t / n, i = t - c * n;
+    Fe* a = acc + c * ld_acc + i;
+    *a = fe_add(mont_mul(*a, y_m[i]), e[c * ld_e + i]);
+}
+
 // zerofier of {c q^i}: coefficient j = zr[n - j] * c^(n - j), j = 0..n
 __global__ void __launch_bounds__(256) geo_zerofier_out_kernel(const Fe* __restrict__ zr, uint64_t n, const Fe* __restrict__ clo, const Fe* __restrict__ chi, Fe* __restrict__ out) {
     const uint64_t j = GS_INDEX();

@@ -145,6 +145,94 @@ __global__ void __launch_bounds__(256) pt_horner_kernel(Fe* __restrict__ acc, co
     if (i < k) acc[i] = fe_add(mont_mul(acc[i], y_m[i]), e[i]);
 }
 
+// ---- MANY COLUMNS per call (sc_polytree_evaluate_columns_dev / sc_polytree_interpolate_columns_dev) ----------------------------
+// A set of C' = 2^logC columns rides through the tree with the column index INNERMOST: a level is [2^l][K >> l][C'], so the
+// transform of a level is the same batched column transform with logC more batch bits, "the first K entries" become the first
+// K * C', and every elementwise step below is its single-column kernel with one extra shift: the tree's own tables (zf, invg_f,
+// the weights) are indexed by flat >> logC, the data by flat (model: tests/emu/polytree_columns_model.py).  Column c of the
+// caller lies at pitch ld (c * ld); lanes c >= cols of a set are padding: loaded as zeros, never stored.
+
+// the transposing load of pt_rev_poly_kernel: F[t][c] = f_c[K-1-t] for t < K (0 where K-1-t >= m, and in the padding lanes), 0 above
+__global__ void __launch_bounds__(256) pt_rev_poly_cols_kernel(const Fe* __restrict__ f, uint64_t m, uint64_t ld_in, uint64_t cols, Fe* __restrict__ F, uint64_t K, int logC,
+                                                              uint64_t total) {
+    uint64_t i = PT_INDEX();
+    if (i >= total) return;
+    const uint64_t t = i >> logC, c = i & ((1ull << logC) - 1);
+    Fe v{0, 0};
+    if (t < K && K - 1 - t < m && c < cols) v = f[c * ld_in + (K - 1 - t)];
+    F[i] = v;
+}
+
+// out[t][c] = c_m2 * a[t][c] * tab[t]   (the root multiply by invg_f; out may alias a)
+__global__ void __launch_bounds__(256) pt_mul_tab_cols_kernel(const Fe* a, const Fe* __restrict__ tab, Fe* out, uint64_t total, int logC, Fe c_m2) {
+    uint64_t i = PT_INDEX();
+    if (i < total) out[i] = mont_mul(mont_mul(a[i], tab[i >> logC]), c_m2);
+}
+
+// pt_corr_kernel on [n][B][C'] / [n][2B][C']: D[f][i][c] = c_m2 * C[f][i>>1][c] * zf[(-f) mod n][i^1]
+__global__ void __launch_bounds__(256) pt_corr_cols_kernel(const Fe* __restrict__ C, const Fe* __restrict__ zf, Fe* __restrict__ D, uint64_t n, int logB2, int logC, Fe c_m2) {
+    uint64_t t = PT_INDEX();
+    if (t >= (n << (logB2 + logC))) return;
+    const uint64_t c = t & ((1ull << logC) - 1), u = t >> logC;
+    const uint64_t f = u >> logB2, i = u & ((1ull << logB2) - 1);
+    const uint64_t nf = (n - f) & (n - 1);
+    Fe a = C[(((f << (logB2 - 1)) + (i >> 1)) << logC) + c];
+    Fe b = zf[(nf << logB2) + (i ^ 1)];
+    D[t] = mont_mul(mont_mul(a, b), c_m2);
+}
+
+// [n][B][C'] -> [2n][B][C'] with plain zero padding (pt_expand_kernel with top = 0: the interpolants are not monic); half = n * B * C'
+__global__ void __launch_bounds__(256) pt_expand_cols_kernel(const Fe* __restrict__ in, Fe* __restrict__ out, uint64_t half) {
+    uint64_t i = PT_INDEX();
+    if (i >= 2 * half) return;
+    out[i] = (i < half) ? in[i] : Fe{0, 0};
+}
+
+// pt_comb_kernel: E[f][j][c] = c_m2 * (Ph[f][2j][c] * zf[f][2j+1] + Ph[f][2j+1][c] * zf[f][2j])
+__global__ void __launch_bounds__(256) pt_comb_cols_kernel(const Fe* __restrict__ Ph, const Fe* __restrict__ zf, Fe* __restrict__ E, uint64_t total_out, int logC, Fe c_m2) {
+    uint64_t i = PT_INDEX();
+    if (i >= total_out) return;
+    const uint64_t c = i & ((1ull << logC) - 1), u = i >> logC;
+    Fe pl = Ph[((2 * u) << logC) + c], pr = Ph[((2 * u + 1) << logC) + c], zl = zf[2 * u], zr = zf[2 * u + 1];
+    E[i] = mont_mul(fe_add(mont_mul(pl, zr), mont_mul(pr, zl)), c_m2);
+}
+
+// out[i] = v for i < n (the numerators of the cached weights: Montgomery ones)
+__global__ void __launch_bounds__(256) pt_fill_kernel(Fe* __restrict__ out, uint64_t n, Fe v) {
+    uint64_t i = PT_INDEX();
+    if (i < n) out[i] = v;
+}
+
+// interpolation weights, transposing load: W[i][c] = v_c[i] / Z'(d_i) for i < k (winv_m: 1 / Z'(d_i) as Montgomery forms, shared by the
+// columns), 0 on the padding leaves and in the padding lanes; total = K * C'
+__global__ void __launch_bounds__(256) pt_weights_cols_kernel(const Fe* __restrict__ values, uint64_t ld_in, uint64_t cols, const Fe* __restrict__ winv_m, uint64_t k,
+                                                             Fe* __restrict__ W, int logC, uint64_t total) {
+    uint64_t t = PT_INDEX();
+    if (t >= total) return;
+    const uint64_t i = t >> logC, c = t & ((1ull << logC) - 1);
+    Fe v{0, 0};
+    if (i < k && c < cols) v = mont_mul(values[c * ld_in + i], winv_m[i]);
+    W[t] = v;
+}
+
+// de-interleaving store: out[c * ld_out + i] = src[off + i][c], i < k, c < cols   (off = 0: the k values; off = pad: the k coefficients)
+__global__ void __launch_bounds__(256) pt_store_cols_kernel(const Fe* __restrict__ src, int logC, uint64_t off, uint64_t k, uint64_t total, Fe* __restrict__ out, uint64_t ld_out) {
+    uint64_t t = PT_INDEX();
+    if (t >= total) return;
+    const uint64_t c = t / k, i = t - c * k;
+    out[c * ld_out + i] = src[((off + i) << logC) + c];
+}
+
+// pt_horner_kernel with the de-interleaving load: acc_c[i] = acc_c[i] * y[i] + e[i][c]; the powers y_i = x_i^K are shared by the columns
+__global__ void __launch_bounds__(256) pt_horner_cols_kernel(Fe* __restrict__ acc, uint64_t ld_acc, const Fe* __restrict__ y_m, const Fe* __restrict__ e, int logC, uint64_t k,
+                                                            uint64_t total) {
+    uint64_t t = PT_INDEX();
+    if (t >= total) return;
+    const uint64_t c = t / k, i = t - c * k;
+    Fe* a = acc + c * ld_acc + i;
+    *a = fe_add(mont_mul(*a, y_m[i]), e[(i << logC) + c]);
+}
+
 #undef PT_INDEX
 
 }  // namespace sc

@@ -73,6 +73,7 @@ struct sc_polytree {
     Fe* zf;        // L levels of 2K entries: level l at zf + l*2K, [2^(l+1)][K >> l] = transforms of level l at twice its size
     Fe* invg_f;    // size-2K transform of rev(Z)^-1 mod y^K (built by the first evaluation)
     size_t zc_bytes, zf_bytes;
+    Fe* winv_m = nullptr;   // k: 1 / Z'(d_i) as Montgomery forms, Z = the zerofier of the k real points (built by the first column interpolation)
 };
 
 namespace {
@@ -245,6 +246,137 @@ int polytree_interpolate(sc_polytree* t, const Fe* d_values, Fe* d_out, hipStrea
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(d_out, cur + pad, k * sizeof(Fe), hipMemcpyDeviceToDevice, st));
     HIPCHK(hipStreamSynchronize(st));
+    return SC_OK;
+}
+
+// ---- many columns per call (the *_cols kernels of polytree.cuh): a set of C' = 2^logC columns, column index innermost ----------
+// Columns per set: 2K * C' elements per temporary within the launch budget (sc_set_tuning("tree_cols_launch_log"), 2^26 by
+// default), and no more lanes than the power of two that holds all columns
+int polytree_set_log(const sc_polytree* t, uint64_t cols) {
+    const int budget = g.tree_cols_launch_log - (t->L + 1);
+    int logC = 0;
+    while (logC < budget && (1ull << logC) < cols) ++logC;
+    return logC;
+}
+// lanes of a set that holds `nc` real columns: the power of two >= nc (the padding lanes compute on zeros and are never stored)
+inline int lanes_log(uint64_t nc) { return ilog2(nc); }
+
+// polytree_evaluate_all for nc <= 2^logC columns at pitch ld_in: the values at all K leaves are left INTERLEAVED in by[0 .. K << logC).
+// bx, by: 2K << logC entries each, tk: K << logC.
+int polytree_evaluate_all_cols(sc_polytree* t, const Fe* d_coeffs, uint64_t m, uint64_t ld_in, uint64_t nc, int logC, Fe* bx, Fe* by, Fe* tk, hipStream_t st) {
+    const uint64_t K = t->K;
+    const int L = t->L;
+    if (L == 0) {
+        hipLaunchKernelGGL(pt_rev_poly_cols_kernel, dim3(pt_blocks(K << logC)), dim3(256), 0, st, d_coeffs, m, ld_in, nc, by, K, logC, K << logC);
+        HIPCHK(hipGetLastError());
+        return SC_OK;
+    }
+    const uint64_t wide = (2 * K) << logC;
+    hipLaunchKernelGGL(pt_rev_poly_cols_kernel, dim3(pt_blocks(wide)), dim3(256), 0, st, d_coeffs, m, ld_in, nc, by, K, logC, wide);
+    SCCHK(ntt_cols(by, bx, L + 1, logC, false, st));
+    hipLaunchKernelGGL(pt_mul_tab_cols_kernel, dim3(pt_blocks(wide)), dim3(256), 0, st, (const Fe*)bx, (const Fe*)t->invg_f, bx, wide, logC, ninv_scaled(L + 1, 2));
+    SCCHK(ntt_cols(bx, by, L + 1, logC, true, st));
+    for (int l = L; l >= 1; --l) {
+        const uint64_t n = 1ull << l;
+        const int logB = L - l;
+        SCCHK(ntt_cols(by, tk, l, logB + logC, false, st));
+        hipLaunchKernelGGL(pt_corr_cols_kernel, dim3(pt_blocks(wide)), dim3(256), 0, st, (const Fe*)tk, (const Fe*)(t->zf + (uint64_t)(l - 1) * 2 * K), bx, n, logB + 1, logC,
+                           ninv_scaled(l, 2));
+        SCCHK(ntt_cols(bx, by, l, logB + 1 + logC, true, st));     // rows < n/2 = the first K << logC entries = next level's series
+    }
+    HIPCHK(hipGetLastError());
+    return SC_OK;
+}
+
+// polytree_evaluate for `cols` columns: column c's m coefficients at d_coeffs + c * ld_in, its k values to d_out + c * ld_out.  Every
+// step is issued once per set of columns; nothing waits (but the first use of a tree builds its inverse series, which does).
+int polytree_evaluate_columns(sc_polytree* t, const Fe* d_coeffs, uint64_t m, uint64_t ld_in, uint64_t cols, const Fe* d_points, Fe* d_out, uint64_t ld_out,
+                              hipStream_t st) {
+    const uint64_t K = t->K, k = t->k;
+    SCCHK(polytree_inverse_series(t, st));
+    const uint64_t per = 1ull << polytree_set_log(t, cols);
+    const int logP = ilog2(per);
+    PoolTmpAsync bx, by, tk, y;
+    SCCHK(bx.get(((2 * K) << logP) * sizeof(Fe)));
+    SCCHK(by.get(((2 * K) << logP) * sizeof(Fe)));
+    SCCHK(tk.get((K << logP) * sizeof(Fe)));
+    if (m > K) {
+        SCCHK(y.get(k * sizeof(Fe)));
+        hipLaunchKernelGGL(pt_pow2_kernel, dim3(pt_blocks(k)), dim3(256), 0, st, d_points, k, t->L, y.fe());
+    }
+    const uint64_t chunks = m > K ? (m + K - 1) / K : 1;
+    for (uint64_t done = 0; done < cols; done += per) {
+        const uint64_t nc = cols - done < per ? cols - done : per;
+        const int logC = lanes_log(nc);
+        const Fe* src = d_coeffs + done * ld_in;
+        Fe* dst = d_out + done * ld_out;
+        for (uint64_t j = chunks; j-- > 0;) {
+            const uint64_t len = (j == chunks - 1) ? m - j * K : K;
+            SCCHK(polytree_evaluate_all_cols(t, src + j * K, len, ld_in, nc, logC, bx.fe(), by.fe(), tk.fe(), st));
+            if (j == chunks - 1) hipLaunchKernelGGL(pt_store_cols_kernel, dim3(pt_blocks(k * nc)), dim3(256), 0, st, (const Fe*)by.fe(), logC, (uint64_t)0, k, k * nc, dst, ld_out);
+            else hipLaunchKernelGGL(pt_horner_cols_kernel, dim3(pt_blocks(k * nc)), dim3(256), 0, st, dst, ld_out, (const Fe*)y.fe(), (const Fe*)by.fe(), logC, k, k * nc);
+        }
+        HIPCHK(hipGetLastError());
+    }
+    return SC_OK;
+}
+
+// 1 / Z'(d_i) for the k real points, once per tree: the derivative of the zerofier at all leaves and one division of ones.  A zero
+// derivative (a repeated point) fails with what sc_polytree_interpolate_dev reports, and nothing is kept.
+int polytree_weights(sc_polytree* t, hipStream_t st) {
+    if (t->winv_m || t->L == 0) return SC_OK;
+    const uint64_t K = t->K, k = t->k;
+    PoolTmpAsync bx, by, tk, p, ones;
+    SCCHK(bx.get(2 * K * sizeof(Fe)));
+    SCCHK(by.get(2 * K * sizeof(Fe)));
+    SCCHK(tk.get(K * sizeof(Fe)));
+    SCCHK(p.get(K * sizeof(Fe)));
+    SCCHK(ones.get(k * sizeof(Fe)));
+    hipLaunchKernelGGL(pt_deriv_kernel, dim3(pt_blocks(K)), dim3(256), 0, st, (const Fe*)(t->zc + (uint64_t)t->L * K), K, K - k, k, p.fe());
+    SCCHK(polytree_evaluate_all(t, p.fe(), k, tk.fe(), bx.fe(), by.fe(), p.fe(), st));
+    hipLaunchKernelGGL(pt_fill_kernel, dim3(pt_blocks(k)), dim3(256), 0, st, ones.fe(), k, fe_mont_one());
+    HIPCHK(hipGetLastError());
+    Fe* w = nullptr;
+    HIPCHK(pool_alloc((void**)&w, k * sizeof(Fe)));
+    int rc = pointwise_div_device(ones.fe(), tk.fe(), w, k, st);     // R / Z'(d_i): the Montgomery form of the inverse; waits for the verdict
+    if (rc != SC_OK) { release_after_streams(w, k * sizeof(Fe)); return rc; }
+    t->winv_m = w;
+    return SC_OK;
+}
+
+// polytree_interpolate for `cols` columns: column c's k values at d_values + c * ld_in, its k coefficients to d_out + c * ld_out
+int polytree_interpolate_columns(sc_polytree* t, const Fe* d_values, uint64_t ld_in, uint64_t cols, Fe* d_out, uint64_t ld_out, hipStream_t st) {
+    const uint64_t K = t->K, k = t->k, pad = K - k;
+    const int L = t->L;
+    SCCHK(polytree_weights(t, st));
+    const uint64_t per = 1ull << polytree_set_log(t, cols);
+    const int logP = ilog2(per);
+    PoolTmpAsync bx, by, tk, p;
+    SCCHK(bx.get(((2 * K) << logP) * sizeof(Fe)));
+    SCCHK(by.get(((2 * K) << logP) * sizeof(Fe)));
+    SCCHK(tk.get((K << logP) * sizeof(Fe)));
+    SCCHK(p.get((K << logP) * sizeof(Fe)));
+    for (uint64_t done = 0; done < cols; done += per) {
+        const uint64_t nc = cols - done < per ? cols - done : per;
+        const int logC = lanes_log(nc);
+        const uint64_t half = K << logC;
+        const Fe* src = d_values + done * ld_in;
+        Fe* cur = p.fe();
+        Fe* nxt = tk.fe();
+        if (L == 0) hipLaunchKernelGGL(pt_rev_poly_cols_kernel, dim3(pt_blocks(half)), dim3(256), 0, st, src, (uint64_t)1, ld_in, nc, cur, K, logC, half);   // one point: the value itself
+        else hipLaunchKernelGGL(pt_weights_cols_kernel, dim3(pt_blocks(half)), dim3(256), 0, st, src, ld_in, nc, (const Fe*)t->winv_m, k, cur, logC, half);
+        // up: P = P_L * Z_R + P_R * Z_L
+        for (int l = 0; l < L; ++l) {
+            hipLaunchKernelGGL(pt_expand_cols_kernel, dim3(pt_blocks(2 * half)), dim3(256), 0, st, (const Fe*)cur, bx.fe(), half);
+            SCCHK(ntt_cols(bx.fe(), by.fe(), l + 1, L - l + logC, false, st));
+            hipLaunchKernelGGL(pt_comb_cols_kernel, dim3(pt_blocks(half)), dim3(256), 0, st, (const Fe*)by.fe(), (const Fe*)(t->zf + (uint64_t)l * 2 * K), bx.fe(), half, logC,
+                               ninv_scaled(l + 1, 2));
+            SCCHK(ntt_cols(bx.fe(), nxt, l + 1, L - l - 1 + logC, true, st));
+            Fe* s = cur; cur = nxt; nxt = s;
+        }
+        hipLaunchKernelGGL(pt_store_cols_kernel, dim3(pt_blocks(k * nc)), dim3(256), 0, st, (const Fe*)cur, logC, pad, k, k * nc, d_out + done * ld_out, ld_out);
+        HIPCHK(hipGetLastError());
+    }
     return SC_OK;
 }
 
@@ -507,6 +639,63 @@ int geodomain_interpolate_columns(const sc_geodomain* d, const Fe* values, uint6
     return SC_OK;
 }
 
+// geodomain_evaluate for `cols` columns: column c's m coefficients at coeffs + c * ld_in, its n values at out + c * ld_out.  The five
+// steps of geodomain_evaluate_chunk, each issued ONCE for a set of columns ([cols][M] work buffers, NttOpts::cols; sets as
+// geodomain_interpolate_columns makes them); polynomials longer than n go through the same Horner over chunks of n coefficients,
+// the chunk powers shared by the columns.  Nothing waits.
+int geodomain_evaluate_columns(const sc_geodomain* d, const Fe* coeffs, uint64_t m, uint64_t ld_in, uint64_t cols, Fe* out, uint64_t ld_out, hipStream_t st) {
+    const uint64_t n = d->n, M = d->M;
+    if (m == 0) {
+        hipLaunchKernelGGL(geo_zero_cols_kernel, dim3(pt_blocks(cols * n)), dim3(256), 0, st, out, ld_out, n, cols * n);
+        HIPCHK(hipGetLastError());
+        return SC_OK;
+    }
+    uint64_t per = COLS_ELEMS_PER_LAUNCH / M;
+    if (per < 1) per = 1;
+    if (per > 65536) per = 65536;
+    if (per > cols) per = cols;
+    PoolTmpAsync bx, by, y, vals;
+    SCCHK(bx.get(per * M * sizeof(Fe)));
+    SCCHK(by.get(per * M * sizeof(Fe)));
+    const Fe rt = canonical_root(d->logM), rti = root_inverse(rt, M);
+    const Fe c_m2 = ninv_scaled(d->logM, 2);
+    const uint64_t chunks = (m + n - 1) / n;
+    if (chunks > 1) {                                                       // y_i = x_i^n = c^n (q^n)^i
+        SCCHK(y.get(n * sizeof(Fe)));
+        SCCHK(vals.get(per * n * sizeof(Fe)));
+        const Fe cn_m = mont_pow(to_mont(d->c), n);
+        const Fe qn = from_mont(mont_pow(to_mont(d->q), n));
+        PowTables* py;
+        SCCHK(get_pow(qn, n, st, &py));
+        hipLaunchKernelGGL(geo_chunk_power_kernel, dim3(pt_blocks(n)), dim3(256), 0, st, y.fe(), n, cn_m, (const Fe*)py->lo, (const Fe*)py->hi);
+    }
+    for (uint64_t done = 0; done < cols; done += per) {
+        const uint64_t k = cols - done < per ? cols - done : per;
+        Fe* o = out + done * ld_out;
+        for (uint64_t j = chunks; j-- > 0;) {
+            const uint64_t len = (j == chunks - 1) ? m - j * n : n;
+            const Fe* p = coeffs + done * ld_in + j * n;
+            const bool top = j == chunks - 1;
+            int rc;
+            const PowTables* pc = geo_cpow(d, d->c, n, st, &rc);           // (looked up per use: a table in use is a recent lookup)
+            SCCHK(rc);
+            NttOpts padded, whole;
+            padded.cols = whole.cols = (uint32_t)k;
+            padded.in_limit = len;
+            hipLaunchKernelGGL(geo_eval_in_cols_kernel, dim3(pt_blocks(k * len)), dim3(256), 0, st, p, ld_in, len, k * len, pc ? (const Fe*)pc->lo : nullptr,
+                               pc ? (const Fe*)pc->hi : nullptr, (const Fe*)d->tinv_m, bx.fe(), M);
+            SCCHK(ntt_device(bx.fe(), by.fe(), d->logM, rt, false, padded, st));
+            hipLaunchKernelGGL(geo_corr_cols_kernel, dim3(pt_blocks(k * M)), dim3(256), 0, st, (const Fe*)by.fe(), (const Fe*)d->Bf, bx.fe(), d->logM, k * M, c_m2);
+            SCCHK(ntt_device(bx.fe(), by.fe(), d->logM, rti, false, whole, st));
+            hipLaunchKernelGGL(geo_mul_tab_cols_kernel, dim3(pt_blocks(k * n)), dim3(256), 0, st, (const Fe*)by.fe(), M, (const Fe*)d->tinv_m, top ? o : vals.fe(), top ? ld_out : n,
+                               n, k * n);
+            if (!top) hipLaunchKernelGGL(geo_horner_cols_kernel, dim3(pt_blocks(k * n)), dim3(256), 0, st, o, ld_out, (const Fe*)y.fe(), (const Fe*)vals.fe(), n, n, k * n);
+        }
+        HIPCHK(hipGetLastError());
+    }
+    return SC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -551,12 +740,31 @@ int sc_polytree_interpolate_dev(sc_polytree_t* tree, const void* d_values, void*
     if (!tree || !d_out || !d_values) return fail(SC_ERR_BAD_ARG, "null argument");
     return polytree_interpolate(tree, (const Fe*)d_values, (Fe*)d_out, pick_stream(stream));
 }
+int sc_polytree_evaluate_columns_dev(sc_polytree_t* tree, const void* d_coeffs, uint64_t m, uint64_t ld_in, uint64_t cols, const void* d_points, void* d_out, uint64_t ld_out,
+                                     void* stream) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    if (!tree || !d_out || (m && !d_coeffs)) return fail(SC_ERR_BAD_ARG, "null argument");
+    if (m > tree->K && !d_points) return fail(SC_ERR_BAD_ARG, "polynomial longer than the padded domain needs the points for chunked evaluation");
+    if (cols > 1 && (ld_in < m || ld_out < tree->k)) return fail(SC_ERR_BAD_ARG, "a column stride below the column's length");
+    if (cols == 0) return SC_OK;
+    return polytree_evaluate_columns(tree, (const Fe*)d_coeffs, m, ld_in, cols, (const Fe*)d_points, (Fe*)d_out, ld_out, pick_stream(stream));
+}
+int sc_polytree_interpolate_columns_dev(sc_polytree_t* tree, const void* d_values, uint64_t ld_in, uint64_t cols, void* d_out, uint64_t ld_out, void* stream) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    if (!tree || !d_out || !d_values) return fail(SC_ERR_BAD_ARG, "null argument");
+    if (cols > 1 && (ld_in < tree->k || ld_out < tree->k)) return fail(SC_ERR_BAD_ARG, "a column stride below the number of points");
+    if (cols == 0) return SC_OK;
+    return polytree_interpolate_columns(tree, (const Fe*)d_values, ld_in, cols, (Fe*)d_out, ld_out, pick_stream(stream));
+}
 int sc_polytree_free(sc_polytree_t* tree) {
     std::lock_guard<std::mutex> lk(g_mu);
     if (!tree) return SC_OK;
     release_after_streams(tree->zc, tree->zc_bytes);
     release_after_streams(tree->zf, tree->zf_bytes);
     if (tree->invg_f) release_after_streams(tree->invg_f, 2 * tree->K * sizeof(Fe));
+    if (tree->winv_m) release_after_streams(tree->winv_m, tree->k * sizeof(Fe));
     delete tree;
     return SC_OK;
 }
@@ -727,6 +935,14 @@ int sc_geodomain_interpolate_columns_dev(const sc_geodomain_t* domain, const voi
     if (ld_in < domain->n || ld_out < domain->n) return fail(SC_ERR_BAD_ARG, "a column stride below the number of points");
     if (cols == 0) return SC_OK;
     return geodomain_interpolate_columns(domain, (const Fe*)d_values, ld_in, cols, (Fe*)d_out, ld_out, pick_stream(stream));
+}
+int sc_geodomain_evaluate_columns_dev(const sc_geodomain_t* domain, const void* d_coeffs, uint64_t m, uint64_t ld_in, uint64_t cols, void* d_out, uint64_t ld_out, void* stream) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    if (!domain || !d_out || (m && !d_coeffs)) return fail(SC_ERR_BAD_ARG, "null argument");
+    if (cols > 1 && (ld_in < m || ld_out < domain->n)) return fail(SC_ERR_BAD_ARG, "a column stride below the column's length");
+    if (cols == 0) return SC_OK;
+    return geodomain_evaluate_columns(domain, (const Fe*)d_coeffs, m, ld_in, cols, (Fe*)d_out, ld_out, pick_stream(stream));
 }
 int sc_geodomain_free(sc_geodomain_t* domain) {
     std::lock_guard<std::mutex> lk(g_mu);

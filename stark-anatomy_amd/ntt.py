@@ -632,19 +632,50 @@ def _rows_of(matrix, count, n, field):
     return [DeviceCodeword(DeviceVector.wrap(matrix.ptr + 16 * n * c, n, matrix), field) for c in range(count)]
 
 
+def fast_evaluate_columns_device(coefficient_list, domain):
+    """[fast_evaluate_device(c, domain) for c in coefficient_list] for DeviceCodewords of any lengths on a DeviceDomain of either
+    kind: every step of the evaluation is issued once for all columns (sc_geodomain_evaluate_columns_dev on a progression,
+    sc_polytree_evaluate_columns_dev through the resident tree otherwise) and the results are views of ONE value matrix [cols][n].
+    The coefficients are first copied into one zero-padded matrix unless they already are equally spaced rows of one."""
+    coefficient_list = list(coefficient_list)
+    if not coefficient_list:
+        return []
+    n, cols = len(domain), len(coefficient_list)
+    m = max(len(c) for c in coefficient_list)
+    if m:
+        holder, pitch = _as_matrix(coefficient_list, m)
+        matrix = _View(holder, (cols - 1) * pitch + m)     # (`holder` keeps the owner alive for the call; frees are parked behind the stream)
+    else:
+        matrix, pitch = DeviceVector(1), 0
+    return _rows_of(domain.tree.evaluate_columns(matrix, m, cols, pitch), cols, n, domain.field)
+
+
+def fast_evaluate_columns(polynomials, domain, primitive_root, root_order):
+    """[fast_evaluate(p, domain, primitive_root, root_order) for p in polynomials]: on a domain that goes to the device, one
+    upload, one column evaluation (progression tables or subproduct tree), one download; below that the recursion per polynomial"""
+    _check_root(primitive_root, root_order)
+    polynomials = list(polynomials)
+    n, cols = len(domain), len(polynomials)
+    if not polynomials or n < DEVICE_TREE_MIN_POINTS:
+        return [fast_evaluate(p, domain, primitive_root, root_order) for p in polynomials]
+    tables = _device_tree(domain)
+    m = max(len(p.coefficients) for p in polynomials)
+    matrix = DeviceVector.from_bytes(b"".join(_pack(p.coefficients) + bytes(16 * (m - len(p.coefficients))) for p in polynomials)) if m else DeviceVector(1)
+    flat = _unpack(tables.evaluate_columns(matrix, m, cols).to_bytes(), cols * n, primitive_root.field)
+    return [flat[c * n:(c + 1) * n] for c in range(cols)]
+
+
 def fast_interpolate_columns_device(domain, values):
-    """[fast_interpolate_device(domain, v) for v in values] for DeviceCodewords of len(domain) values each.  On a progression
-    domain every step of the interpolation is issued once for all columns (sc_geodomain_interpolate_columns_dev) and the results
-    are views of ONE coefficient matrix [cols][n]; the columns are first copied into one matrix unless they already are the
-    consecutive rows of one.  A tree domain goes column by column through its resident tree."""
+    """[fast_interpolate_device(domain, v) for v in values] for DeviceCodewords of len(domain) values each.  Every step of the
+    interpolation is issued once for all columns -- sc_geodomain_interpolate_columns_dev on a progression domain,
+    sc_polytree_interpolate_columns_dev through the resident tree on any other -- and the results are views of ONE coefficient
+    matrix [cols][n]; the columns are first copied into one matrix unless they already are the consecutive rows of one."""
     values = list(values)
     n = len(domain)
     for v in values:
         assert(n == len(v)), "cannot interpolate over domain of different length than values list"
     if not values:
         return []
-    if not isinstance(domain.tree, _sc.GeoDomain):
-        return [fast_interpolate_device(domain, v) for v in values]
     cols = len(values)
     first = values[0].vec.ptr
     if all(v.vec.ptr == first + 16 * n * c for c, v in enumerate(values)):
@@ -658,7 +689,7 @@ def fast_interpolate_columns_device(domain, values):
 
 def fast_interpolate_columns(domain, values_list, primitive_root, root_order):
     """[fast_interpolate(domain, v, primitive_root, root_order) for v in values_list]: on a domain that goes to the device
-    and is a progression, one upload, one column interpolation, one download"""
+    (a progression or any other points), one upload, one column interpolation, one download; below that the recursion per column"""
     _check_root(primitive_root, root_order)
     values_list = list(values_list)
     for values in values_list:
@@ -666,9 +697,9 @@ def fast_interpolate_columns(domain, values_list, primitive_root, root_order):
     if not values_list:
         return []
     n, cols = len(domain), len(values_list)
-    tables = _device_tree(domain) if n >= DEVICE_TREE_MIN_POINTS else None
-    if not isinstance(tables, _sc.GeoDomain):
+    if n < DEVICE_TREE_MIN_POINTS:
         return [fast_interpolate(domain, values, primitive_root, root_order) for values in values_list]
+    tables = _device_tree(domain)                          # (a repeated point raises AssertionError("divide by zero") as fast_interpolate does)
     matrix = DeviceVector.from_bytes(b"".join(_pack(values) for values in values_list))
     flat = _unpack(tables.interpolate_columns(matrix, cols).to_bytes(), cols * n, primitive_root.field)
     return [Polynomial(flat[c * n:(c + 1) * n]) for c in range(cols)]

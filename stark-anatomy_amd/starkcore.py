@@ -157,6 +157,8 @@ SIGNATURES = {
     "sc_polytree_zerofier_dev": (_int, [_vp, _vp, _vp]),
     "sc_polytree_evaluate_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _vp]),
     "sc_polytree_interpolate_dev": (_int, [_vp, _vp, _vp, _vp]),
+    "sc_polytree_evaluate_columns_dev": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _u64, _vp]),
+    "sc_polytree_interpolate_columns_dev": (_int, [_vp, _vp, _u64, _u64, _vp, _u64, _vp]),
     "sc_polytree_free": (_int, [_vp]),
     "sc_geodomain_create": (_int, [_vp, _vp, _u64, ctypes.POINTER(_vp), _vp]),
     "sc_geodomain_points": (_u64, [_vp]),
@@ -165,6 +167,7 @@ SIGNATURES = {
     "sc_geodomain_evaluate_dev": (_int, [_vp, _vp, _u64, _vp, _vp]),
     "sc_geodomain_interpolate_dev": (_int, [_vp, _vp, _vp, _vp]),
     "sc_geodomain_interpolate_columns_dev": (_int, [_vp, _vp, _u64, _u64, _vp, _u64, _vp]),
+    "sc_geodomain_evaluate_columns_dev": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _u64, _vp]),
     "sc_geodomain_free": (_int, [_vp]),
 }
 
@@ -619,6 +622,23 @@ class PolyTree:
         _check(lib().sc_polytree_interpolate_dev(self._h, values.ptr, out.ptr, None))
         return out
 
+    def evaluate_columns(self, coeff_matrix, m, cols, ld_in=None):
+        """coeff_matrix: DeviceVector [cols][m], column c's m coefficients at element c * m (c * ld_in where given) -> DeviceVector
+        [cols][k] of the columns' values; every step of `evaluate` issued once per set of columns (sc_polytree_evaluate_columns_dev)"""
+        ld_in = m if ld_in is None else ld_in
+        assert cols == 0 or coeff_matrix.n >= (cols - 1) * ld_in + m
+        out = DeviceVector(max(cols * self.k, 1))
+        _check(lib().sc_polytree_evaluate_columns_dev(self._h, coeff_matrix.ptr, m, ld_in, cols, self.points.ptr, out.ptr, self.k, None))
+        return out
+
+    def interpolate_columns(self, values_matrix, cols):
+        """values_matrix: DeviceVector [cols][k], column c's values at element c * k -> DeviceVector [cols][k] of the columns'
+        coefficients; every step of `interpolate` issued once per set of columns (sc_polytree_interpolate_columns_dev)"""
+        assert values_matrix.n >= cols * self.k
+        out = DeviceVector(max(cols * self.k, 1))
+        _check(lib().sc_polytree_interpolate_columns_dev(self._h, values_matrix.ptr, self.k, cols, out.ptr, self.k, None))
+        return out
+
     def free(self):
         if self._h is not None and _lib is not None:
             _lib.sc_polytree_free(self._h)
@@ -681,6 +701,15 @@ class GeoDomain:
         assert values.n == self.k
         out = DeviceVector(self.k)
         _check(lib().sc_geodomain_interpolate_dev(self._h, values.ptr, out.ptr, None))
+        return out
+
+    def evaluate_columns(self, coeff_matrix, m, cols, ld_in=None):
+        """coeff_matrix: DeviceVector [cols][m], column c's m coefficients at element c * m (c * ld_in where given) -> DeviceVector
+        [cols][k] of the columns' values; every step of `evaluate` issued once for all columns (sc_geodomain_evaluate_columns_dev)"""
+        ld_in = m if ld_in is None else ld_in
+        assert cols == 0 or coeff_matrix.n >= (cols - 1) * ld_in + m
+        out = DeviceVector(max(cols * self.k, 1))
+        _check(lib().sc_geodomain_evaluate_columns_dev(self._h, coeff_matrix.ptr, m, ld_in, cols, out.ptr, self.k, None))
         return out
 
     def interpolate_columns(self, values_matrix, cols):
