@@ -534,6 +534,40 @@ int sc_merkle_open_batch(const sc_merkle_t* tree, const uint64_t* indices, uint6
  * A row that indexes outside the digests, roots or rounds given: SC_ERR_BAD_ARG, nothing is run. */
 int sc_merkle_verify_batch(const void* rows, uint64_t n, const void* digests, uint64_t n_digests, const void* roots, uint64_t n_roots, uint8_t* verdicts_out);
 int sc_fri_colinearity_batch(const void* rows, uint64_t n, const void* rounds, uint64_t n_rounds, uint8_t* verdicts_out);
+/* The verifier's third check as rows (csrc/combination.cuh): the nonlinear combination recomputed at the opened points
+ * (fast_stark.py:236-284), for one AIR on one FRI domain and any number of proofs (members).  Synchronous, host buffers in and out, any
+ * row count: the rows go to the device in chunks through the same staging buffer ("verify_stage_kb"); a chunk is three launches -- the
+ * point matrix, the AIR under the plan of sc_mpoly_eval_columns_dev, the weighted sum -- and one wait.  All residues are 16 bytes
+ * little-endian.  The AIR's variables are X, `registers` current and `registers` next values: nvars = 1 + 2 registers <= 255; ncons /
+ * nterms / exps / coefs as sc_mpoly_eval_columns_dev takes them (exps: [terms][nvars] bytes, so no term can name a variable beyond
+ * nvars).  Per member: 1 + 2 ncons + 2 registers weights (randomizer; per transition quotient plain and shifted; per boundary quotient
+ * plain and shifted), and polys[(m * registers + s) * 4 ..] = {offset, length} of register s's boundary zerofier, then of its boundary
+ * interpolant, in elements of `pool`, lowest degree first; length 0 is the zero polynomial.
+ * A row is 64 + 32 registers bytes: {u64 member, u64 index, claimed, randomizer leaf, transition-zerofier leaf, registers boundary-quotient
+ * leaves at `index`, registers at successor = (index + step) mod domain_length}.  With x = generator * omega^index (x' at the successor),
+ * trace_s = quotient_s * zerofier_s(x) + interpolant_s(x), point = (x, trace at x, trace at x'):
+ *   total = randomizer * w_0 + sum_c (AIR_c(point) / zerofier leaf) * (w + x^transition_shifts[c] * w') + sum_s quotient_s * (w + x^boundary_shifts[s] * w')
+ * verdicts_out[i] = 1 when total == claimed, else 0; 2 (undecided: the caller decides) when the zerofier leaf is 0 or a residue the row
+ * uses -- its own, its member's weights or coefficient lists, generator, omega -- is not below p.
+ * n == 0: SC_OK.  SC_ERR_BAD_ARG, nothing run and nothing written: a null pointer, registers 0 or above 127, domain_length no power of
+ * two, step 0, a row with index >= domain_length or member >= members, a coefficient list outside the pool, a coefficient of the AIR
+ * not below p. */
+typedef struct sc_combination {
+    uint64_t registers, ncons;
+    const uint64_t* nterms;             /* [ncons] */
+    const uint8_t* exps;
+    const void* coefs;
+    uint64_t generator[2], omega[2];
+    uint64_t domain_length, step;
+    const uint64_t* transition_shifts;  /* [ncons] */
+    const uint64_t* boundary_shifts;    /* [registers] */
+    uint64_t members;
+    const void* weights;                /* [members][1 + 2 ncons + 2 registers] */
+    const uint64_t* polys;              /* [members][registers][4] */
+    const void* pool;
+    uint64_t pool_len;                  /* elements */
+} sc_combination_t;
+int sc_stark_combination_batch(const sc_combination_t* shared, const void* rows, uint64_t n, uint8_t* verdicts_out);
 /* opened elements AND their paths in one call: elems_out[i] = d_elems[indices[i]] (d_elems = the device vector the tree was built from) */
 int sc_merkle_query_dev(const sc_merkle_t* tree, const void* d_elems, const uint64_t* indices, uint64_t k, void* elems_out, uint8_t* paths_out);
 /* several (tree, vector) pairs in one round trip (the query phase of Fri.prove, fri.py:124-128): counts[t] of the concatenated

@@ -1,10 +1,12 @@
 // columns.hip -- the kernels of csrc/columns.cuh and their entries: the division of a matrix of polynomial columns (pointwise and on
 // a coset, code/ntt.py:159-176 for every column at once), the nonlinear combination of code/fast_stark.py:130-145 in one pass, and ONE
 // deferred verdict for all columns of a call (the scheme of sc_coset_divide_later_dev: a one-wave kernel behind the work writes the
-// words to a pinned slot, then a sequence number).
+// words to a pinned slot, then a sequence number).  Also the verifier's combination at the opened points (csrc/combination.cuh,
+// sc_stark_combination_batch), which runs the AIR through mpoly_eval_columns_kernel here.
 #include "core.h"
 #include "columns.cuh"
 #include "mpoly_plan.h"
+#include "combination_plan.h"
 
 namespace sci {
 
@@ -36,6 +38,15 @@ __global__ void __launch_bounds__(256) combine_cols_kernel(const CombineTerm* __
 // grid (point blocks) x (pairs of member and constraint): the pair is uniform in a workgroup, the tables are read with scalar loads
 __global__ void __launch_bounds__(256) mpoly_eval_columns_kernel(const MpolyCols D) {
     mpoly_cols_thread(D, blockIdx.x, blockIdx.y, threadIdx.x);
+}
+
+// the verifier's combination rows (csrc/combination.cuh): grid (row blocks) x (variables of the point), and (row blocks); the shared
+// description travels as a kernel argument, the verdicts are plain byte stores
+__global__ void __launch_bounds__(256) combination_point_kernel(const CombShared S) {
+    combination_point_thread(S, blockIdx.x, blockIdx.y, threadIdx.x);
+}
+__global__ void __launch_bounds__(256) combination_sum_kernel(const CombShared S) {
+    combination_sum_thread(S, blockIdx.x, threadIdx.x);
 }
 
 __global__ void __launch_bounds__(256) scale_cols_kernel(const Fe* in, uint64_t ld_in, Fe* out, uint64_t ld_out, uint64_t n,
@@ -128,6 +139,39 @@ static int upload_words(void* d_dst, const void* host, size_t bytes, hipStream_t
     HIPCHK(hipStreamSynchronize(st));
     return SC_OK;
 }
+
+
+// the plan's tables as mpoly_eval_columns_kernel reads them -- coefficients (16-byte elements first), variables, constraints, drops,
+// exponent words -- in device memory of the call's own, and the launches over them
+struct MpolyTables {
+    PoolTmpAsync mem;
+    size_t o_coef = 0, o_vars = 0, o_cons = 0, o_drop = 0, o_exps = 0;
+    uint32_t nvw = 0;
+    int put(const MpolyPlan& P, const std::vector<MpolyVar>& vars, hipStream_t st) {
+        const size_t b_coef = P.coef.size() * sizeof(Fe), b_vars = vars.size() * sizeof(MpolyVar), b_cons = P.cons.size() * sizeof(MpolyCons),
+                     b_drop = P.drop.size() * sizeof(uint32_t), b_exps = P.exps.size() * sizeof(uint32_t);
+        std::vector<uint8_t> table(b_coef + b_vars + b_cons + b_drop + b_exps);
+        uint8_t* at = table.data();
+        auto add = [&](const void* src, size_t bytes) { if (bytes) memcpy(at, src, bytes); at += bytes; return (size_t)(at - bytes - table.data()); };
+        o_coef = add(P.coef.data(), b_coef); o_vars = add(vars.data(), b_vars); o_cons = add(P.cons.data(), b_cons); o_drop = add(P.drop.data(), b_drop);
+        o_exps = add(P.exps.data(), b_exps);
+        nvw = P.nvw;
+        SCCHK(mem.get(table.size() + 8));
+        return upload_words(mem.p, table.data(), table.size(), st);
+    }
+    int launch(const Fe* vals, uint64_t n, uint64_t members, uint64_t ncons, Fe* out, uint64_t ld_out, hipStream_t st) const {
+        const uint8_t* T = (const uint8_t*)mem.p;
+        const uint64_t pairs = members * ncons;
+        for (uint64_t pair0 = 0; pair0 < pairs; pair0 += COLS_GRID_ROWS) {
+            const uint64_t rows = pairs - pair0 < COLS_GRID_ROWS ? pairs - pair0 : COLS_GRID_ROWS;
+            const MpolyCols D{vals, (const MpolyVar*)(T + o_vars), (const MpolyCons*)(T + o_cons), (const Fe*)(T + o_coef), (const uint32_t*)(T + o_drop),
+                              (const uint32_t*)(T + o_exps), nvw, (uint32_t)ncons, n, out, ld_out, (uint32_t)pair0};
+            hipLaunchKernelGGL(mpoly_eval_columns_kernel, dim3((unsigned)((n + COLS_WG - 1) / COLS_WG), (unsigned)rows), dim3(COLS_WG), 0, st, D);
+            HIPCHK(hipGetLastError());
+        }
+        return SC_OK;
+    }
+};
 
 }  // namespace sci
 
@@ -306,24 +350,72 @@ int sc_mpoly_eval_columns_dev(const void* d_vals, uint64_t nvars, uint64_t n, ui
         if (lo < out_hi && out_lo < hi) return fail(SC_ERR_BAD_ARG, "the output may not overlap the values");
     }
     hipStream_t st = pick_stream(stream);
-    // the tables as the kernel reads them: coefficients (16-byte elements first), variables, constraints, drops, exponent words
-    const size_t b_coef = P.coef.size() * sizeof(Fe), b_vars = vars.size() * sizeof(MpolyVar), b_cons = P.cons.size() * sizeof(MpolyCons),
-                 b_drop = P.drop.size() * sizeof(uint32_t), b_exps = P.exps.size() * sizeof(uint32_t);
-    std::vector<uint8_t> table(b_coef + b_vars + b_cons + b_drop + b_exps);
-    uint8_t* at = table.data();
-    auto put = [&](const void* src, size_t bytes) { if (bytes) memcpy(at, src, bytes); at += bytes; return (size_t)(at - bytes - table.data()); };
-    const size_t o_coef = put(P.coef.data(), b_coef), o_vars = put(vars.data(), b_vars), o_cons = put(P.cons.data(), b_cons), o_drop = put(P.drop.data(), b_drop),
-                 o_exps = put(P.exps.data(), b_exps);
-    PoolTmpAsync d_table;
+    MpolyTables tables;
+    SCCHK(tables.put(P, vars, st));
+    return tables.launch((const Fe*)d_vals, n, members, ncons, (Fe*)d_out, ld_out, st);
+}
+
+// FastStark.verify_batch's combination check at the opened points (csrc/combination.cuh): per chunk of staged rows the point matrix,
+// the AIR under the plan above (members = 1, n = the chunk's rows: ONE launch for all constraints) and the weighted sum, on the
+// library stream with one wait.  What every chunk reads -- weights, coefficient pool, the members' lists, shifts, the plan -- is
+// uploaded once; the chunks' rows and verdicts go through the bounded pinned buffer of the other two verifier entries.
+int sc_stark_combination_batch(const sc_combination_t* shared, const void* rows, uint64_t n, uint8_t* verdicts_out) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    if (n == 0) return SC_OK;
+    if (!shared || !rows || !verdicts_out) return fail(SC_ERR_BAD_ARG, "null argument");
+    const sc_combination_t& c = *shared;
+    CombTables T;
+    if (const char* what = combination_prepare(c, rows, n, T)) return fail(SC_ERR_BAD_ARG, what);
+    if (T.undecided) {
+        memset(verdicts_out, CB_UNDECIDED, n);
+        return SC_OK;
+    }
+    const uint32_t w = (uint32_t)c.registers, ncons = (uint32_t)c.ncons, nvars = 1 + 2 * w;
+    const uint64_t stride = comb_row_bytes(w);
+    const size_t cap = g.verify_stage_bytes;
+    const uint64_t fit = combination_chunk_rows(cap, w), per = n < fit ? n : fit;
+    auto align = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t rows_b = align(per * stride);
+    uint8_t* stage;
+    SCCHK(verify_stage_buffer(cap, &stage));
+    hipStream_t st = g.stream;
+    // [weights][pool][lists][shifts][member flags]: 16-byte elements first
+    const size_t b_w = T.weights_m.size() * sizeof(Fe), b_pool = c.pool_len * sizeof(Fe), b_polys = 2 * c.members * w * sizeof(CombPoly),
+                 b_shifts = T.shifts.size() * sizeof(uint64_t), b_bad = c.members;
+    std::vector<uint8_t> table(b_w + b_pool + b_polys + b_shifts + b_bad);
+    memcpy(table.data(), T.weights_m.data(), b_w);
+    if (b_pool) memcpy(table.data() + b_w, c.pool, b_pool);
+    memcpy(table.data() + b_w + b_pool, c.polys, b_polys);
+    memcpy(table.data() + b_w + b_pool + b_polys, T.shifts.data(), b_shifts);
+    memcpy(table.data() + b_w + b_pool + b_polys + b_shifts, T.member_bad.data(), b_bad);
+    PoolTmpAsync d_table, d_stage, d_vals;
     SCCHK(d_table.get(table.size() + 8));
+    SCCHK(d_stage.get(rows_b + align(per)));
+    SCCHK(d_vals.get((size_t)(nvars + ncons) * per * sizeof(Fe)));
     SCCHK(upload_words(d_table.p, table.data(), table.size(), st));
-    const uint8_t* T = (const uint8_t*)d_table.p;
-    for (uint64_t pair0 = 0; pair0 < pairs; pair0 += COLS_GRID_ROWS) {
-        const uint64_t rows = pairs - pair0 < COLS_GRID_ROWS ? pairs - pair0 : COLS_GRID_ROWS;
-        const MpolyCols D{(const Fe*)d_vals, (const MpolyVar*)(T + o_vars), (const MpolyCons*)(T + o_cons), (const Fe*)(T + o_coef), (const uint32_t*)(T + o_drop),
-                          (const uint32_t*)(T + o_exps), P.nvw, (uint32_t)ncons, n, (Fe*)d_out, ld_out, (uint32_t)pair0};
-        hipLaunchKernelGGL(mpoly_eval_columns_kernel, dim3((unsigned)((n + COLS_WG - 1) / COLS_WG), (unsigned)rows), dim3(COLS_WG), 0, st, D);
+    MpolyTables plan;
+    if (ncons) SCCHK(plan.put(T.plan, combination_vars(w, per), st));
+    const uint8_t* D = (const uint8_t*)d_table.p;
+    uint8_t* d_rows = (uint8_t*)d_stage.p;
+    Fe* vals = d_vals.fe();
+    Fe* tq = vals + (size_t)nvars * per;
+    for (uint64_t i = 0; i < n; i += per) {
+        const uint64_t count = n - i < per ? n - i : per;
+        memcpy(stage, (const uint8_t*)rows + i * stride, count * stride);
+        HIPCHK(hipMemcpyAsync(d_rows, stage, count * stride, hipMemcpyHostToDevice, st));
+        const CombShared S{d_rows, count, w, ncons, T.generator_m, T.omega_m, c.domain_length - 1, c.step, (const CombPoly*)(D + b_w + b_pool),
+                           (const Fe*)(D + b_w), (const Fe*)D, D + b_w + b_pool + b_polys + b_shifts, (const uint64_t*)(D + b_w + b_pool + b_polys),
+                           vals, per, tq, d_rows + rows_b};
+        const unsigned gx = (unsigned)((count + COLS_WG - 1) / COLS_WG);
+        hipLaunchKernelGGL(combination_point_kernel, dim3(gx, nvars), dim3(COLS_WG), 0, st, S);
         HIPCHK(hipGetLastError());
+        if (ncons) SCCHK(plan.launch(vals, count, 1, ncons, tq, per, st));
+        hipLaunchKernelGGL(combination_sum_kernel, dim3(gx), dim3(COLS_WG), 0, st, S);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(stage + rows_b, d_rows + rows_b, count, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        memcpy(verdicts_out + i, stage + rows_b, count);
     }
     return SC_OK;
 }

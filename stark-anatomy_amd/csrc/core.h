@@ -7,7 +7,8 @@
 //   polytree_geo.hip  subproduct trees and geometric progressions (fast_zerofier / fast_evaluate / fast_interpolate)
 //   fourstep.hip      batched transforms, the sharded four-step plan, the RCCL communicator, the direct-store corner turn
 //   rescue.hip        the Rescue-Prime permutation (hash and trace) over many inputs
-//   columns.hip       division, combination and one deferred verdict over a matrix of polynomial columns (csrc/columns.cuh)
+//   columns.hip       division, combination and one deferred verdict over a matrix of polynomial columns (csrc/columns.cuh); the
+//                     verifier's combination at the opened points as rows (csrc/combination.cuh)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -257,6 +258,7 @@ int fold_constants(uint64_t N, Fe offset, Fe omega, hipStream_t st, PowTables** 
 int host_pool_get(size_t bytes, void** out);
 int host_pool_put(void* p);
 bool host_pool_holds(const void* p, size_t bytes);
+int verify_stage_buffer(size_t bytes, uint8_t** out);   // the batched verifier's pinned staging buffer, grown to `bytes` (one per process; callers hold g_mu)
 
 // ---- polytree_geo.hip
 Fe canonical_root(int logn);

@@ -1129,6 +1129,9 @@ int verify_chunked(const Row* rows, uint64_t n, const uint8_t* table, size_t ent
     return SC_OK;
 }
 }  // namespace
+namespace sci {
+int verify_stage_buffer(size_t bytes, uint8_t** out) { return verify_stage(bytes, out); }
+}  // namespace sci
 }  // extern "C++"
 
 int sc_merkle_verify_batch(const void* rows, uint64_t n, const void* digests, uint64_t n_digests, const void* roots, uint64_t n_roots, uint8_t* verdicts_out) {

@@ -824,9 +824,8 @@ class FastStark:
                 self._zerofier_values[order] = (tz_dev, zvals)
             cols = K * C
             tvals, whole = DeviceVector(cols * order), DeviceVector(cols * order)
-            nterms = (ctypes.c_uint64 * C)(*[len(terms) for _, _, terms in group])
-            exps = bytes(e for _, _, terms in group for k, _ in terms for e in k)
-            coefs = b"".join(v.to_bytes(16, "little") for _, _, terms in group for _, v in terms)
+            counts, exps, coefs = MPolynomial.pack_terms([terms for _, _, terms in group])
+            nterms = (ctypes.c_uint64 * C)(*counts)
             _sc._check(lib.sc_mpoly_eval_columns_dev(vals.ptr, nvars, order, K, var_base, var_ld, var_src, var_rot, C, nterms, exps, coefs, tvals.ptr, order, None))
             handle = ctypes.c_void_p()
             rc = lib.sc_pointwise_div_columns_later_dev(tvals.ptr, order, zvals.ptr, 0, tvals.ptr, order, order, cols, ctypes.byref(handle), None)
@@ -1075,8 +1074,9 @@ class FastStark:
     def verify_batch(self, proofs, transition_constraints, boundaries, transition_zerofier_root, proof_streams=None):
         """[self.verify(proofs[i], transition_constraints, boundaries[i], transition_zerofier_root, proof_streams[i]) for i ...] with
         every Merkle path and FRI colinearity test of the whole batch checked in one device call per kind (csrc/merkle_verify.cuh).
-        The walk over each proof is `verify`'s, pull for pull; the checks that are cheap on the host (the last codeword, its degree,
-        the combination at the opened points) run here, the rest become rows.  A proof on which `verify` raises is reported False."""
+        The walk over each proof is `verify`'s, pull for pull; the checks that are cheap on the host (the last codeword, its degree)
+        run here, the rest become rows -- the combination at the opened points too (COMBINATION_ON_DEVICE; one more device call for
+        the batch).  A proof on which `verify` raises is reported False."""
         if proof_streams is None:
             proof_streams = [None] * len(proofs)
         checks = BatchChecks(len(proofs))
@@ -1125,7 +1125,7 @@ class FastStark:
             # undo the boundary quotient: trace = quotient * zerofier + interpolant
             return [quotient_leaves[s][index] * zerofiers[s].evaluate(x) + interpolants[s].evaluate(x) for s in registers]
 
-        for index, claimed in opened:
+        def holds(index, claimed):
             successor = (index + step) % N
             x = self.generator * (self.omega ^ index)
             point = [x] + trace_row(index, x) + trace_row(successor, self.generator * (self.omega ^ successor))
@@ -1137,9 +1137,69 @@ class FastStark:
             for s, shift in zip(registers, boundary_shifts):
                 quotient = quotient_leaves[s][index]
                 total = total + quotient * next(weight) + quotient * (x ^ shift) * next(weight)
-            if not (total == claimed):
-                return False
+            return bool(total == claimed)
+
+        # the opened points become rows of one device call for the whole batch (csrc/combination.cuh); `holds` decides what the rows
+        # cannot hold or the device leaves undecided, and every point when the check stays on the host
+        group = self._combination_group(checks, transition_constraints, transition_shifts, boundary_shifts) if FastStark.COMBINATION_ON_DEVICE else None
+        if group is None:
+            for index, claimed in opened:
+                if not holds(index, claimed):
+                    return False
+            return True
+        member = group.member(weights, zerofiers, interpolants)
+        for index, claimed in opened:
+            successor = (index + step) % N
+            checks.combination(owner, group, member, index, claimed, randomizer[index], zerofier_values[index], [quotient_leaves[s][index] for s in registers],
+                               [quotient_leaves[s][successor] for s in registers], lambda index=index, claimed=claimed: holds(index, claimed))
         return True
+
+    # The combination at the opened points of verify_batch (fast_stark.py:236-284 per point and proof) as rows of ONE device call for
+    # the whole batch: the trace rows rebuilt from the boundary quotients, the AIR under the prover's Horner plan (csrc/mpoly_plan.h),
+    # the transition quotients, the shifts, the weighted sum (csrc/combination.cuh).  False: the host loop, as before.
+    COMBINATION_ON_DEVICE = True
+    # Batches of fewer opened points than this keep the host loop (the three launches and the wait have a price).  Unmeasured so far:
+    # 0 until tools/verify_timing.py has found a crossover.
+    COMBINATION_DEVICE_MIN_ROWS = 0
+
+    def _combination_tables(self, transition_constraints):
+        """the constraints as sc_stark_combination_batch takes them (MPolynomial.pack_terms over 1 + 2 registers variables), None when
+        one has no dictionary, a coefficient that is not a residue of the main field, an exponent above 255 or too many variables"""
+        nvars = 1 + 2 * self.num_registers
+        try:
+            term_lists = []
+            for constraint in transition_constraints:
+                dictionary = getattr(constraint, "dictionary", None)
+                if type(dictionary) is not dict or nvars > 255:
+                    return None
+                for v in dictionary.values():
+                    if not (type(v) is FieldElement and type(v.value) is int and 0 <= v.value < Field.P_MAIN and v.field.p == Field.P_MAIN):
+                        return None
+                plan = constraint.value_domain_terms([1] * nvars)
+                if plan is NotImplemented:
+                    return None
+                term_lists.append(plan[1])
+            return MPolynomial.pack_terms(term_lists)
+        except Exception:
+            return None
+
+    def _combination_group(self, checks, transition_constraints, transition_shifts, boundary_shifts):
+        """the rows of this AIR on this domain in `checks` (made when the batch's first proof gets here), None when the check cannot
+        be a device call at all: another field, constraints or shifts the format does not hold"""
+        if self.field.p != Field.P_MAIN:
+            return None
+        key = ("stark", id(self), id(transition_constraints), tuple(transition_shifts), tuple(boundary_shifts))
+
+        def make():
+            tables = self._combination_tables(transition_constraints)
+            N = self.fri.domain_length
+            fits = (tables is not None and all(type(k) is int and 0 <= k < (1 << 64) for k in list(transition_shifts) + list(boundary_shifts))
+                    and N >= 1 and N & (N - 1) == 0 and all(type(e.value) is int and 0 <= e.value < (1 << 128) for e in (self.generator, self.omega)))
+            if not fits:
+                return False
+            return CombinationRows(self.num_registers, tables, self.generator.value, self.omega.value, N, self.expansion_factor, transition_shifts, boundary_shifts,
+                                   FastStark.COMBINATION_DEVICE_MIN_ROWS, keep=transition_constraints)
+        return checks.combination_group(key, make) or None
 
     @staticmethod
     def _collect_openings(stream, root, positions, checks, owner):

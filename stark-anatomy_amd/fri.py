@@ -92,9 +92,77 @@ def library_transcript(proof_stream, rounds):
     return None
 
 
+def _residue(element):
+    """the canonical int of a FieldElement of the main field, None for anything else"""
+    if type(element) is FieldElement and type(element.value) is int and 0 <= element.value < Field.P_MAIN and element.field.p == Field.P_MAIN:
+        return element.value
+    return None
+
+
+class CombinationRows:
+    """The opened points of the proofs that share one AIR on one FRI domain, as rows of sc_stark_combination_batch
+    (csrc/combination.cuh): what all share, the members (one per proof: its weights and the coefficient lists of its boundary
+    zerofiers and interpolants, equal lists stored once), and per opened point a row next to the host function that decides it
+    when the device does not."""
+
+    def __init__(self, registers, tables, generator, omega, domain_length, step, transition_shifts, boundary_shifts, min_rows=0, keep=None):
+        self.registers, self.tables, self.min_rows, self.keep = registers, tables, min_rows, keep
+        self.generator, self.omega, self.domain_length, self.step = generator, omega, domain_length, step
+        self.transition_shifts, self.boundary_shifts = list(transition_shifts), list(boundary_shifts)
+        self.weights, self.polys, self.pool, self.places, self.members = [], [], [], {}, 0
+        self.rows, self.owners, self.hosts = [], [], []
+        self.host_only = []                      # (owner, host function) of rows the format cannot hold
+
+    def member(self, weights, zerofiers, interpolants):
+        """a proof's tables -> its member number, None when a value is not a residue of the main field"""
+        try:
+            values = [_residue(w) for w in weights]
+            lists = [[_residue(c) for c in polynomial.coefficients] for pair in zip(zerofiers, interpolants) for polynomial in pair]
+        except Exception:
+            return None
+        if len(values) != 1 + 2 * len(self.transition_shifts) + 2 * self.registers or len(lists) != 2 * self.registers:
+            return None
+        if None in values or any(None in coefficients for coefficients in lists):
+            return None
+        self.weights.append(_sc.pack(values))
+        for coefficients in lists:
+            key = tuple(coefficients)
+            place = self.places.get(key)
+            if place is None:
+                place = self.places[key] = sum(map(len, self.pool)) if coefficients else 0
+                self.pool.append(coefficients)
+            self.polys += [place, len(coefficients)]
+        self.members += 1
+        return self.members - 1
+
+    def add(self, owner, member, index, claimed, randomizer, zerofier, current, following, host):
+        """one opened point; host: () -> bool, the loop body of FastStark.verify the row stands for"""
+        try:
+            values = [_residue(v) for v in [claimed, randomizer, zerofier] + list(current) + list(following)]
+            fits = member is not None and type(index) is int and 0 <= index < self.domain_length and None not in values and len(values) == 3 + 2 * self.registers
+        except Exception:
+            fits = False
+        if not fits:
+            self.host_only.append((owner, host))
+            return
+        self.rows.append(member.to_bytes(8, "little") + index.to_bytes(8, "little") + _sc.pack(values))
+        self.owners.append(owner)
+        self.hosts.append(host)
+
+    def verdicts(self):
+        """the device call: a uint8 array over the rows"""
+        import numpy as np
+        nterms, exps, coefs = self.tables
+        shared = _sc.Combination(self.registers, nterms, exps, coefs, self.generator, self.omega, self.domain_length, self.step, self.transition_shifts,
+                                 self.boundary_shifts, self.members, b"".join(self.weights), np.asarray(self.polys, dtype=np.uint64),
+                                 _sc.pack([c for coefficients in self.pool for c in coefficients]))
+        return _sc.combination_batch(shared, np.frombuffer(b"".join(self.rows), dtype=_sc.combination_row_dtype(self.registers)))
+
+
 class BatchChecks:
-    """The checks of a batch of proofs collected as rows (csrc/merkle_verify.cuh) instead of evaluated one by one: every Merkle
-    path and every colinearity test of every proof, tagged with the proof it belongs to, then ONE device call per kind (`run`).
+    """The checks of a batch of proofs collected as rows (csrc/merkle_verify.cuh, csrc/combination.cuh) instead of evaluated one by
+    one: every Merkle path, every colinearity test and every opened point of the combination of every proof, tagged with the proof it
+    belongs to, then ONE device call per kind (`run`; the combination: one per AIR and domain).
     A row the device format cannot hold (a leaf that is not a residue below 2^128, a path that is not 64-byte digests, a root that is
     not a 64-byte string, a value that is not a residue of the main field) is decided here, by the host function it replaces."""
 
@@ -108,6 +176,8 @@ class BatchChecks:
         self.c_a, self.c_b, self.c_round, self.c_y, self.c_owner, self.rounds = [], [], [], [], [], []
         self.col_points = []                     # per colinearity row: its points, for test_colinearity if the device leaves it undecided
         self.truncations = []                    # (values list, its length before round 0, round 0's colinearity references)
+        self.combinations = {}                   # key of an (AIR, domain) group -> its CombinationRows
+        self.combination_device_rows = 0         # rows sent to sc_stark_combination_batch by `run`
 
     def reject(self, owner):
         self.ok[owner] = False
@@ -190,6 +260,46 @@ class BatchChecks:
             self.ok[owner] = False
         return ("host", accepted)
 
+    def combination_group(self, key, make):
+        """the CombinationRows of the (AIR, domain) group `key`, made by make() when the batch meets the group for the first time"""
+        group = self.combinations.get(key)
+        if group is None:
+            group = self.combinations[key] = make()
+        return group
+
+    def combination(self, owner, group, member, index, claimed, randomizer, zerofier, current, following, host):
+        """one opened point of proof `owner` -- the recomputed combination equals `claimed` (the loop body of FastStark.verify) -- as a
+        row of `group`; a row the format cannot hold is decided by host() in `run`"""
+        group.add(owner, member, index, claimed, randomizer, zerofier, current, following, host)
+
+    def _run_combinations(self, ok):
+        def on_host(owner, host):
+            if ok[owner]:                        # (a proof that has failed already needs no further verdict)
+                try:
+                    accepted = host()
+                except Exception:
+                    accepted = False
+                if not accepted:
+                    ok[owner] = False
+        for group in self.combinations.values():
+            if not group:                        # (a group whose AIR the format does not hold: its proofs ran the host loop)
+                continue
+            for owner, host in group.host_only:
+                on_host(owner, host)
+            if not group.rows:
+                continue
+            if len(group.rows) < group.min_rows:
+                for owner, host in zip(group.owners, group.hosts):
+                    on_host(owner, host)
+                continue
+            verdicts = group.verdicts()
+            self.combination_device_rows += len(group.rows)
+            for t, verdict in enumerate(verdicts):
+                if verdict == _sc.UNDECIDED:
+                    on_host(group.owners[t], group.hosts[t])      # (the reference's own exception makes it False)
+                elif verdict != 1:
+                    ok[group.owners[t]] = False
+
     def run(self):
         """the device calls, then a proof's verdict: its host checks passed and every row of it passes"""
         import numpy as np
@@ -209,6 +319,7 @@ class BatchChecks:
                 except Exception:
                     col_verdicts[t] = 0
             ok[np.asarray(self.c_owner, dtype=np.int64)[col_verdicts != 1]] = False
+        self._run_combinations(ok)
         # Fri.verify appends round 0's pairs test by test and stops at the first failed colinearity test: the same prefix here
         for values, base, refs in self.truncations:
             for t, (where, what) in enumerate(refs):

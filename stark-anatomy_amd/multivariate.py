@@ -158,6 +158,13 @@ class MPolynomial:
             bound = max(bound, d)
         return bound, terms
 
+    @staticmethod
+    def pack_terms(term_lists):
+        """the constraint tables of sc_mpoly_eval_columns_dev and sc_stark_combination_batch from the term lists of value_domain_terms,
+        one per constraint: (terms per constraint, the [terms][nvars] exponent bytes, the packed coefficients)"""
+        return ([len(terms) for terms in term_lists], bytes(e for terms in term_lists for k, _ in terms for e in k),
+                b"".join(v.to_bytes(16, "little") for terms in term_lists for _, v in terms))
+
     def _evaluate_symbolic_value_domain(self, point):
         """The same polynomial computed pointwise: the point polynomials are evaluated on a power-of-two domain larger than
         the degree of the result (one zero-padded NTT each), the AIR is evaluated value by value (`mpoly_eval_kernel`), and

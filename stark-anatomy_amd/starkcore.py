@@ -128,6 +128,7 @@ SIGNATURES = {
     "sc_merkle_open_batch": (_int, [_vp, _vp, _u64, _vp]),
     "sc_merkle_verify_batch": (_int, [_vp, _u64, _vp, _u64, _vp, _u64, _vp]),
     "sc_fri_colinearity_batch": (_int, [_vp, _u64, _vp, _u64, _vp]),
+    "sc_stark_combination_batch": (_int, [_vp, _vp, _u64, _vp]),
     "sc_merkle_query_dev": (_int, [_vp, _vp, _vp, _u64, _vp, _vp]),
     "sc_merkle_query_multi_dev": (_int, [_u64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sc_merkle_level_copy_dev": (_int, [_vp, _int, _vp, _vp]),
@@ -558,6 +559,56 @@ def colinearity_batch(rows, rounds):
     out = np.zeros(len(rows), dtype=np.uint8)
     if len(rows):
         _check(lib().sc_fri_colinearity_batch(rows.ctypes.data, len(rows), rounds.ctypes.data, len(rounds), out.ctypes.data))
+    return out
+
+
+class _CombinationShared(ctypes.Structure):
+    """sc_combination_t of include/starkcore.h"""
+    _fields_ = [("registers", _u64), ("ncons", _u64), ("nterms", _vp), ("exps", _vp), ("coefs", _vp), ("generator", _u64 * 2), ("omega", _u64 * 2),
+                ("domain_length", _u64), ("step", _u64), ("transition_shifts", _vp), ("boundary_shifts", _vp), ("members", _u64), ("weights", _vp),
+                ("polys", _vp), ("pool", _vp), ("pool_len", _u64)]
+
+
+def combination_row_dtype(registers):
+    """a row of sc_stark_combination_batch for an AIR of `registers` registers (csrc/combination.cuh CombRowHead and its leaves)"""
+    import numpy as np
+    row = np.dtype([("member", "<u8"), ("index", "<u8"), ("claimed", "<u8", (2,)), ("randomizer", "<u8", (2,)), ("zerofier", "<u8", (2,)),
+                    ("current", "<u8", (registers, 2)), ("next", "<u8", (registers, 2))])
+    assert row.itemsize == 64 + 32 * registers
+    return row
+
+
+class Combination:
+    """What the rows of one sc_stark_combination_batch call share, as the C structure and the buffers it points into.  nterms: terms per
+    constraint; exps: their [terms][1 + 2 registers] exponent bytes; coefs, weights, pool: packed residues (16 bytes little-endian);
+    polys: per member and register (zerofier offset, length, interpolant offset, length) in elements of the pool."""
+
+    def __init__(self, registers, nterms, exps, coefs, generator, omega, domain_length, step, transition_shifts, boundary_shifts, members, weights, polys, pool):
+        import numpy as np
+        ncons = len(nterms)
+        # 16-byte elements in numpy arrays of their own: aligned, and alive as long as this object
+        as_words = lambda raw: np.frombuffer(bytes(raw), dtype="<u8").copy() if len(raw) else np.zeros(2, dtype="<u8")
+        self._keep = [np.asarray(list(nterms) or [0], dtype="<u8"), np.frombuffer(bytes(exps) or b"\0", dtype=np.uint8).copy(), as_words(coefs),
+                      np.asarray(list(transition_shifts) or [0], dtype="<u8"), np.asarray(list(boundary_shifts), dtype="<u8"), as_words(weights),
+                      np.ascontiguousarray(polys, dtype="<u8").reshape(-1), as_words(pool)]
+        at = [a.ctypes.data for a in self._keep]
+        self.registers = registers
+        self.struct = _CombinationShared(registers, ncons, at[0], at[1], at[2], (_u64 * 2)(*fe_words(generator)), (_u64 * 2)(*fe_words(omega)), domain_length, step,
+                                         at[3], at[4], members, at[5], at[6], at[7], len(pool) // 16)
+
+
+def fe_words(value):
+    return value & 0xFFFFFFFFFFFFFFFF, value >> 64
+
+
+def combination_batch(shared, rows):
+    """sc_stark_combination_batch: rows (an array of combination_row_dtype(shared.registers)) over a Combination -> uint8 verdicts (1 / 0,
+    UNDECIDED: the caller decides the row with the host loop)"""
+    import numpy as np
+    rows = np.ascontiguousarray(rows, dtype=combination_row_dtype(shared.registers))
+    out = np.zeros(len(rows), dtype=np.uint8)
+    if len(rows):
+        _check(lib().sc_stark_combination_batch(ctypes.byref(shared.struct), rows.ctypes.data, len(rows), out.ctypes.data))
     return out
 
 

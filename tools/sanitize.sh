@@ -2,7 +2,8 @@
 # Sanitizer builds.  `bash tools/sanitize.sh cpu` runs what needs no GPU; `... gpu <outdir>` runs on the GPU box
 # (gpurun -- 'bash tools/sanitize.sh gpu gpurun_out/<dir>').  Clean logs are kept under profiles/.
 #   cpu:  oracle/stark_oracle.c (gcc), tests/emu/ntt_emu.cpp (g++; the kernels' round bodies, the planner, field.cuh on the
-#         host) and tests/emu/plan_dump.cpp (the planner over its grid of cases) under ASan + UBSan against their test suites; the HOST side of libstarkcore.so (hipcc -fsanitize=address,undefined:
+#         host) and tests/emu/plan_dump.cpp (the planner over its grid of cases) under ASan + UBSan against their test suites;
+#         tests/emu/combination_emu.cpp (the verifier's combination rows) as a stand-alone program under ASan + UBSan; the HOST side of libstarkcore.so (hipcc -fsanitize=address,undefined:
 #         device code is not instrumented) against the host-only suites: transcript, proof pickler, ABI
 #   gpu:  the same ASan + UBSan library under the C-ABI parity tests and the Fri / FastStark host tests, tools/thread_stress.py;
 #         a ThreadSanitizer build under tools/thread_stress.py (three prover threads in one process).
@@ -43,6 +44,8 @@ if [ "$MODE" = cpu ]; then
   LD_PRELOAD=$GCC_RT STARK_ORACLE_LIB=$LIBS/libstark_oracle_san.so NTT_EMU_LIB=$LIBS/libntt_emu_san.so timeout 2400 python -m pytest tests/test_emu.py -x -q 2>&1 | tail -4 || status=1
   echo "== planner equivalence (g++, ASan + UBSan): tests/test_ntt_plans.py"
   NTT_PLAN_CXXFLAGS="-O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer" timeout 600 python -m pytest tests/test_ntt_plans.py -x -q 2>&1 | tail -4 || status=1
+  echo "== combination rows, the kernels' walk as a stand-alone program (g++, ASan + UBSan): tests/test_combination_emu.py -k standalone"
+  COMBINATION_EMU_CXXFLAGS="-O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer" timeout 600 python -m pytest tests/test_combination_emu.py -k standalone -x -q 2>&1 | tail -4 || status=1
   echo "== libstarkcore.so host side (hipcc, ASan + UBSan): tests/test_proof_pickle.py tests/test_host_cpu.py tests/test_abi.py"
   build_lib address,undefined $LIBS/libstarkcore_san.so || status=1
   LD_PRELOAD=$CLANG_RT STARKCORE_LIB=$LIBS/libstarkcore_san.so timeout 1500 python -m pytest tests/test_proof_pickle.py tests/test_host_cpu.py tests/test_abi.py -x -q 2>&1 | tail -4 || status=1
