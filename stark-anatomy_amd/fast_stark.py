@@ -381,6 +381,9 @@ class FastStark:
         if on_device:
             transition_quotients = self._transition_quotients_on_device(transition_constraints, point, self._lift(transition_zerofier), pending, batched)
         else:
+            if isinstance(transition_zerofier, DevicePolynomial):
+                # preprocess(device_resident=True) with a trace shorter than DEVICE_MIN: the host-list data flow divides host polynomials
+                transition_zerofier = transition_zerofier.to_polynomial()
             transition_polynomials = [a.evaluate_symbolic(point) for a in transition_constraints]
             transition_quotients = [fast_coset_divide(tp, transition_zerofier, self.generator, self.omicron, self.omicron_domain_length) for tp in transition_polynomials]
 

@@ -6,7 +6,8 @@ runs this.  Output: small JSON fixtures next to this file.  Only DATA is written
 regenerated from seeds, outputs stored in full for small sizes and as SHA-256 of the packed
 16-byte-LE output for larger ones).  No reference source is copied.
 
-usage:  python tests/golden/make_golden.py [--big] [--fri-big] [--host-mirror] [--stark-synth [log_fri:s:seed ...]]     (--big adds 2^18 / 2^20 NTT digests, --fri-big 2^14 and 2^16 Fri.prove runs; minutes)
+usage:  python tests/golden/make_golden.py [--big] [--fri-big] [--host-mirror] [--stark-synth [log_fri:s:seed ...]] [--expansion]     (--big adds 2^18 / 2^20 NTT digests, --fri-big 2^14 and 2^16 Fri.prove runs; minutes)
+        --expansion writes expansion.json alone: proofs at expansion factors other than 4; 178 s of reference time in all (the sum of its reference_seconds), under 4 minutes with the rest
 """
 import hashlib
 import json
@@ -439,9 +440,136 @@ def gen_stark_synth(cases):
         dump("fast_stark_synth.json", out)
 
 
+def gen_expansion():
+    """Proofs at expansion factors other than 4 (every other golden file records 4): num_rounds, Fri.prove of an honest codeword and
+    of one whose polynomial has one coefficient too many, and FastStark proofs -- the synthetic AIR, Rescue-Prime, a wide trace (by
+    make_wide_golden.py) -- with the reference's verdicts on the proof, on a false boundary claim and on altered proofs.  The
+    instances are those of tests/expansion_cases.py, built here with the reference's classes.  Written to expansion.json."""
+    import fast_stark as ref_fast_stark
+    import multivariate as ref_multivariate
+    import rescue_prime as ref_rp
+    sys.path.insert(2, os.path.join(REPO, "tests"))
+    sys.path.insert(2, HERE)
+    import expansion_cases
+    import make_wide_golden
+    assert ref_fast_stark.__file__.startswith(REF) and ref_multivariate.__file__.startswith(REF)
+    out = {"num_rounds": [], "fri": [], "stark": []}
+
+    t0 = time.time()
+    # ef stops the loop: (64, 2, 1) (1024, 16, 2) (2048, 32, 4) (8192, 8, 1) (128, 32, 2) (1 << 15, 1 << 12, 2) (1 << 16, 16, 3);
+    # 4 s does: (256, 2, 3) (1024, 8, 5) (1024, 64, 33) (512, 16, 40) (1 << 20, 2, 40); both at once: (1024, 64, 16)
+    for n, ef, s in [(64, 2, 1), (256, 2, 3), (1024, 8, 5), (1024, 16, 2), (2048, 32, 4), (8192, 8, 1), (8192, 8, 2), (128, 32, 2), (1024, 64, 3),
+                     (1024, 64, 33), (1024, 64, 16), (512, 16, 40), (1 << 15, 1 << 12, 2), (1 << 16, 16, 8), (1 << 20, 2, 40)]:
+        out["num_rounds"].append([n, ef, s, ref_fri.Fri(field.generator(), field.primitive_nth_root(n), n, ef, s).num_rounds()])
+    out["num_rounds_reference_seconds"] = round(time.time() - t0, 3)
+
+    # (logN, ef, s, seed, does the reference's verify finish).  The last shape's last codeword has 8192 elements -- past the
+    # 4096 that travel through the tail kernel's pinned block; the reference's verifier interpolates it by Lagrange's formula
+    # (hours), so only its proofs are recorded.
+    shapes = [(6, 2, 1, 5000, True), (8, 2, 3, 5001, True), (10, 8, 5, 5002, True), (10, 16, 2, 5003, True), (11, 32, 4, 5004, True), (13, 8, 2, 5005, True),
+              (7, 32, 2, 5006, True), (10, 64, 3, 5007, True), (9, 16, 40, 5008, True), (16, 16, 8, 5009, True), (15, 1 << 12, 2, 5010, False)]
+    for logN, ef, s, seed, verifiable in shapes:
+        N = 1 << logN
+        om = field.primitive_nth_root(N)
+        fr = ref_fri.Fri(field.generator(), om, N, ef, s)
+        nr = fr.num_rounds()
+        for honest in (True, False):
+            count = N // ef + (0 if honest else 1)
+            coeffs = fes(seed + (0 if honest else 100), count)
+            assert not coeffs[-1].is_zero()
+            cw = ref_ntt.fast_coset_evaluate(Polynomial(coeffs), field.generator(), om, N)
+            ps = ref_ip.ProofStream()
+            t0 = time.time()
+            top = fr.prove(cw, ps)
+            t1 = time.time()
+            ser = ps.serialize()
+            verdict = fr.verify(ref_ip.ProofStream().deserialize(ser), []) if verifiable else None
+            t2 = time.time()
+            assert verdict in (None, honest), (logN, ef, s, honest, verdict)
+            upto = ref_ip.ProofStream()                  # the transcript the indices are drawn from (fri.py:122): the roots and the last codeword
+            upto.objects = ps.objects[:nr + 1]
+            last = ps.objects[nr]
+            out["fri"].append({
+                "indices_seed": upto.prover_fiat_shamir().hex(), "last_codeword": vals(last) if len(last) <= 64 else None,
+                "logN": logN, "num_colinearity_tests": s, "expansion_factor": ef, "coeff_seed": seed + (0 if honest else 100), "num_coeffs": count,
+                "honest": honest, "num_rounds": nr, "codeword_sha256": sha_packed(cw), "top_level_indices": top, "num_objects": len(ps.objects),
+                "serialized_len": len(ser), "serialized_sha256": hashlib.sha256(ser).hexdigest(), "roots": [o.hex() for o in ps.objects[:nr]],
+                "last_codeword_len": len(ps.objects[nr]), "last_codeword_sha256": sha_packed(ps.objects[nr]), "verifies": verdict,
+                "reference_seconds": {"prove": round(t1 - t0, 2), "verify": round(t2 - t1, 2) if verifiable else None}})
+            print("fri logN", logN, "ef", ef, "s", s, "honest" if honest else "one coefficient more", "prove %.1fs verify %.1fs" % (t1 - t0, t2 - t1), verdict, flush=True)
+
+    def verdict_of(stark, proof, air, boundary, tzr):
+        try:
+            return stark.verify(proof, air, boundary, tzr) == True      # noqa: E712
+        except AssertionError:
+            return False
+
+    def describe(stark, proof, air, boundary, tzr, top):
+        """the reference's verdicts on the false boundary claim and on the altered proofs"""
+        import pickle
+        t0 = time.time()
+        objects = pickle.loads(proof)
+        places = expansion_cases.alteration_places(len(objects), stark.num_registers, stark.expansion_factor, stark.fri_domain_length, top)
+        for place in places:
+            place["verifies"] = verdict_of(stark, pickle.dumps(expansion_cases.altered(objects, place, field.one())), air, boundary, tzr)
+        bad = verdict_of(stark, proof, air, expansion_cases.false_claim(boundary, field.one()), tzr)
+        return {"top_level_indices": top, "num_objects": len(objects), "false_claim_verifies": bad, "alterations": places,
+                "reference_alterations_seconds": round(time.time() - t0, 1)}
+
+    def stark_record(kind, ef, s_checks, sec, seed, registers, cycles, trace, air_of, boundary, extra):
+        rng = random.Random(seed)
+        ref_fast_stark.os.urandom = lambda k, rng=rng: bytes(rng.getrandbits(8) for _ in range(k))
+        stark = ref_fast_stark.FastStark(field, ef, s_checks, sec, registers, cycles)
+        sampled, fri_prove = [], stark.fri.prove
+        stark.fri.prove = lambda codeword, proof_stream: (sampled.append(fri_prove(codeword, proof_stream)), sampled[-1])[1]
+        air = air_of(stark)
+        t0 = time.time()
+        tz, tzc, tzr = stark.preprocess()
+        t1 = time.time()
+        proof = stark.prove(trace, air, boundary, tz, tzc)
+        t2 = time.time()
+        ok = stark.verify(proof, air, boundary, tzr)
+        t3 = time.time()
+        ps = ref_ip.ProofStream().deserialize(proof)
+        rec = dict(extra)
+        rec.update({"kind": kind, "registers": registers, "num_colinearity_checks": s_checks, "urandom_seed": seed, "expansion_factor": ef, "security_level": sec,
+                    "original_trace_length": cycles, "omicron_domain_length": stark.omicron_domain_length, "fri_domain_length": stark.fri_domain_length,
+                    "zerofier_coeffs_sha256": sha_packed(tz.coefficients), "zerofier_root": tzr.hex(), "proof_len": len(proof),
+                    "proof_sha256": hashlib.sha256(proof).hexdigest(), "first_roots": [o.hex() for o in ps.objects[:registers + 1]], "verifies": ok})
+        rec.update(describe(stark, proof, air, boundary, tzr, sampled[0]))
+        rec["reference_seconds"] = {"preprocess": round(t1 - t0, 1), "prove": round(t2 - t1, 1), "verify": round(t3 - t2, 1),
+                                    "false_claim_and_alterations": rec.pop("reference_alterations_seconds")}
+        print(kind, extra, "ef", ef, "s", s_checks, "seed", seed, rec["reference_seconds"], ok, rec["false_claim_verifies"], [a["verifies"] for a in rec["alterations"]], flush=True)
+        out["stark"].append(rec)
+
+    for log_fri, ef, s_checks, seed in [(10, 8, 4, 51), (11, 16, 2, 52), (12, 8, 8, 53), (14, 16, 4, 54)]:
+        _, T, _, rows, air, boundary = expansion_cases.synthetic_instance(log_fri, ef, s_checks, ref_algebra, ref_multivariate)
+        stark_record("synthetic", ef, s_checks, 2 * s_checks, seed, 2, T, rows, lambda stark, air=air: air, boundary, {"log_fri": log_fri})
+    rp = ref_rp.RescuePrime()
+    input_element = field.sample(b"0xdeadbeef")
+    output_element = rp.hash(input_element)
+    for ef, s_checks, seed in [(8, 2, 61), (16, 3, 62)]:
+        stark_record("rescue_prime", ef, s_checks, 2, seed, rp.m, rp.N + 1, rp.trace(input_element), lambda stark: rp.transition_constraints(stark.omicron),
+                     rp.boundary_constraints(output_element), {"input": str(input_element.value), "output": str(output_element.value)})
+    # the wide trace: make_wide_golden.py's instance and record, with the verdicts added
+    rec = make_wide_golden.prove_with_reference(11, 8, 4, 71, ef=8, describe=describe)
+    rec["kind"] = "wide"
+    rec["reference_seconds"] = {"prove": rec.pop("reference_prove_seconds"), "false_claim_and_alterations": rec.pop("reference_alterations_seconds")}
+    print("wide", rec["reference_seconds"], rec["verifies"], rec["false_claim_verifies"], [a["verifies"] for a in rec["alterations"]], flush=True)
+    out["stark"].append(rec)
+
+    def seconds(node):
+        return sum(seconds(v) for v in node.values()) if isinstance(node, dict) else (node or 0)
+    out["reference_seconds_total"] = round(out["num_rounds_reference_seconds"] + sum(seconds(r["reference_seconds"]) for r in out["fri"] + out["stark"]), 1)
+    print("reference time in all: %.1f s" % out["reference_seconds_total"])
+    dump("expansion.json", out)
+
+
 if __name__ == "__main__":
     big = "--big" in sys.argv
-    if "--fri-big" in sys.argv:
+    if "--expansion" in sys.argv:
+        gen_expansion()
+    elif "--fri-big" in sys.argv:
         gen_fri()                  # fri.json again, with the 2^14 proof (the other records are reproduced identically)
     elif "--stark-synth" in sys.argv:
         # --stark-synth [log_fri:s:seed ...]; default: the sizes that take minutes in all

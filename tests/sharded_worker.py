@@ -297,17 +297,24 @@ def fri_main():
     from ip import ProofStream
     rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
     dist.init_process_group("gloo", rank=rank, world_size=world)
-    golden = json.load(open(os.path.join(REPO, "tests", "golden", "fri.json")))
+    if "expansion" in sys.argv[2:]:
+        # one record at another expansion factor (tests/golden/expansion.json): 2^10 points, expansion factor 8, 5 tests
+        records = [r for r in json.load(open(os.path.join(REPO, "tests", "golden", "expansion.json")))["fri"]
+                   if (r["logN"], r["expansion_factor"], r["honest"]) == (10, 8, True)]
+        assert len(records) == 1
+    else:
+        records = json.load(open(os.path.join(REPO, "tests", "golden", "fri.json")))["prove_synth"]
     field = Field.main()
     ok = True
-    for rec in golden["prove_synth"]:
+    for rec in records:
         logN = rec["logN"]
         if logN > 10:
             continue
         N = 1 << logN
         om = field.primitive_nth_root(N)
-        coeffs = synth.synth_packed(rec["coeff_seed"], N // 4).tobytes()
-        cw = np.frombuffer(po.C.coset_evaluate(coeffs, N // 4, po.GENERATOR, om.value, N), dtype=np.int64).reshape(N, 2)
+        count = rec.get("num_coeffs", N // 4)
+        coeffs = synth.synth_packed(rec["coeff_seed"], count).tobytes()
+        cw = np.frombuffer(po.C.coset_evaluate(coeffs, count, po.GENERATOR, om.value, N), dtype=np.int64).reshape(N, 2)
         for logR in ({6: (2, 3), 10: (3, 5, 8)}[logN]):
             R = 1 << logR
             if R < world:
@@ -460,10 +467,16 @@ def stark_main():
             a = tensor.contiguous().numpy().view(np.uint64).reshape(-1, 2)
             return poly(int(a[i, 0]) | (int(a[i, 1]) << 64) for i in range(length))
 
-    golden = json.load(open(os.path.join(REPO, "tests", "golden", "fast_stark.json")))
+    if "expansion" in sys.argv[2:]:
+        # one record at another expansion factor (tests/golden/expansion.json): Rescue-Prime at expansion factor 8
+        records = [r for r in json.load(open(os.path.join(REPO, "tests", "golden", "expansion.json")))["stark"]
+                   if (r["kind"], r["expansion_factor"]) == ("rescue_prime", 8)]
+        assert len(records) == 1
+    else:
+        records = json.load(open(os.path.join(REPO, "tests", "golden", "fast_stark.json")))["runs"]
     rp = RescuePrime()
     ok = True
-    for rec in golden["runs"]:
+    for rec in records:
         rng = random.Random(rec["urandom_seed"])
         fast_stark.os.urandom = lambda k, rng=rng: bytes(rng.getrandbits(8) for _ in range(k))
         input_element = FieldElement(int(rec["input"]), field)

@@ -54,6 +54,20 @@ def test_sharded_stark_prover_gloo_matches_reference_proofs(world):
     assert r.stdout.count("ok") == world
 
 
+@pytest.mark.parametrize("world", [1, 2])
+@pytest.mark.parametrize("what", ["fri", "stark"])
+def test_sharded_provers_gloo_at_another_expansion_factor(what, world):
+    """The two tests above on one record each of tests/golden/expansion.json -- the reference's Fri.prove at 2^10 points with expansion
+    factor 8, and its FastStark proof of the Rescue-Prime workload at expansion factor 8: the FRI-to-trace domain ratio, the
+    companion openings at index + 8 and the last codeword's length are the sharded provers' own, and the bytes are the reference's."""
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), OMP_NUM_THREADS="1")
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
+           "--master-port", env["MASTER_PORT"], os.path.join(REPO, "tests", "sharded_worker.py"), what, "expansion"]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-4000:]
+    assert r.stdout.count("ok") == world
+
+
 @pytest.mark.parametrize("case", ["no_gpu", "all_children_pass", "one_child_dies"])
 def test_direct_store_preflight_agreement_gloo(case, tmp_path):
     """sharded_setup.direct_store_preflight (the children that try the direct-store corner turn's ingredients before any rank does): the
