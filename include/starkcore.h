@@ -71,7 +71,7 @@ int sc_stream_join(void* other_stream);
  * batch kernels correct by +-p on two limbs and an exact kernel redoes the tiles they flag, 0: exact arithmetic on every tile, 2: both
  * kernels on every tile (a test hook) -- see sc_ntt_columns_dev; "div_cols_chunk" = columns that share one batch inversion in
  * sc_pointwise_div_columns_later_dev / sc_coset_divide_columns_later_dev with a shared divisor, 0 = chosen by shape; "div_cols_launch_log" = log2 of the values
- * one set of launches of sc_coset_divide_columns_later_dev takes, 26 by default and at most, at least 1: a test hook that makes the entry
+ * one set of launches of sc_coset_divide_columns_later_dev (and of sc_poly_divmod_columns_dev) takes, 26 by default and at most, at least 1: a test hook that makes the entry
  * work through a small matrix in several chunks of columns; "tree_cols_launch_log" = log2 of the elements one temporary of a set of columns of
  * sc_polytree_evaluate_columns_dev / sc_polytree_interpolate_columns_dev holds, 26 by default and at most, at least 1: a test hook that
  * makes those entries work through their columns in several sets).  Two keys manage the device-memory pool instead (freed vectors and trees are kept
@@ -273,6 +273,25 @@ int sc_coset_divide_columns_later_dev(const void* d_a, uint64_t na, uint64_t ld_
                                       uint64_t cols, const uint64_t offset[2], const uint64_t root[2], uint64_t order,
                                       void* d_out, const uint64_t* n_out /* host, cols entries */, uint64_t ld_out,
                                       sc_later_t** later, void* stream);
+/* ---- division with remainder : code/univariate.py:80-97 (Polynomial.divide) ------------------- */
+/* a = q * b + r for a of na and b of nb coefficients, b[nb-1] != 0 and na >= nb >= 1: q gets na - nb + 1 coefficients (zero on top
+ * where a's top coefficients are zero), r gets nb - 1.  No coset, no transform order to pass, any divisor -- monic or not, with roots
+ * anywhere: rev(b) is inverted as a power series by Newton doubling, rev(q) = rev(a) * rev(b)^-1 mod y^(na-nb+1), and r = a - q * b
+ * is formed cyclically at the divisor's size (csrc/polydiv.cuh).  q == NULL: no quotient is stored; r == NULL: no remainder is
+ * computed (that step is skipped); both NULL: SC_ERR_BAD_ARG.  nb == 1 divides by the constant (r has no coefficients).
+ * SC_ERR_BAD_ARG, before anything is enqueued: nb == 0, na < nb, na > 2^31, a pitch below what is stored per column, outputs that
+ * overlap an operand or each other.  SC_ERR_DIV_ZERO: b[nb-1] == 0 (the one value the call reads back, before any work is enqueued:
+ * nothing is written to q or r).  The host form is synchronous; the _dev forms wait for that one value and enqueue the rest. */
+int sc_poly_divmod(const void* a, uint64_t na, const void* b, uint64_t nb, void* q /* na-nb+1 */, void* r /* nb-1 */);
+int sc_poly_divmod_dev(const void* d_a, uint64_t na, const void* d_b, uint64_t nb, void* d_q, void* d_r, void* stream);
+/* The same for `cols` numerators that are columns of one matrix (column c: na coefficients at element c * ld_a) and ONE divisor: the
+ * series and the divisor's transform are computed once, every transform and every kernel runs once per set of columns
+ * (sc_set_tuning("div_cols_launch_log") values per set).  Column c's na - nb + 1 quotient coefficients go to element c * ld_q of d_q,
+ * its nb - 1 remainder coefficients to element c * ld_r of d_r; nothing between the columns is written.  cols == 0: SC_OK, nothing
+ * happens.  The temporaries are the call's own (returned to the pool behind the streams in use): no shared scratch, no one-stream rule. */
+int sc_poly_divmod_columns_dev(const void* d_a, uint64_t na, uint64_t ld_a, uint64_t cols,
+                               const void* d_b, uint64_t nb,            /* ONE divisor for all columns */
+                               void* d_q, uint64_t ld_q, void* d_r, uint64_t ld_r, void* stream);
 /* Polynomial.degree (code/univariate.py:7-17) of a coefficient vector in HBM: index of the last non-zero entry, -1 if none (synchronous) */
 int sc_vec_degree_dev(const void* d_v, uint64_t n, int64_t* degree_out, void* stream);
 /* The same for `cols` vectors of n entries each, column c at element c * ld of d_v (ld >= n; entries between the columns are not

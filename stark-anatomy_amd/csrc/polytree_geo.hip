@@ -3,6 +3,7 @@
 #include "core.h"
 #include "polytree.cuh"
 #include "geoseq.cuh"
+#include "polydiv.cuh"
 
 namespace sci {
 
@@ -698,6 +699,137 @@ int geodomain_evaluate_columns(const sc_geodomain* d, const Fe* coeffs, uint64_t
 
 }  // namespace
 
+// ============================================================================ division with remainder (polydiv.cuh)
+
+namespace {
+
+// a of na, b of nb coefficients: m quotient and nr remainder coefficients, and the transforms of the three steps
+struct PolyDivShape {
+    uint64_t na, nb, m, nr;
+    uint64_t g;            // coefficients of rev(b) that matter: min(nb, m)
+    int logP;              // Newton runs to P = 2^logP >= m coefficients (its largest transform: 2P)
+    int log2, log3;        // rev(a) h at n2 = 2^log2 >= 2m - 1;  q b mod (x^n3 - 1) at n3 = 2^log3 >= nb   (both at least 2)
+};
+
+inline bool pd_overlap(const void* x, uint64_t nx, const void* y, uint64_t ny) {
+    const uintptr_t x0 = (uintptr_t)x, x1 = x0 + nx * sizeof(Fe), y0 = (uintptr_t)y, y1 = y0 + ny * sizeof(Fe);
+    return x && y && nx && ny && x0 < y1 && y0 < x1;
+}
+
+// everything sc_poly_divmod* refuses before anything is enqueued (the leading coefficient is looked at by polydiv_columns)
+int polydiv_args(const void* d_a, uint64_t na, uint64_t ld_a, uint64_t cols, const void* d_b, uint64_t nb, const void* d_q, uint64_t ld_q, const void* d_r, uint64_t ld_r,
+                 PolyDivShape* out) {
+    if (!d_a || !d_b) return fail(SC_ERR_BAD_ARG, "null argument");
+    if (!d_q && !d_r) return fail(SC_ERR_BAD_ARG, "neither quotient nor remainder asked for");
+    if (nb == 0) return fail(SC_ERR_BAD_ARG, "empty divisor");
+    if (na < nb) return fail(SC_ERR_BAD_ARG, "numerator shorter than the divisor");
+    PolyDivShape s;
+    s.na = na; s.nb = nb; s.m = na - nb + 1; s.nr = nb - 1;
+    s.g = nb < s.m ? nb : s.m;
+    if (na > (1ull << 31)) return fail(SC_ERR_BAD_ARG, "operand longer than the transforms take");
+    s.logP = ilog2(s.m);
+    s.log2 = std::max(1, ilog2(2 * s.m - 1));
+    s.log3 = std::max(1, ilog2(nb));
+    if (s.logP + 1 > 32 || s.log2 > 32 || s.log3 > 32) return fail(SC_ERR_BAD_ARG, "operand longer than the transforms take");
+    if (ld_a < na || (d_q && ld_q < s.m) || (d_r && ld_r < s.nr)) return fail(SC_ERR_BAD_ARG, "a column stride below the column length");
+    if (cols) {
+        const uint64_t ea = (cols - 1) * ld_a + na, eq = (cols - 1) * ld_q + s.m, er = (cols - 1) * ld_r + s.nr;
+        if (pd_overlap(d_q, eq, d_a, ea) || pd_overlap(d_q, eq, d_b, nb) || pd_overlap(d_r, er, d_a, ea) || pd_overlap(d_r, er, d_b, nb) || pd_overlap(d_q, eq, d_r, er))
+            return fail(SC_ERR_BAD_ARG, "the outputs may not overlap the operands or each other");
+    }
+    *out = s;
+    return SC_OK;
+}
+
+// h = rev(b)^-1 mod y^m in hbuf (2P entries, P >= m of them valid; one entry for a constant divisor): b[nb-1]^-1, then logP
+// Newton steps, step lm at transform size 4 * 2^lm like polytree_inverse_series.  G, H, T: min(nb, m) and 2P and 2P entries.
+int polydiv_inverse_series(const Fe* d_b, const PolyDivShape& s, Fe lead_inv, Fe* G, Fe* hbuf, Fe* H, Fe* T, hipStream_t st) {
+    hipLaunchKernelGGL(pt_fill_kernel, dim3(1), dim3(256), 0, st, hbuf, (uint64_t)1, lead_inv);
+    if (s.nb == 1) return SC_OK;                          // a constant: its inverse is the whole series
+    if (s.logP) hipLaunchKernelGGL(pd_rev_kernel, dim3(pt_blocks(s.g)), dim3(256), 0, st, d_b, (uint64_t)0, s.nb - 1, s.g, G, (uint64_t)0);
+    for (int lm = 0; lm < s.logP; ++lm) {                 // 2^lm known coefficients -> 2^(lm+1)
+        const int logn = lm + 2;
+        const uint64_t n = 1ull << logn, have = 1ull << lm;
+        const Fe rt = canonical_root(logn);
+        NttOpts o;
+        o.in_limit = have;
+        SCCHK(ntt_device(hbuf, H, logn, rt, false, o, st));
+        o.in_limit = 2 * have < s.g ? 2 * have : s.g;
+        SCCHK(ntt_device(G, T, logn, rt, false, o, st));
+        hipLaunchKernelGGL(pt_newton_kernel, dim3(pt_blocks(n)), dim3(256), 0, st, H, (const Fe*)T, n, ninv_scaled(logn, 3));
+        SCCHK(ntt_device(H, hbuf, logn, root_inverse(rt, n), false, NttOpts(), st));
+    }
+    HIPCHK(hipGetLastError());
+    return SC_OK;
+}
+
+// the three steps for `cols` columns and ONE divisor: the series and the two tables once, every transform and every kernel once
+// per set of columns (div_cols_launch_log values per temporary, at most 65 535 columns: grid.y).  Temporaries are the call's own.
+int polydiv_columns(const Fe* d_a, uint64_t ld_a, uint64_t cols, const Fe* d_b, Fe* d_q, uint64_t ld_q, Fe* d_r, uint64_t ld_r, const PolyDivShape& s, hipStream_t st) {
+    Fe lead;
+    SCCHK(read_small_polled(d_b + (s.nb - 1), sizeof(Fe), st, &lead));
+    if (fe_is_zero(lead)) return fail(SC_ERR_DIV_ZERO, "divide by zero");
+    if (fe_ge_p(lead)) return fail(SC_ERR_BAD_ARG, "leading coefficient is not a canonical residue");
+    const Fe lead_inv = from_mont(mont_inv(to_mont(lead)));
+    const bool with_r = d_r && s.nr;
+    if (!with_r && !d_q) return SC_OK;                    // the remainder of a division by a constant: no coefficients
+    const uint64_t n2 = 1ull << s.log2, n3 = 1ull << s.log3, P = 1ull << s.logP, wide = with_r && n3 > n2 ? n3 : n2;
+    uint64_t per = (1ull << g.div_cols_launch_log) / wide;
+    if (per < 1) per = 1;
+    if (per > 65535) per = 65535;
+    if (per > cols) per = cols;
+    PoolTmpAsync G, hbuf, H, T, Hf, Bf, X, Y;
+    SCCHK(G.get(s.g * sizeof(Fe)));
+    SCCHK(hbuf.get(2 * P * sizeof(Fe)));
+    SCCHK(H.get(2 * P * sizeof(Fe)));
+    SCCHK(T.get(2 * P * sizeof(Fe)));
+    SCCHK(Hf.get(n2 * sizeof(Fe)));
+    if (with_r) SCCHK(Bf.get(n3 * sizeof(Fe)));
+    SCCHK(X.get(per * wide * sizeof(Fe)));
+    SCCHK(Y.get(per * wide * sizeof(Fe)));
+    SCCHK(polydiv_inverse_series(d_b, s, lead_inv, G.fe(), hbuf.fe(), H.fe(), T.fe(), st));
+    const Fe rt2 = canonical_root(s.log2), rt3 = canonical_root(s.log3);
+    NttOpts o;
+    o.in_limit = s.nb == 1 ? 1 : s.m;
+    SCCHK(ntt_device(hbuf.fe(), Hf.fe(), s.log2, rt2, false, o, st));
+    if (with_r) {
+        o.in_limit = s.nb;
+        SCCHK(ntt_device(d_b, Bf.fe(), s.log3, rt3, false, o, st));
+    }
+    for (uint64_t done = 0; done < cols; done += per) {
+        const unsigned k = (unsigned)(cols - done < per ? cols - done : per);
+        const Fe* a = d_a + done * ld_a;
+        Fe* q = d_q ? d_q + done * ld_q : nullptr;
+        // rev(q) = rev(a)[0..m) h mod y^m: columns of X at pitch n2
+        hipLaunchKernelGGL(pd_rev_kernel, dim3(pt_blocks(s.m), k), dim3(256), 0, st, a, ld_a, s.na - 1, s.m, X.fe(), n2);
+        NttOpts oc;
+        oc.cols = k;
+        oc.in_limit = s.m;
+        SCCHK(ntt_device(X.fe(), Y.fe(), s.log2, rt2, false, oc, st));
+        hipLaunchKernelGGL(pd_mul_tab_kernel, dim3(pt_blocks(n2), k), dim3(256), 0, st, Y.fe(), n2, (const Fe*)Hf.fe(), n2, ninv_scaled(s.log2, 2));
+        oc.in_limit = ~0ull;
+        SCCHK(ntt_device(Y.fe(), X.fe(), s.log2, root_inverse(rt2, n2), false, oc, st));
+        if (!with_r) {
+            hipLaunchKernelGGL(pd_rev_kernel, dim3(pt_blocks(s.m), k), dim3(256), 0, st, (const Fe*)X.fe(), n2, s.m - 1, s.m, q, ld_q);
+            HIPCHK(hipGetLastError());
+            continue;
+        }
+        // r = a - q b mod (x^n3 - 1): q folded into Y at pitch n3 (and stored), the product back in Y
+        const uint64_t nf = s.m < n3 ? s.m : n3;
+        hipLaunchKernelGGL(pd_fold_rev_kernel, dim3(pt_blocks(nf), k), dim3(256), 0, st, (const Fe*)X.fe(), n2, s.m, n3, Y.fe(), n3, q, ld_q);
+        oc.in_limit = nf;
+        SCCHK(ntt_device(Y.fe(), X.fe(), s.log3, rt3, false, oc, st));
+        hipLaunchKernelGGL(pd_mul_tab_kernel, dim3(pt_blocks(n3), k), dim3(256), 0, st, X.fe(), n3, (const Fe*)Bf.fe(), n3, ninv_scaled(s.log3, 2));
+        oc.in_limit = ~0ull;
+        SCCHK(ntt_device(X.fe(), Y.fe(), s.log3, root_inverse(rt3, n3), false, oc, st));
+        hipLaunchKernelGGL(pd_remainder_kernel, dim3(pt_blocks(s.nr), k), dim3(256), 0, st, a, ld_a, s.na, (const Fe*)Y.fe(), n3, n3, d_r + done * ld_r, ld_r, s.nr);
+        HIPCHK(hipGetLastError());
+    }
+    return SC_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 // ---- subproduct tree: fast_zerofier / fast_evaluate / fast_interpolate
@@ -948,6 +1080,46 @@ int sc_geodomain_free(sc_geodomain_t* domain) {
     std::lock_guard<std::mutex> lk(g_mu);
     geodomain_release(domain);
     return SC_OK;
+}
+
+// ---- division with remainder (polydiv.cuh): Polynomial.divide, code/univariate.py:80-97
+int sc_poly_divmod_columns_dev(const void* d_a, uint64_t na, uint64_t ld_a, uint64_t cols, const void* d_b, uint64_t nb, void* d_q, uint64_t ld_q, void* d_r, uint64_t ld_r,
+                               void* stream) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    PolyDivShape s;
+    SCCHK(polydiv_args(d_a, na, ld_a, cols, d_b, nb, d_q, ld_q, d_r, ld_r, &s));
+    if (cols == 0) return SC_OK;
+    return polydiv_columns((const Fe*)d_a, ld_a, cols, (const Fe*)d_b, (Fe*)d_q, ld_q, (Fe*)d_r, ld_r, s, pick_stream(stream));
+}
+int sc_poly_divmod_dev(const void* d_a, uint64_t na, const void* d_b, uint64_t nb, void* d_q, void* d_r, void* stream) {
+    return sc_poly_divmod_columns_dev(d_a, na, na, 1, d_b, nb, d_q, na - nb + 1, d_r, nb ? nb - 1 : 0, stream);
+}
+int sc_poly_divmod(const void* a, uint64_t na, const void* b, uint64_t nb, void* q, void* r) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    if (!a || !b || (!q && !r)) return fail(SC_ERR_BAD_ARG, "null argument");
+    if (nb == 0 || na < nb) return fail(SC_ERR_BAD_ARG, nb ? "numerator shorter than the divisor" : "empty divisor");
+    const uint64_t m = na - nb + 1, nr = nb - 1;
+    PoolTmp ops, res;
+    SCCHK(ops.get((na + nb) * sizeof(Fe)));
+    SCCHK(res.get((m + nr) * sizeof(Fe)));
+    Fe *da = ops.fe(), *db = da + na, *dq = res.fe(), *dr = dq + m;
+    PolyDivShape s;
+    SCCHK(polydiv_args(da, na, na, 1, db, nb, q ? dq : nullptr, m, r ? dr : nullptr, nr, &s));
+    hipStream_t st = g.stream;
+    // (a failure behind an upload waits for the stream: the host buffers are the caller's, the pool buffers go back on return)
+    auto run = [&]() -> int {
+        SCCHK(upload(da, a, na * sizeof(Fe), st));
+        SCCHK(upload(db, b, nb * sizeof(Fe), st));
+        SCCHK(polydiv_columns(da, na, 1, db, q ? dq : nullptr, m, r ? dr : nullptr, nr, s, st));
+        if (q) HIPCHK(hipMemcpyAsync(q, dq, m * sizeof(Fe), hipMemcpyDeviceToHost, st));
+        if (r && nr) HIPCHK(hipMemcpyAsync(r, dr, nr * sizeof(Fe), hipMemcpyDeviceToHost, st));
+        return SC_OK;
+    };
+    const int rc = run();
+    if (hipStreamSynchronize(st) != hipSuccess && rc == SC_OK) return fail(SC_ERR_HIP, "division with remainder failed");
+    return rc;
 }
 
 

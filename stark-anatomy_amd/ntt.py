@@ -3,7 +3,8 @@
 Same callables, argument meaning, assertion messages and list-length conventions as the reference's
 code/ntt.py (ntt :3, intt :20, fast_multiply :32, fast_zerofier :66, fast_evaluate :82,
 fast_interpolate :102, fast_coset_evaluate :132, fast_coset_divide :137); the transforms, the coset
-scaling, the Hadamard product / pointwise division and the truncations run on the MI355X.
+scaling, the Hadamard product / pointwise division and the truncations run on the MI355X.  fast_divide is
+Polynomial.divide (code/univariate.py:80-97) -- division WITH remainder, by any divisor -- on the same transforms.
 
 `list[FieldElement]` in -> new `list[FieldElement]` out (arguments are never mutated).  The *_device
 variants take/return `DeviceCodeword` (data stays in HBM; no per-element marshalling) and are what
@@ -374,6 +375,21 @@ class DevicePolynomial:
         coset g <factor> never does -- q(factor X) there is q's own codeword, one place on (fast_stark.py:105-113)"""
         return ScaledLater(self, factor)
 
+    def divmod(self, divisor):
+        """Polynomial.divide (code/univariate.py:80-97) on resident vectors (sc_poly_divmod_dev) -> (quotient, remainder) as
+        DevicePolynomials of degree(self) - degree(divisor) + 1 and degree(divisor) coefficients; a numerator of lower degree:
+        (the empty polynomial, self), like the reference.  A zero divisor raises fast_coset_divide's assertion."""
+        dn, dd = DevicePolynomial.degrees([self, divisor])
+        assert(dd != -1), "cannot divide by zero polynomial"
+        if dn < dd:
+            return DevicePolynomial(DeviceVector(1), self.field, 0), self
+        _require_main_field(self.field)
+        quo, rem = DeviceVector(dn - dd + 1), DeviceVector(max(dd, 1))
+        _sc._check(_sc.lib().sc_poly_divmod_dev(self.vec.ptr, dn + 1, divisor.vec.ptr, dd + 1, quo.ptr, rem.ptr, None))
+        quotient = DevicePolynomial(quo, self.field, dn - dd + 1)
+        quotient._degree = dn - dd                         # the leading coefficient is self's over the divisor's: not zero
+        return quotient, DevicePolynomial(rem, self.field, dd)
+
     def coset_evaluate(self, offset, generator, order):
         """fast_coset_evaluate (code/ntt.py:132-135) -> DeviceCodeword"""
         out = DeviceVector(order)
@@ -459,6 +475,101 @@ def coset_divide_device(lhs, rhs, offset, primitive_root, root_order, exact=Fals
         assert(flag.value == 1), "cannot perform polynomial division because remainder is not zero"
         quotient._degree = dl - dr                         # an exact quotient's leading coefficient is lhs's over rhs's: not zero
     return quotient
+
+
+def _divide_lengths(numerator, denominator, dn, dd):
+    """list lengths of Polynomial.divide's results for dn >= dd >= 0: the quotient's, and the one the reference's running remainder
+    ends with (it grows to the subtractee's list length when the denominator list carries trailing zeros)"""
+    return dn - dd + 1, max(len(numerator.coefficients), dn - dd + len(denominator.coefficients))
+
+
+def fast_divide(numerator, denominator):
+    """Polynomial.divide (code/univariate.py:80-97) on the GPU (sc_poly_divmod): the same (quotient, remainder) -- values and list
+    lengths -- None for a zero denominator, (Polynomial([]), numerator) for a numerator of lower degree.  Any divisor: no coset,
+    no transform order, a remainder.  Numerators of degree < 8 are left to the long division."""
+    dd = denominator.degree()
+    if dd == -1:
+        return None
+    dn = numerator.degree()
+    if dn < dd:
+        return (Polynomial([]), numerator)
+    if dn < 8:
+        return numerator._schoolbook_divide(denominator)
+    field = denominator.coefficients[0].field
+    _require_main_field(field)
+    n_quo, n_rem = _divide_lengths(numerator, denominator, dn, dd)
+    quo, rem = ctypes.create_string_buffer(16 * n_quo), ctypes.create_string_buffer(16 * max(dd, 1))
+    _sc._check(_sc.lib().sc_poly_divmod(_pack(numerator.coefficients[:dn + 1]), dn + 1, _pack(denominator.coefficients[:dd + 1]), dd + 1, quo, rem))
+    return Polynomial(_unpack(quo.raw, n_quo, field)), Polynomial(_unpack(rem.raw, dd, field) + [field.zero()] * (n_rem - dd))
+
+
+def fast_divide_columns(numerators, denominator):
+    """[fast_divide(n, denominator) for n in numerators]: one upload, ONE division of all columns by the one divisor
+    (sc_poly_divmod_columns_dev: its series is inverted once), one download.  Numerators of lower degree than the longest get their
+    quotient's zero top coefficients stripped again; those below the divisor's degree (and a zero divisor, a short longest
+    numerator) are answered on the host as fast_divide answers them."""
+    numerators = list(numerators)
+    dd = denominator.degree()
+    dns = [n.degree() for n in numerators]
+    batch = [c for c, dn in enumerate(dns) if dn >= dd]
+    if dd == -1 or not batch or max(dns) < 8:
+        return [fast_divide(n, denominator) for n in numerators]
+    field = denominator.coefficients[0].field
+    _require_main_field(field)
+    na, nb = max(dns) + 1, dd + 1
+    m, ld_r = na - nb + 1, max(dd, 1)
+    cols = len(batch)
+    src = DeviceVector.from_bytes(b"".join(_pack(numerators[c].coefficients[:dns[c] + 1]) + bytes(16 * (na - dns[c] - 1)) for c in batch))
+    divisor = DeviceVector.from_bytes(_pack(denominator.coefficients[:nb]))
+    quo, rem = DeviceVector(cols * m), DeviceVector(cols * ld_r)
+    _sc._check(_sc.lib().sc_poly_divmod_columns_dev(src.ptr, na, na, cols, divisor.ptr, nb, quo.ptr, m, rem.ptr, ld_r, None))
+    quos = _unpack(quo.to_bytes(), cols * m, field)
+    rems = _unpack(rem.to_bytes(), cols * ld_r, field) if dd else []
+    out = [(Polynomial([]), n) for n in numerators]
+    for k, c in enumerate(batch):
+        n_quo, n_rem = _divide_lengths(numerators[c], denominator, dns[c], dd)
+        out[c] = (Polynomial(quos[k * m:k * m + n_quo]), Polynomial(rems[k * ld_r:k * ld_r + dd] + [field.zero()] * (n_rem - dd)))
+    return out
+
+
+# divide_columns_device hands fewer columns than this to DevicePolynomial.divmod one by one (tools/divide_timing.py; DESIGN.md section 6)
+DIVIDE_COLUMNS_MIN = 2
+
+
+def divide_columns_device(numerators, divisor, quotients=True, remainders=True):
+    """[n.divmod(divisor) for n in numerators] for DevicePolynomials and ONE divisor as one library call
+    (sc_poly_divmod_columns_dev) -> (quotients, remainders): lists of DevicePolynomials that are rows of one matrix each, or None
+    for the list not asked for (quotients=False / remainders=False; without remainders the product q * b is never formed).  Every
+    column is divided as a numerator of the LONGEST numerator's degree (shorter ones are zero-padded into the matrix, unless the
+    numerators already are equally spaced rows of one), so every quotient has the same number of coefficients -- zero on top for a
+    shorter numerator, one zero coefficient if no numerator reaches the divisor's degree -- and every remainder deg(divisor)."""
+    numerators = list(numerators)
+    assert(quotients or remainders), "neither quotients nor remainders asked for"
+    assert(not divisor.is_zero()), "cannot divide by zero polynomial"
+    if not numerators:
+        return ([] if quotients else None), ([] if remainders else None)
+    field = divisor.field
+    _require_main_field(field)
+    dd = divisor.degree()
+    dns = DevicePolynomial.degrees(numerators)
+    nb = dd + 1
+    na = max(max(dns) + 1, nb)
+    m, cols = na - nb + 1, len(numerators)
+    if cols < DIVIDE_COLUMNS_MIN and min(dns) >= dd:
+        pairs = [n.divmod(divisor) for n in numerators]
+        return ([q for q, _ in pairs] if quotients else None), ([r for _, r in pairs] if remainders else None)
+    holder, ld_a = _as_matrix(numerators, na)
+    ld_r = max(dd, 1)
+    quo = DeviceVector(cols * m) if quotients else None
+    rem = DeviceVector(cols * ld_r) if remainders else None
+    _sc._check(_sc.lib().sc_poly_divmod_columns_dev(holder.ptr, na, ld_a, cols, divisor.vec.ptr, nb, quo.ptr if quotients else None, m,
+                                                    rem.ptr if remainders else None, ld_r, None))
+    rows = lambda matrix, ld, n: [DevicePolynomial(DeviceVector.wrap(matrix.ptr + 16 * ld * c, max(n, 1), matrix), field, n) for c in range(cols)]
+    quos = rows(quo, m, m) if quotients else None
+    if quotients:
+        for q, dn in zip(quos, dns):
+            q._degree = dn - dd if dn >= dd else -1        # the leading coefficient is the numerator's over the divisor's: not zero
+    return quos, (rows(rem, ld_r, dd) if remainders else None)
 
 
 def _pitch_of(vectors, n):

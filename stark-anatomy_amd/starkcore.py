@@ -92,6 +92,9 @@ SIGNATURES = {
     "sc_vec_degree_columns_dev": (_int, [_vp, _u64, _u64, _u64, ctypes.POINTER(ctypes.c_int64), _vp]),
     "sc_pointwise_mul_dev": (_int, [_vp, _vp, _vp, _u64, _vp]),
     "sc_pointwise_div_dev": (_int, [_vp, _vp, _vp, _u64, _vp]),
+    "sc_poly_divmod": (_int, [_vp, _u64, _vp, _u64, _vp, _vp]),
+    "sc_poly_divmod_dev": (_int, [_vp, _u64, _vp, _u64, _vp, _vp, _vp]),
+    "sc_poly_divmod_columns_dev": (_int, [_vp, _u64, _u64, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _vp]),
     "sc_coset_divide_later_dev": (_int, [_vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _u64, ctypes.POINTER(_vp), _vp]),
     "sc_pointwise_div_later_dev": (_int, [_vp, _vp, _vp, _u64, ctypes.POINTER(_vp), _vp]),
     "sc_later_wait": (_int, [_vp, ctypes.POINTER(ctypes.c_int64)]),

@@ -3,7 +3,8 @@
 Mirrors the interface and list-length conventions of reference code/univariate.py:3-160 (coefficient
 lists are little-endian, may carry trailing zeros; `degree()` ignores them, equality ignores them).
 Quadratic paths here (schoolbook multiply / long division / Lagrange) are the reference's own
-small-degree fallbacks and test oracles; the fast paths live in ntt.py and run on the GPU.
+small-degree fallbacks and test oracles; the fast paths live in ntt.py and run on the GPU (`*` and
+`divide` / `/` / `%` hand long operands to them).
 Arithmetic is done on plain ints and wrapped back into FieldElement at the boundary.
 """
 from algebra import *
@@ -117,7 +118,25 @@ class Polynomial:
                     out[i + j] = (out[i + j] + x * y) % p
         return Polynomial(_wrap(out, field))
 
+    # divisor and quotient of at least this many coefficients each go through the GPU's division with remainder (ntt.fast_divide:
+    # Newton inversion of the reversed divisor, csrc/polydiv.cuh) instead of the long division below: same quotient, same remainder,
+    # same list lengths.  Never below 32: short polynomials are divided on machines without a GPU, as FAST_MUL_MIN_LEN assumes.
+    # Measured (tools/divide_timing.py, profiles/poly_divide/): at 32 + 32 coefficients the long division
+    # still wins (0.17 ms against 0.30), at 64 + 64 the device is 1.9x faster and from there on at every shape measured.
+    FAST_DIV_MIN_LEN = 64
+
     def divide(numerator, denominator):
+        """(quotient, remainder); None for a zero denominator (univariate.py:80-97).  Long operands in the main field are divided on
+        the GPU, everything else by the reference's long division."""
+        if len(denominator.coefficients) >= Polynomial.FAST_DIV_MIN_LEN and len(numerator.coefficients) >= 2 * Polynomial.FAST_DIV_MIN_LEN - 1:
+            # decide on DEGREES, not list lengths (lists may carry trailing zeros)
+            dd, dn = denominator.degree(), numerator.degree()
+            if min(dd + 1, dn - dd + 1) >= Polynomial.FAST_DIV_MIN_LEN and denominator.coefficients[0].field.p == Field.P_MAIN:
+                from ntt import fast_divide
+                return fast_divide(numerator, denominator)
+        return numerator._schoolbook_divide(denominator)
+
+    def _schoolbook_divide(numerator, denominator):
         """Schoolbook long division -> (quotient, remainder); None for a zero denominator (univariate.py:80-97)."""
         dd = denominator.degree()
         if dd == -1:
