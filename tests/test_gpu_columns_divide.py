@@ -90,10 +90,15 @@ def free_slots(sc):
 
 # ---------------------------------------------------------------- pointwise division
 
-def _div_columns(sc, a, ld_a, b, ld_b, out, ld_out, n, cols):
+def _div_columns_later(sc, a, ld_a, b, ld_b, out, ld_out, n, cols, stream=None):
+    """the call only enqueued on `stream` (a ctypes.c_void_p, None: the library's): the handle, to be waited for with _words"""
     h = ctypes.c_void_p()
-    sc._check(sc.lib().sc_pointwise_div_columns_later_dev(a.ptr, ld_a, b.ptr, ld_b, out.ptr, ld_out, n, cols, ctypes.byref(h), None))
-    return _words(h)
+    sc._check(sc.lib().sc_pointwise_div_columns_later_dev(a.ptr, ld_a, b.ptr, ld_b, out.ptr, ld_out, n, cols, ctypes.byref(h), stream))
+    return h
+
+
+def _div_columns(sc, a, ld_a, b, ld_b, out, ld_out, n, cols):
+    return _words(_div_columns_later(sc, a, ld_a, b, ld_b, out, ld_out, n, cols))
 
 
 @pytest.mark.parametrize("n,cols", [(1, 1), (17, 3), (4097, 5), (255, 300), ((1 << 16) + 1, 2)])
@@ -154,11 +159,16 @@ def _interpolant(num, d, root, order):
     return C.scale(C.intt(root, C.pointwise_div(ca, cb, order), order), order, pow(G, -1, P))
 
 
-def _coset_columns(sc, a, na, ld_a, b, nb, ld_b, cols, root, order, out, n_out, ld_out):
+def _coset_columns_later(sc, a, na, ld_a, b, nb, ld_b, cols, root, order, out, n_out, ld_out, stream=None):
+    """the call only enqueued on `stream` (a ctypes.c_void_p, None: the library's): the handle, to be waited for with _words"""
     h = ctypes.c_void_p()
     sc._check(sc.lib().sc_coset_divide_columns_later_dev(a.ptr, na, ld_a, b.ptr, nb, ld_b, cols, sc.fe_bytes(G), sc.fe_bytes(root), order, out.ptr,
-                                                         (ctypes.c_uint64 * cols)(*n_out), ld_out, ctypes.byref(h), None))
-    return _words(h)
+                                                         (ctypes.c_uint64 * cols)(*n_out), ld_out, ctypes.byref(h), stream))
+    return h
+
+
+def _coset_columns(sc, a, na, ld_a, b, nb, ld_b, cols, root, order, out, n_out, ld_out):
+    return _words(_coset_columns_later(sc, a, na, ld_a, b, nb, ld_b, cols, root, order, out, n_out, ld_out))
 
 
 def _coset_single(sc, num, d, root, order, n_out):
@@ -185,16 +195,23 @@ def _degree_of(packed):
     return po.degree(_ints(top + bytes(-len(top) % 16)))
 
 
-def _check_coset_columns(sc, columns, nb, shared, root, order, n_out):
-    """columns: [(numerator ints, divisor ints, expected interpolant bytes or None to take it from the oracle)].  The columns form on
-    the numerators as rows of one matrix (sentinels behind each) and the divisors zero-padded to nb, under both settings of
-    small_divisor_direct: quotients against the expectation and against the single-column entry, words against both."""
-    cols = len(columns)
+def _coset_operands(sc, columns, nb, shared, n_out):
+    """(a, na, ld_a, b, ld_out): the numerators as rows of one device matrix (zero-padded to the longest, sentinels behind each), the
+    divisors zero-padded to nb (the first one alone where shared), and the pitch of an output that takes the longest quotient"""
     na = max(len(num) for num, _, _ in columns)
     ld_a, ld_out = na + 2, max(max(n_out), 1) + 1
     a = sc.DeviceVector.from_bytes(_matrix([synth.pack_ints(num + [0] * (na - len(num))) for num, _, _ in columns], ld_a))
     d_rows = [synth.pack_ints(d + [0] * (nb - len(d))) for _, d, _ in columns]
     b = sc.DeviceVector.from_bytes(d_rows[0] if shared else b"".join(d_rows))
+    return a, na, ld_a, b, ld_out
+
+
+def _check_coset_columns(sc, columns, nb, shared, root, order, n_out):
+    """columns: [(numerator ints, divisor ints, expected interpolant bytes or None to take it from the oracle)].  The columns form on
+    the numerators as rows of one matrix (sentinels behind each) and the divisors zero-padded to nb, under both settings of
+    small_divisor_direct: quotients against the expectation and against the single-column entry, words against both."""
+    cols = len(columns)
+    a, na, ld_a, b, ld_out = _coset_operands(sc, columns, nb, shared, n_out)
     fulls = [full if full is not None else _interpolant(num, d, root, order) for num, d, full in columns]
     want_words = [(0, _degree_of(full[16 * k:])) for full, k in zip(fulls, n_out)]
     for direct in (1, 0):

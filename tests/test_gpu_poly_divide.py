@@ -198,6 +198,74 @@ def test_columns_in_chunks(sc, want_r):
     assert r == ([s[1] for s in single] if want_r else None)
 
 
+MULTI_PASS = (2101, 2100, 3)                          # m, nb, cols: Newton up to 2^13, the quotient product at 2^13, the remainder product at 2^12
+
+
+@functools.lru_cache(maxsize=None)
+def multi_pass_columns():
+    """(columns, b) of MULTI_PASS: a general numerator, an exact product (by the oracle's transforms) and a numerator with two zero
+    top coefficients"""
+    m, nb, cols = MULTI_PASS
+    na = m + nb - 1
+    b = synth.synth_ints(8200, nb)
+    b[-1] = P - 2
+    columns = [synth.synth_ints(8201 + c, na) for c in range(cols)]
+    columns[1] = oracle_product(synth.synth_ints(8210, m - 1) + [3], b)
+    columns[2][-2:] = [0, 0]
+    assert all(len(c) == na for c in columns)
+    return columns, b
+
+
+def check_defining_property(columns, b, q, r):
+    """a = q b + r with len(r) = nb - 1, column by column: that determines (q, r) uniquely (the long division is too slow here)"""
+    m, nb, _ = MULTI_PASS
+    for a, qc, rc in zip(columns, q, r):
+        qc, rc = synth.unpack_ints(qc), synth.unpack_ints(rc)
+        assert len(qc) == m and len(rc) == nb - 1 and max(qc) < P and max(rc) < P
+        assert trim(po.poly_add(oracle_product(qc, b), rc)) == trim(a)
+
+
+def test_columns_multi_pass(sc):
+    """the columns form where every transform that matters has more than one pass (above single_pass_max_log = 2^11; the shapes of
+    test_columns_match_single are all single-pass): NttOpts::cols > 1 with in_limit < n, the default column stride, columns of X and Y
+    at pitch n2 = 2^13 resp. n3 = 2^12.  Every column equals the single-column entry byte for byte and satisfies a = q b + r by the
+    oracle's product; the gaps keep the sentinel; leaving out one output leaves the other as it was."""
+    m, nb, cols = MULTI_PASS
+    assert sc.lib().sc_ntt_num_passes(1 << 12) > 1
+    columns, b = multi_pass_columns()
+    na, nr = m + nb - 1, nb - 1
+    single = [dev_divmod(sc, a, b) for a in columns]
+    check_defining_property(columns, b, [s[0] for s in single], [s[1] for s in single])
+    assert single[1][1] == bytes(16 * nr)                                   # the exact product
+    for ld_a, ld_q, ld_r in ((na, m, nr), (na + 5, m + 3, nr + 2)):
+        q, r = dev_divmod_columns(sc, columns, b, ld_a, ld_q, ld_r)
+        assert q == [s[0] for s in single], ld_a
+        assert r == [s[1] for s in single], ld_a
+    check_defining_property(columns, b, q, r)
+    q_only, none = dev_divmod_columns(sc, columns, b, na + 5, m + 3, nr + 2, want_r=False)
+    assert none is None and q_only == q
+    none, r_only = dev_divmod_columns(sc, columns, b, na + 5, m + 3, nr + 2, want_q=False)
+    assert none is None and r_only == r
+
+
+@pytest.mark.parametrize("want_r", [True, False], ids=["with_remainder", "quotient_only"])
+def test_columns_multi_pass_in_chunks(sc, want_r):
+    """the same three columns with the launch limit lowered to 2^14 values against temporaries of 2^13 per column: sets of 2 and 1
+    columns that reuse X and Y, every transform multi-pass"""
+    m, nb, cols = MULTI_PASS
+    columns, b = multi_pass_columns()
+    single = [dev_divmod(sc, a, b) for a in columns]
+    sc.set_tuning("div_cols_launch_log", 14)
+    try:
+        q, r = dev_divmod_columns(sc, columns, b, m + nb + 4, m + 3, nb + 1, want_r=want_r)
+    finally:
+        sc.set_tuning("div_cols_launch_log", 26)
+    assert q == [s[0] for s in single]
+    assert r == ([s[1] for s in single] if want_r else None)
+    if want_r:
+        check_defining_property(columns, b, q, r)
+
+
 # ---- 5. errors --------------------------------------------------------------------------------------------------------------------
 
 def test_errors_leave_outputs_alone(sc):
