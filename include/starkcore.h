@@ -71,7 +71,7 @@ int sc_stream_join(void* other_stream);
  * batch kernels correct by +-p on two limbs and an exact kernel redoes the tiles they flag, 0: exact arithmetic on every tile, 2: both
  * kernels on every tile (a test hook) -- see sc_ntt_columns_dev; "div_cols_chunk" = columns that share one batch inversion in
  * sc_pointwise_div_columns_later_dev / sc_coset_divide_columns_later_dev with a shared divisor, 0 = chosen by shape; "div_cols_launch_log" = log2 of the values
- * one set of launches of sc_coset_divide_columns_later_dev (and of sc_poly_divmod_columns_dev) takes, 26 by default and at most, at least 1: a test hook that makes the entry
+ * one set of launches of sc_coset_divide_columns_later_dev (and of sc_poly_divmod_columns_dev, sc_poly_mul_columns_dev, sc_poly_product_dev) takes, 26 by default and at most, at least 1: a test hook that makes the entry
  * work through a small matrix in several chunks of columns; "tree_cols_launch_log" = log2 of the elements one temporary of a set of columns of
  * sc_polytree_evaluate_columns_dev / sc_polytree_interpolate_columns_dev holds, 26 by default and at most, at least 1: a test hook that
  * makes those entries work through their columns in several sets).  Two keys manage the device-memory pool instead (freed vectors and trees are kept
@@ -292,6 +292,32 @@ int sc_poly_divmod_dev(const void* d_a, uint64_t na, const void* d_b, uint64_t n
 int sc_poly_divmod_columns_dev(const void* d_a, uint64_t na, uint64_t ld_a, uint64_t cols,
                                const void* d_b, uint64_t nb,            /* ONE divisor for all columns */
                                void* d_q, uint64_t ld_q, void* d_r, uint64_t ld_r, void* stream);
+/* ---- products, powers, products of many : code/univariate.py:48-57 (__mul__), :140-150 (__xor__) -- */
+/* Operands and results resident in HBM.  The library picks the transform itself: the smallest power of two that holds the result, with
+ * the root Field.primitive_nth_root gives -- no root, no order to pass.  The length passed in is the length used: zero coefficients on
+ * top are allowed, so are all-zero operands, and the WHOLE stated output length is written (zero on top where the operands' top
+ * coefficients are zero) -- the list length of the reference's product.  Nothing behind the stated output length is touched, nothing
+ * between a row's length and its stride is read into a result or written (csrc/polymul.cuh).
+ * SC_ERR_BAD_ARG, before anything is enqueued: a NULL pointer, a zero length, a stride below its length, an output that overlaps an
+ * operand, a result of more than 2^32 coefficients.  Nothing is read back: every call is enqueued on `stream` and returns.
+ * The temporaries are the call's own (returned to the pool behind the streams in use): no shared scratch, no one-stream rule -- the
+ * operands must be complete on `stream`, and calls on different streams do not disturb one another beyond sharing the table caches
+ * like every transform.  (The host entry sc_poly_mul above works in the shared scratch and is bound to the one-stream rule.)
+ * sc_poly_mul_dev: out = a * b, na + nb - 1 coefficients; d_a == d_b with na == nb (a square) is transformed once. */
+int sc_poly_mul_dev(const void* d_a, uint64_t na, const void* d_b, uint64_t nb, void* d_out /* na+nb-1 */, void* stream);
+/* out[c] = a[c] * b[c] for `cols` columns (column c of a matrix at element c * its stride); ld_b == 0: ONE multiplicand for all columns,
+ * transformed once per call.  Every other transform and kernel runs once per set of columns (sc_set_tuning("div_cols_launch_log")
+ * values per set, at most 65 535 columns); the multiplicands are read at their strides, not copied.  cols == 0: SC_OK, nothing happens. */
+int sc_poly_mul_columns_dev(const void* d_a, uint64_t na, uint64_t ld_a, uint64_t cols,
+                            const void* d_b, uint64_t nb, uint64_t ld_b /* 0: one shared multiplicand */,
+                            void* d_out, uint64_t ld_out, void* stream);
+/* out = a^exponent, exponent * (na - 1) + 1 coefficients: exponent 0 gives the single coefficient 1 (also for an all-zero a), exponent 1
+ * a copy, anything else one forward transform at the result's size, one pointwise power and one inverse transform. */
+int sc_poly_pow_dev(const void* d_a, uint64_t na, uint64_t exponent, void* d_out /* exponent*(na-1)+1 */, void* stream);
+/* out = the product of `count` rows of n coefficients each (row j at element j * ld of d_rows), count * (n - 1) + 1 coefficients: a
+ * balanced tree of log2(count) levels, every level one columns transform of all its rows, the pairwise products and one inverse
+ * columns transform per set of rows (sets as above); an odd last row is carried up.  count == 1 copies; count == 0: SC_OK, nothing happens. */
+int sc_poly_product_dev(const void* d_rows, uint64_t n, uint64_t ld, uint64_t count, void* d_out /* count*(n-1)+1 */, void* stream);
 /* Polynomial.degree (code/univariate.py:7-17) of a coefficient vector in HBM: index of the last non-zero entry, -1 if none (synchronous) */
 int sc_vec_degree_dev(const void* d_v, uint64_t n, int64_t* degree_out, void* stream);
 /* The same for `cols` vectors of n entries each, column c at element c * ld of d_v (ld >= n; entries between the columns are not

@@ -4,6 +4,7 @@
 #include "polytree.cuh"
 #include "geoseq.cuh"
 #include "polydiv.cuh"
+#include "polymul.cuh"
 
 namespace sci {
 
@@ -830,6 +831,186 @@ int polydiv_columns(const Fe* d_a, uint64_t ld_a, uint64_t cols, const Fe* d_b, 
 
 }  // namespace
 
+// ============================================================================ products, powers, products of many (polymul.cuh)
+
+namespace {
+
+// the largest result the transforms take: 2^32 coefficients, as for the division
+constexpr uint64_t PM_MAX_LEN = 1ull << 32;
+
+// transform size of a result of `len` coefficients: the smallest power of two that holds it, at least 2
+inline int pm_log(uint64_t len) { return std::max(1, ilog2(len)); }
+
+// extent in elements of `rows` rows of n elements at pitch ld; false: it does not fit 64 bits of bytes
+inline bool pm_extent(uint64_t rows, uint64_t ld, uint64_t n, uint64_t* out) {
+    const unsigned __int128 e = (unsigned __int128)(rows - 1) * ld + n;
+    if (e > (~0ull) / sizeof(Fe)) return false;
+    *out = (uint64_t)e;
+    return true;
+}
+
+// columns of one set: div_cols_launch_log values per temporary, at most 65 535 (grid.y), at least `least`
+inline uint64_t pm_per_set(uint64_t n, uint64_t least) {
+    uint64_t per = (1ull << g.div_cols_launch_log) / n;
+    if (per > 65535) per = 65535;
+    return per < least ? least : per;
+}
+
+// everything sc_poly_mul_dev / sc_poly_mul_columns_dev refuse before anything is enqueued
+int polymul_args(const void* d_a, uint64_t na, uint64_t ld_a, uint64_t cols, const void* d_b, uint64_t nb, uint64_t ld_b, const void* d_out, uint64_t ld_out, uint64_t* n_out) {
+    if (!d_a || !d_b || !d_out) return fail(SC_ERR_BAD_ARG, "null argument");
+    if (na == 0 || nb == 0) return fail(SC_ERR_BAD_ARG, "empty operand");
+    if (na > PM_MAX_LEN || nb > PM_MAX_LEN || na + nb - 1 > PM_MAX_LEN) return fail(SC_ERR_BAD_ARG, "result longer than the transforms take");
+    const uint64_t len = na + nb - 1;
+    if (ld_a < na || (ld_b && ld_b < nb) || ld_out < len) return fail(SC_ERR_BAD_ARG, "a column stride below the column length");
+    if (cols) {
+        uint64_t ea, eb, eo;
+        if (!pm_extent(cols, ld_a, na, &ea) || !pm_extent(ld_b ? cols : 1, ld_b, nb, &eb) || !pm_extent(cols, ld_out, len, &eo))
+            return fail(SC_ERR_BAD_ARG, "matrix larger than the address space");
+        if (pd_overlap(d_out, eo, d_a, ea) || pd_overlap(d_out, eo, d_b, eb)) return fail(SC_ERR_BAD_ARG, "the output may not overlap an operand");
+    }
+    *n_out = len;
+    return SC_OK;
+}
+
+// out[c] = a[c] * b[c] (ld_b == 0: a[c] * b) for `cols` columns: the shared multiplicand's transform once, every other transform
+// and every kernel once per set of columns.  square: b IS a (one column); it is transformed once.  Temporaries are the call's own.
+int polymul_columns(const Fe* d_a, uint64_t na, uint64_t ld_a, uint64_t cols, const Fe* d_b, uint64_t nb, uint64_t ld_b, Fe* d_out, uint64_t ld_out, bool square,
+                    hipStream_t st) {
+    const uint64_t len = na + nb - 1;
+    const int logn = pm_log(len);
+    const uint64_t n = 1ull << logn;
+    uint64_t per = pm_per_set(n, 1);
+    if (per > cols) per = cols;
+    const bool shared = ld_b == 0 && !square;
+    PoolTmpAsync Bf, X, Y;
+    if (shared) SCCHK(Bf.get(n * sizeof(Fe)));
+    SCCHK(X.get(per * n * sizeof(Fe)));
+    SCCHK(Y.get(per * n * sizeof(Fe)));
+    const Fe rt = canonical_root(logn), rti = root_inverse(rt, n), c_m2 = ninv_scaled(logn, 2);
+    if (shared) {
+        NttOpts o;
+        o.in_limit = nb;
+        SCCHK(ntt_device(d_b, Bf.fe(), logn, rt, false, o, st));
+    }
+    for (uint64_t done = 0; done < cols; done += per) {
+        const unsigned k = (unsigned)(cols - done < per ? cols - done : per);
+        NttOpts oc;
+        oc.cols = k;
+        oc.in_limit = na;
+        oc.col_stride_in = ld_a;
+        SCCHK(ntt_device(d_a + done * ld_a, X.fe(), logn, rt, false, oc, st));
+        const Fe* bf = shared ? Bf.fe() : X.fe();
+        if (!shared && !square) {
+            oc.in_limit = nb;
+            oc.col_stride_in = ld_b;
+            SCCHK(ntt_device(d_b + done * ld_b, Y.fe(), logn, rt, false, oc, st));
+            bf = Y.fe();
+        }
+        hipLaunchKernelGGL(pm_mul_kernel, dim3(pt_blocks(n), k), dim3(256), 0, st, (const Fe*)X.fe(), n, bf, shared ? (uint64_t)0 : n, X.fe(), n, n, c_m2);
+        NttOpts oi;
+        oi.cols = k;
+        SCCHK(ntt_device(X.fe(), Y.fe(), logn, rti, false, oi, st));
+        hipLaunchKernelGGL(pm_store_kernel, dim3(pt_blocks(len), k), dim3(256), 0, st, (const Fe*)Y.fe(), n, d_out + done * ld_out, ld_out, len);
+        HIPCHK(hipGetLastError());
+    }
+    return SC_OK;
+}
+
+// a^e: exponent 0 is the constant 1, exponent 1 a copy, anything else one forward transform at the result's size, the pointwise
+// power and one inverse transform
+int polypow(const Fe* d_a, uint64_t na, uint64_t e, Fe* d_out, uint64_t len, hipStream_t st) {
+    if (e == 0) {
+        hipLaunchKernelGGL(pt_fill_kernel, dim3(1), dim3(256), 0, st, d_out, (uint64_t)1, Fe{1, 0});
+        HIPCHK(hipGetLastError());
+        return SC_OK;
+    }
+    if (e == 1) {
+        HIPCHK(hipMemcpyAsync(d_out, d_a, na * sizeof(Fe), hipMemcpyDeviceToDevice, st));
+        return SC_OK;
+    }
+    const int logn = pm_log(len);
+    const uint64_t n = 1ull << logn;
+    PoolTmpAsync X, Y;
+    SCCHK(X.get(n * sizeof(Fe)));
+    SCCHK(Y.get(n * sizeof(Fe)));
+    const Fe rt = canonical_root(logn);
+    NttOpts o;
+    o.in_limit = na;
+    SCCHK(ntt_device(d_a, X.fe(), logn, rt, false, o, st));
+    hipLaunchKernelGGL(pm_pow_kernel, dim3(pt_blocks(n)), dim3(256), 0, st, X.fe(), n, n, e, ninv_scaled(logn, 0));
+    SCCHK(ntt_device(X.fe(), Y.fe(), logn, root_inverse(rt, n), false, NttOpts(), st));
+    HIPCHK(hipMemcpyAsync(d_out, Y.fe(), len * sizeof(Fe), hipMemcpyDeviceToDevice, st));
+    return SC_OK;
+}
+
+// one level of the product tree: `rows` rows of `len` coefficients -> (rows + 1) / 2 rows of min(2 len - 1, total), at transform size n
+struct PolyProductLevel {
+    uint64_t rows, len, out_len, n;
+    int logn;
+};
+
+// the product of `count` rows of n0 coefficients at pitch ld: a balanced tree whose levels live in two buffers in turn (the first
+// level reads the caller's rows).  Per level and set of rows: one columns transform, the pairwise products, one inverse columns
+// transform; an odd last row is carried up as it is, zero-extended to the level's length.  No product of any level is longer than
+// the result, so no level needs a transform above the result's size.
+int polyproduct(const Fe* d_rows, uint64_t n0, uint64_t ld, uint64_t count, Fe* d_out, uint64_t total, hipStream_t st) {
+    if (count == 1) {
+        HIPCHK(hipMemcpyAsync(d_out, d_rows, n0 * sizeof(Fe), hipMemcpyDeviceToDevice, st));
+        return SC_OK;
+    }
+    std::vector<PolyProductLevel> levels;
+    uint64_t level_elems = 0, set_elems = 0;
+    for (uint64_t rows = count, len = n0; rows > 1; rows = (rows + 1) / 2) {
+        PolyProductLevel lv;
+        lv.rows = rows; lv.len = len;
+        lv.out_len = 2 * len - 1 < total ? 2 * len - 1 : total;
+        lv.logn = pm_log(lv.out_len);
+        lv.n = 1ull << lv.logn;
+        levels.push_back(lv);
+        level_elems = std::max(level_elems, (rows + 1) / 2 * lv.n);
+        set_elems = std::max(set_elems, std::min((pm_per_set(lv.n, 2) & ~(uint64_t)1), rows & ~(uint64_t)1) * lv.n);
+        len = lv.out_len;
+    }
+    PoolTmpAsync L0, L1, F, G;
+    SCCHK(L0.get(level_elems * sizeof(Fe)));
+    if (levels.size() > 1) SCCHK(L1.get(level_elems * sizeof(Fe)));
+    SCCHK(F.get(set_elems * sizeof(Fe)));
+    SCCHK(G.get(set_elems / 2 * sizeof(Fe)));
+    const Fe* src = d_rows;
+    uint64_t pitch = ld;
+    for (size_t l = 0; l < levels.size(); ++l) {
+        const PolyProductLevel& lv = levels[l];
+        Fe* dst = (l & 1) ? L1.fe() : L0.fe();
+        const uint64_t paired = lv.rows & ~(uint64_t)1, per = std::min((pm_per_set(lv.n, 2) & ~(uint64_t)1), paired);
+        const Fe rt = canonical_root(lv.logn), rti = root_inverse(rt, lv.n), c_m2 = ninv_scaled(lv.logn, 2);
+        for (uint64_t done = 0; done < paired; done += per) {
+            const unsigned k = (unsigned)(paired - done < per ? paired - done : per);
+            NttOpts oc;
+            oc.cols = k;
+            oc.in_limit = lv.len;
+            oc.col_stride_in = pitch;
+            SCCHK(ntt_device(src + done * pitch, F.fe(), lv.logn, rt, false, oc, st));
+            hipLaunchKernelGGL(pm_mul_kernel, dim3(pt_blocks(lv.n), k / 2), dim3(256), 0, st, (const Fe*)F.fe(), 2 * lv.n, (const Fe*)F.fe() + lv.n, 2 * lv.n, G.fe(), lv.n, lv.n, c_m2);
+            NttOpts oi;
+            oi.cols = k / 2;
+            SCCHK(ntt_device(G.fe(), dst + done / 2 * lv.n, lv.logn, rti, false, oi, st));
+            HIPCHK(hipGetLastError());
+        }
+        if (lv.rows & 1) {
+            Fe* up = dst + paired / 2 * lv.n;
+            HIPCHK(hipMemcpyAsync(up, src + paired * pitch, lv.len * sizeof(Fe), hipMemcpyDeviceToDevice, st));
+            if (lv.out_len > lv.len) HIPCHK(hipMemsetAsync(up + lv.len, 0, (lv.out_len - lv.len) * sizeof(Fe), st));
+        }
+        src = dst;
+        pitch = lv.n;
+    }
+    HIPCHK(hipMemcpyAsync(d_out, src, total * sizeof(Fe), hipMemcpyDeviceToDevice, st));
+    return SC_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 // ---- subproduct tree: fast_zerofier / fast_evaluate / fast_interpolate
@@ -1122,5 +1303,46 @@ int sc_poly_divmod(const void* a, uint64_t na, const void* b, uint64_t nb, void*
     return rc;
 }
 
+
+// ---- products, powers, products of many (polymul.cuh): Polynomial.__mul__ / __xor__, code/univariate.py:48-57, :140-150
+int sc_poly_mul_columns_dev(const void* d_a, uint64_t na, uint64_t ld_a, uint64_t cols, const void* d_b, uint64_t nb, uint64_t ld_b, void* d_out, uint64_t ld_out, void* stream) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    uint64_t len;
+    SCCHK(polymul_args(d_a, na, ld_a, cols, d_b, nb, ld_b, d_out, ld_out, &len));
+    if (cols == 0) return SC_OK;
+    return polymul_columns((const Fe*)d_a, na, ld_a, cols, (const Fe*)d_b, nb, ld_b, (Fe*)d_out, ld_out, false, pick_stream(stream));
+}
+int sc_poly_mul_dev(const void* d_a, uint64_t na, const void* d_b, uint64_t nb, void* d_out, void* stream) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    uint64_t len;
+    SCCHK(polymul_args(d_a, na, na, 1, d_b, nb, nb, d_out, na + nb - 1, &len));
+    return polymul_columns((const Fe*)d_a, na, na, 1, (const Fe*)d_b, nb, nb, (Fe*)d_out, len, d_a == d_b && na == nb, pick_stream(stream));
+}
+int sc_poly_pow_dev(const void* d_a, uint64_t na, uint64_t exponent, void* d_out, void* stream) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    if (!d_a || !d_out) return fail(SC_ERR_BAD_ARG, "null argument");
+    if (na == 0) return fail(SC_ERR_BAD_ARG, "empty operand");
+    const unsigned __int128 len = (unsigned __int128)exponent * (na - 1) + 1;
+    if (na > PM_MAX_LEN || len > PM_MAX_LEN) return fail(SC_ERR_BAD_ARG, "result longer than the transforms take");
+    if (pd_overlap(d_out, (uint64_t)len, d_a, na)) return fail(SC_ERR_BAD_ARG, "the output may not overlap the operand");
+    return polypow((const Fe*)d_a, na, exponent, (Fe*)d_out, (uint64_t)len, pick_stream(stream));
+}
+int sc_poly_product_dev(const void* d_rows, uint64_t n, uint64_t ld, uint64_t count, void* d_out, void* stream) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    if (!d_rows || !d_out) return fail(SC_ERR_BAD_ARG, "null argument");
+    if (n == 0) return fail(SC_ERR_BAD_ARG, "empty operand");
+    if (ld < n) return fail(SC_ERR_BAD_ARG, "a row stride below the row length");
+    if (count == 0) return SC_OK;
+    const unsigned __int128 total = (unsigned __int128)count * (n - 1) + 1;
+    uint64_t extent;
+    if (n > PM_MAX_LEN || total > PM_MAX_LEN) return fail(SC_ERR_BAD_ARG, "result longer than the transforms take");
+    if (!pm_extent(count, ld, n, &extent)) return fail(SC_ERR_BAD_ARG, "matrix larger than the address space");
+    if (pd_overlap(d_out, (uint64_t)total, d_rows, extent)) return fail(SC_ERR_BAD_ARG, "the output may not overlap the operands");
+    return polyproduct((const Fe*)d_rows, n, ld, count, (Fe*)d_out, (uint64_t)total, pick_stream(stream));
+}
 
 }  // extern "C"

@@ -390,6 +390,35 @@ class DevicePolynomial:
         quotient._degree = dn - dd                         # the leading coefficient is self's over the divisor's: not zero
         return quotient, DevicePolynomial(rem, self.field, dd)
 
+    def multiply(self, other):
+        """Polynomial.__mul__ (code/univariate.py:48-57) on resident vectors (sc_poly_mul_dev): len(self) + len(other) - 1
+        coefficients, trailing zeros included; the empty polynomial if either operand is.  Nothing is waited for; `other is self`
+        (a square) is transformed once."""
+        if self.n == 0 or other.n == 0:
+            return DevicePolynomial(DeviceVector(1), self.field, 0)
+        _require_main_field(self.field)
+        out = DeviceVector(self.n + other.n - 1)
+        _sc._check(_sc.lib().sc_poly_mul_dev(self.vec.ptr, self.n, other.vec.ptr, other.n, out.ptr, None))
+        product = DevicePolynomial(out, self.field, self.n + other.n - 1)
+        if self._degree is not None and other._degree is not None:
+            product._degree = -1 if min(self._degree, other._degree) < 0 else self._degree + other._degree    # a field: no zero divisors
+        return product
+
+    def power(self, exponent):
+        """Polynomial.__xor__ (code/univariate.py:140-150) on a resident vector (sc_poly_pow_dev): exponent * (len(self) - 1) + 1
+        coefficients -- one forward transform, one pointwise power, one inverse transform instead of ~2 log2(exponent) products;
+        the empty polynomial for the zero polynomial, like the reference (that asks for the degree: one host wait unless it is known)."""
+        assert(exponent >= 0), "negative exponent"
+        if self.is_zero():
+            return DevicePolynomial(DeviceVector(1), self.field, 0)
+        _require_main_field(self.field)
+        length = exponent * (self.n - 1) + 1
+        out = DeviceVector(length)
+        _sc._check(_sc.lib().sc_poly_pow_dev(self.vec.ptr, self.n, exponent, out.ptr, None))
+        result = DevicePolynomial(out, self.field, length)
+        result._degree = exponent * self._degree
+        return result
+
     def coset_evaluate(self, offset, generator, order):
         """fast_coset_evaluate (code/ntt.py:132-135) -> DeviceCodeword"""
         out = DeviceVector(order)
@@ -597,6 +626,119 @@ def _as_matrix(polynomials, n):
         if min(len(p), n):
             _sc._check(_sc.lib().sc_memcpy_dev(matrix.ptr + 16 * n * c, p.vec.ptr, min(len(p), n), None))
     return matrix, n
+
+
+# multiply_columns_device hands fewer columns than this to DevicePolynomial.multiply one by one.  Measured (tools/multiply_timing.py,
+# profiles/poly_multiply/; DESIGN.md section 6): two resident columns in one call are x1.6 faster than two calls at 2^10, 2^12 and 2^16
+# coefficients, shared multiplicand or one per column, and the gain grows with the number of columns -- so only a single column loops.
+# fast_multiply_columns uses the same limit: on host lists both sides pack and unpack every coefficient in Python, which leaves
+# x1.15 to x2.7 (never slower; below the x1.5 margin for operands of 1024 coefficients at every number of columns).
+MULTIPLY_COLUMNS_MIN = 2
+
+
+def multiply_columns_device(lhs_list, rhs):
+    """[l.multiply(r_c) for l in lhs_list], r_c = rhs (one DevicePolynomial for every column, transformed once) or rhs[c], as ONE
+    library call (sc_poly_mul_columns_dev) -> DevicePolynomials that are rows of one matrix.  Every column is multiplied as a
+    polynomial of the LONGEST operand's length on either side (shorter ones are zero-padded into a matrix, unless the operands already
+    are equally spaced rows of one), so every product has max(len lhs) + max(len rhs) - 1 coefficients, zero on top for a shorter
+    operand; no coefficients at all if one side has none."""
+    lhs_list = list(lhs_list)
+    shared = isinstance(rhs, DevicePolynomial)
+    rhs_list = [rhs] if shared else list(rhs)
+    assert(shared or len(rhs_list) == len(lhs_list)), "one multiplicand, or one per column"
+    if not lhs_list:
+        return []
+    field = lhs_list[0].field
+    na, nb, cols = max(len(p) for p in lhs_list), max(len(p) for p in rhs_list), len(lhs_list)
+    if na == 0 or nb == 0:
+        return [DevicePolynomial(DeviceVector(1), field, 0) for _ in lhs_list]
+    _require_main_field(field)
+    if cols < MULTIPLY_COLUMNS_MIN and all(len(p) == na for p in lhs_list) and all(len(p) == nb for p in rhs_list):
+        return [l.multiply(rhs if shared else rhs_list[c]) for c, l in enumerate(lhs_list)]
+    n = na + nb - 1
+    holder_a, ld_a = _as_matrix(lhs_list, na)
+    holder_b, ld_b = (rhs.vec, 0) if shared else _as_matrix(rhs_list, nb)
+    out = DeviceVector(cols * n)
+    _sc._check(_sc.lib().sc_poly_mul_columns_dev(holder_a.ptr, na, ld_a, cols, holder_b.ptr, nb, ld_b, out.ptr, n, None))
+    products = [DevicePolynomial(DeviceVector.wrap(out.ptr + 16 * n * c, n, out), field, n) for c in range(cols)]
+    for c, (l, product) in enumerate(zip(lhs_list, products)):
+        r = rhs if shared else rhs_list[c]
+        if l._degree is not None and r._degree is not None:
+            product._degree = -1 if min(l._degree, r._degree) < 0 else l._degree + r._degree
+    return products
+
+
+def _host_product_lengths(lhs, rhs):
+    """list length of Polynomial.__mul__'s result: len + len - 1 (code/univariate.py:48-57), nothing if either list is empty"""
+    return len(lhs.coefficients) + len(rhs.coefficients) - 1 if lhs.coefficients and rhs.coefficients else 0
+
+
+def fast_multiply_columns(lhs_list, rhs):
+    """[l * rhs for l in lhs_list] on host Polynomials -- the same values and list lengths -- as one upload, ONE library call
+    (sc_poly_mul_columns_dev: the multiplicand is transformed once) and one download.  Zero operands, empty lists and products of
+    degree below 8 throughout are answered on the host as fast_multiply answers them."""
+    lhs_list = list(lhs_list)
+    dr = rhs.degree()
+    dls = [l.degree() for l in lhs_list]
+    batch = [c for c, dl in enumerate(dls) if dl >= 0]
+    if dr == -1 or len(batch) < MULTIPLY_COLUMNS_MIN or max(dls) + dr < 8:
+        return [l * rhs for l in lhs_list]
+    field = rhs.coefficients[0].field
+    _require_main_field(field)
+    na, nb, cols = max(dls) + 1, dr + 1, len(batch)
+    n = na + nb - 1
+    src = DeviceVector.from_bytes(b"".join(_pack(lhs_list[c].coefficients[:dls[c] + 1]) + bytes(16 * (na - dls[c] - 1)) for c in batch))
+    multiplicand = DeviceVector.from_bytes(_pack(rhs.coefficients[:nb]))
+    out = DeviceVector(cols * n)
+    _sc._check(_sc.lib().sc_poly_mul_columns_dev(src.ptr, na, na, cols, multiplicand.ptr, nb, 0, out.ptr, n, None))
+    flat = _unpack(out.to_bytes(), cols * n, field)
+    # (a zero polynomial with a non-empty list: the schoolbook product's list of zeros)
+    products = [Polynomial([field.zero()] * _host_product_lengths(l, rhs)) for l in lhs_list]
+    for k, c in enumerate(batch):
+        kept = dls[c] + dr + 1
+        products[c] = Polynomial(flat[k * n:k * n + kept] + [field.zero()] * (_host_product_lengths(lhs_list[c], rhs) - kept))
+    return products
+
+
+def fast_power(polynomial, exponent):
+    """Polynomial.__xor__ (code/univariate.py:140-150) on the GPU (sc_poly_pow_dev): the same values and the same list,
+    exponent * (len - 1) + 1 long; the empty polynomial for the zero polynomial.  One forward transform, one pointwise power and one
+    inverse transform instead of the binary method's ~2 log2(exponent) products.  Exponents below 2 and results of degree below 8
+    are left to the binary method."""
+    d = polynomial.degree()
+    if d == -1 or exponent < 2 or d * exponent < 8:
+        return polynomial._binary_power(exponent)
+    field = polynomial.coefficients[0].field
+    _require_main_field(field)
+    kept, full = exponent * d + 1, exponent * (len(polynomial.coefficients) - 1) + 1
+    base = DeviceVector.from_bytes(_pack(polynomial.coefficients[:d + 1]))
+    out = DeviceVector(kept)
+    _sc._check(_sc.lib().sc_poly_pow_dev(base.ptr, d + 1, exponent, out.ptr, None))
+    return Polynomial(_unpack(out.to_bytes(), kept, field) + [field.zero()] * (full - kept))
+
+
+def fast_product(polynomials):
+    """the left-to-right product p_0 * p_1 * ... of host Polynomials -- the same values and the same list, sum(len - 1) + 1 long
+    (empty if a member's list is) -- as one upload, ONE library call (sc_poly_product_dev: a balanced tree, every level one set
+    of launches) and one download.  Shorter members are zero-padded into the matrix.  A zero member, a single member and
+    products of degree below 8 are answered on the host."""
+    polynomials = list(polynomials)
+    assert(polynomials), "the product of no polynomials"
+    degrees = [p.degree() for p in polynomials]
+    if len(polynomials) == 1 or min(degrees) < 0 or sum(degrees) < 8:
+        product = polynomials[0]
+        for p in polynomials[1:]:
+            product = product * p
+        return product
+    field = polynomials[0].coefficients[0].field
+    _require_main_field(field)
+    count, n = len(polynomials), max(degrees) + 1
+    rows = DeviceVector.from_bytes(b"".join(_pack(p.coefficients[:d + 1]) + bytes(16 * (n - d - 1)) for p, d in zip(polynomials, degrees)))
+    total, kept = count * (n - 1) + 1, sum(degrees) + 1
+    out = DeviceVector(total)
+    _sc._check(_sc.lib().sc_poly_product_dev(rows.ptr, n, n, count, out.ptr, None))
+    full = sum(len(p.coefficients) - 1 for p in polynomials) + 1
+    return Polynomial(_unpack(out.to_bytes(0, kept), kept, field) + [field.zero()] * (full - kept))
 
 
 def _columns_verdict(handle):

@@ -92,6 +92,10 @@ SIGNATURES = {
     "sc_vec_degree_columns_dev": (_int, [_vp, _u64, _u64, _u64, ctypes.POINTER(ctypes.c_int64), _vp]),
     "sc_pointwise_mul_dev": (_int, [_vp, _vp, _vp, _u64, _vp]),
     "sc_pointwise_div_dev": (_int, [_vp, _vp, _vp, _u64, _vp]),
+    "sc_poly_mul_dev": (_int, [_vp, _u64, _vp, _u64, _vp, _vp]),
+    "sc_poly_mul_columns_dev": (_int, [_vp, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _u64, _vp]),
+    "sc_poly_pow_dev": (_int, [_vp, _u64, _u64, _vp, _vp]),
+    "sc_poly_product_dev": (_int, [_vp, _u64, _u64, _u64, _vp, _vp]),
     "sc_poly_divmod": (_int, [_vp, _u64, _vp, _u64, _vp, _vp]),
     "sc_poly_divmod_dev": (_int, [_vp, _u64, _vp, _u64, _vp, _vp, _vp]),
     "sc_poly_divmod_columns_dev": (_int, [_vp, _u64, _u64, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _vp]),

@@ -174,7 +174,26 @@ class Polynomial:
         _, remainder = self.divide(rhs)
         return remainder
 
+    # a base of at least this many coefficients (up to its degree) raised to an exponent of at least 2 goes through the GPU's power
+    # (ntt.fast_power: one forward transform, one pointwise power, one inverse transform, csrc/polymul.cuh) instead of the binary
+    # method's ~2 log2(e) products: same coefficients, same list length.  Never below 32: short polynomials are raised on machines
+    # without a GPU, as FAST_MUL_MIN_LEN assumes.  10**9: switched off.
+    # Measured (tools/multiply_timing.py, profiles/poly_multiply/): from 128 coefficients on fast_power is at
+    # least 1.5x faster than the binary method at every exponent measured (at 128: x1.7 for a square, x2.5 for a cube, x3.8 at
+    # e = 7, x4.1 at e = 255); at 32 and 64 coefficients a square gains x1.3 and x1.4 only.
+    FAST_POW_MIN_LEN = 128
+
     def __xor__(self, exponent):
+        """self^exponent (univariate.py:140-150).  Long bases in the main field are raised on the GPU, everything else by the
+        binary method."""
+        if exponent >= 2 and len(self.coefficients) >= Polynomial.FAST_POW_MIN_LEN and self.coefficients[0].field.p == Field.P_MAIN:
+            # decide on the DEGREE, not the list length (lists may carry trailing zeros)
+            if self.degree() + 1 >= Polynomial.FAST_POW_MIN_LEN:
+                from ntt import fast_power
+                return fast_power(self, exponent)
+        return self._binary_power(exponent)
+
+    def _binary_power(self, exponent):
         """self^exponent; the list is exponent * (len - 1) + 1 long whatever the order of the products, so the binary method
         runs from the low bit here (univariate.py:140-150 runs from the high bit)."""
         if self.is_zero():
