@@ -214,7 +214,8 @@ int sc_fourstep_region_bytes(const sc_fourstep_t* plan, uint64_t* bytes);
 int sc_fourstep_set_peers(sc_fourstep_t* plan, void* const* regions);      /* regions[h]: rank h's region as mapped HERE (own: its own) */
 int sc_fourstep_run_direct_dev(sc_fourstep_t* plan, int inverse, const void* d_src, void* d_dst, void* stream);
 int sc_fourstep_direct_status(const sc_fourstep_t* plan, uint64_t* timed_out_epoch);
-/* d_data[r][c] *= root^((row_base + r) * (col_base + c)) * scale, root of order `order` (scale may be NULL = 1) */
+/* d_data[r][c] *= root^((row_base + r) * (col_base + c)) * scale, root of order `order` (scale may be NULL = 1);
+ * cols a power of two, every exponent below `order`.  rows == 0 or cols == 0: SC_OK, nothing happens, nothing else is looked at. */
 int sc_twiddle_matrix_dev(void* d_data, uint64_t rows, uint64_t cols, uint64_t row_base, uint64_t col_base, const uint64_t root[2], uint64_t order,
                           const uint64_t scale[2], void* stream);
 
@@ -328,6 +329,7 @@ int sc_vec_degree_columns_dev(const void* d_v, uint64_t n, uint64_t ld, uint64_t
 int sc_pointwise_mul_dev(const void* d_a, const void* d_b, void* d_out, uint64_t n, void* stream);
 int sc_pointwise_div_dev(const void* d_a, const void* d_b, void* d_out, uint64_t n, void* stream); /* sync; SC_ERR_DIV_ZERO */
 int sc_scale_dev(const void* d_in, void* d_out, uint64_t n, const uint64_t factor[2], void* stream); /* out[i] = in[i] * factor^i */
+/* (factor is a canonical residue: factor >= p is SC_ERR_BAD_ARG with nothing written, as in sc_scale_columns_dev; n == 0: nothing happens) */
 /* acc[shift + j] += weight * src[j], j < n_src: one term `Polynomial([weight]) * (x ^ shift) * term` of the nonlinear combination
  * of code/fast_stark.py:130-145 on coefficient vectors in HBM (shift + n_src <= n_acc) */
 int sc_axpy_shift_dev(void* d_acc, uint64_t n_acc, const void* d_src, uint64_t n_src, uint64_t shift, const uint64_t weight[2], void* stream);
@@ -341,7 +343,8 @@ int sc_combine_columns_dev(const sc_combine_term_t* terms, uint64_t nterms, cons
                            uint64_t cols, void* d_out, uint64_t n_out, uint64_t ld_out, void* stream);
 /* the same scaling (univariate.py:153-154) on one rank's column slab [rows][cols] of a vector viewed as a rows x row_len
  * matrix (multi-GPU fast_coset_evaluate / fast_coset_divide, ntt.py:132-135, :159-176):
- * out[r][c] = in[r][c] * factor^(r * row_len + col_base + c); cols a power of two */
+ * out[r][c] = in[r][c] * factor^(r * row_len + col_base + c); cols a power of two, col_base + cols <= row_len.
+ * factor is a canonical residue: factor >= p is SC_ERR_BAD_ARG with nothing written.  rows == 0 or cols == 0: nothing happens. */
 int sc_scale_slab_dev(const void* d_in, void* d_out, uint64_t rows, uint64_t cols, uint64_t row_len, uint64_t col_base, const uint64_t factor[2], void* stream);
 
 /* ---- fast_zerofier / fast_evaluate / fast_interpolate : code/ntt.py:66-80, :82-100, :102-130 -- */

@@ -1488,6 +1488,7 @@ int sc_scale_dev(const void* d_in, void* d_out, uint64_t n, const uint64_t facto
     std::lock_guard<std::mutex> lk(g_mu);
     SCCHK(ensure_init());
     if (!n) return SC_OK;
+    if (!factor || fe_ge_p(fe_from(factor))) return fail(SC_ERR_BAD_ARG, "factor is not a canonical residue");
     hipStream_t st = pick_stream(stream);
     PowTables* pw;
     SCCHK(get_pow(fe_from(factor), n, st, &pw));
@@ -1513,6 +1514,7 @@ int sc_scale_slab_dev(const void* d_in, void* d_out, uint64_t rows, uint64_t col
     SCCHK(ensure_init());
     if (!rows || !cols) return SC_OK;
     if (!is_pow2(cols) || col_base + cols > row_len) return fail(SC_ERR_BAD_ARG, "slab columns must be a power of two inside the row");
+    if (!factor || fe_ge_p(fe_from(factor))) return fail(SC_ERR_BAD_ARG, "factor is not a canonical residue");
     hipStream_t st = pick_stream(stream);
     PowTables* pw;
     SCCHK(get_pow(fe_from(factor), rows * row_len, st, &pw));

@@ -152,6 +152,7 @@ int sc_twiddle_matrix_dev(void* d_data, uint64_t rows, uint64_t cols, uint64_t r
                           const uint64_t scale[2], void* stream) {
     std::lock_guard<std::mutex> lk(g_mu);
     SCCHK(ensure_init());
+    if (!rows || !cols) return SC_OK;              // nothing to do, whatever the other arguments say (rows - 1 below would wrap)
     hipStream_t st = pick_stream(stream);
     if (!is_pow2(cols) || !is_pow2(order) || order < 2) return fail(SC_ERR_NOT_POW2, "cols and order must be powers of two");
     if ((row_base + rows - 1) * (col_base + cols - 1) >= order) return fail(SC_ERR_BAD_ARG, "twiddle exponent out of range");
