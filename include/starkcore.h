@@ -454,7 +454,8 @@ int sc_scale_columns_dev(const void* d_in, uint64_t ld_in, void* d_out, uint64_t
 /* The permutation of the tutorial's hash over n inputs, one lane each.  The state width is fixed: m = 2 (rate 1, capacity 1), alpha = 3.
  * d_in: n elements (reduced mod p on load).  params: HOST pointer to 4 + 4 * rounds packed canonical residues -- the MDS matrix
  * (row-major, 2 x 2), then the 2 m rounds round constants (round r: [4 r, 4 r + 2) after the cube, [4 r + 2, 4 r + 4) after the
- * inverse cube).  Enqueued on `stream`; n == 0 launches nothing.
+ * inverse cube).  params is read for exactly 4 + 4 * rounds words: what lies behind them is neither read nor checked.
+ * Enqueued on `stream`; n == 0 launches nothing.
  * hash:  d_out[k] = state[0] after `rounds` rounds (n elements).
  * trace: all rounds + 1 states, register s of input k's state t at d_out[(2 k + s) * (rounds + 1) + t] (2 n (rounds + 1) elements).
  * SC_ERR_BAD_ARG: rounds == 0 or > 27, a constant not below p, params NULL, or a NULL buffer with n > 0. */
