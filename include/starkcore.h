@@ -62,7 +62,7 @@ int sc_stream(void** stream_out);
 int sc_stream_join(void* other_stream);
 /* tuning knobs for experiments (defaults are the measured optimum; -1 = choose by size where applicable): key in
  * {"max_tile_log","loge","max_col_log","min_tiles_log","single_pass_max_log","max_digit_log","direct_tw_max_log",
- *  "xcd_remap","fixed_shapes","merkle_big_nlev","wave_local","prio_balance","loge_cols","tw_on_load","prune","fast_fixups","fri_tail","fri_tail_stall","small_divisor_direct","verify_stage_kb","forest_four_lane_wgs","div_cols_chunk","div_cols_launch_log","tree_cols_launch_log"}.  Plans are re-derived on the next
+ *  "xcd_remap","fixed_shapes","merkle_big_nlev","wave_local","prio_balance","loge_cols","tw_on_load","prune","fast_fixups","fri_tail","fri_tail_stall","small_divisor_direct","verify_stage_kb","forest_four_lane_wgs","div_cols_chunk","div_cols_launch_log","tree_cols_launch_log","eval_chunk_log","eval_points_across_min","eval_across_min_products_log"}.  Plans are re-derived on the next
  * call; results never depend on the tuning ("fri_tail_stall" = k >= 0 is a test hook: the host withholds the challenge after round k of
  * the persistent tail kernel, whose wait then gives up after 2^13 polls; -1 = off; "small_divisor_direct" = 0: sc_coset_divide* transforms a
  * divisor of <= 8 coefficients like any other instead of evaluating it point by point; "verify_stage_kb" = the size of the staging buffer
@@ -74,7 +74,12 @@ int sc_stream_join(void* other_stream);
  * one set of launches of sc_coset_divide_columns_later_dev (and of sc_poly_divmod_columns_dev, sc_poly_mul_columns_dev, sc_poly_product_dev) takes, 26 by default and at most, at least 1: a test hook that makes the entry
  * work through a small matrix in several chunks of columns; "tree_cols_launch_log" = log2 of the elements one temporary of a set of columns of
  * sc_polytree_evaluate_columns_dev / sc_polytree_interpolate_columns_dev holds, 26 by default and at most, at least 1: a test hook that
- * makes those entries work through their columns in several sets).  Two keys manage the device-memory pool instead (freed vectors and trees are kept
+ * makes those entries work through their columns in several sets; "eval_chunk_log" = log2 of the coefficients one workgroup of
+ * sc_poly_eval_points_dev takes at least, 8 by default, 8 .. 24: a test hook that decides through how many chunks, and the launch that combines
+ * them, a small input goes; "eval_points_across_min" = the number of points from which sc_poly_eval_points_dev takes its points-across-lanes kernel
+ * instead of the coefficients-across-lanes one, 32 by default, at least 1; "eval_across_min_products_log" = log2 of the modular products
+ * (m * k * cols) a call must have for that to apply, 26 by default, 0 .. 64 -- smaller calls do not fill the device and always spread a chunk
+ * over a workgroup; 0 with "eval_points_across_min" = 1 takes the points-across-lanes kernel everywhere, which is how the tests reach it).  Two keys manage the device-memory pool instead (freed vectors and trees are kept
  * on exact-size free lists, by default up to a quarter of the device's memory divided by the processes sharing the device;
  * environment STARKCORE_POOL_CAP_MB): "pool_cap_mb" = what the lists may keep from now on, "pool_trim" = hand everything on them
  * back to the device now (a caller whose own allocator -- torch's -- ran out of memory). */
@@ -319,6 +324,27 @@ int sc_poly_pow_dev(const void* d_a, uint64_t na, uint64_t exponent, void* d_out
  * balanced tree of log2(count) levels, every level one columns transform of all its rows, the pairwise products and one inverse
  * columns transform per set of rows (sets as above); an odd last row is carried up.  count == 1 copies; count == 0: SC_OK, nothing happens. */
 int sc_poly_product_dev(const void* d_rows, uint64_t n, uint64_t ld, uint64_t count, void* d_out /* count*(n-1)+1 */, void* stream);
+/* ---- values at points, directly : code/univariate.py:99-105 (evaluate, evaluate_domain) ------- */
+/* out[c * ld_out + j] = sum_i coeffs[c * ld_in + i] * points[j]^i,  i < m, j < k, c < cols: `cols` polynomials of m coefficients each
+ * (column c at element c * ld_in of d_coeffs) at the SAME k points, all resident in HBM.  The work is m * k * cols modular products --
+ * no tree, no transform: the route for few points against many coefficients (one point included), where sc_polytree_evaluate_columns_dev
+ * would first reduce the polynomial modulo a zerofier at the polynomial's own size (csrc/polyeval.cuh).  Values are canonical residues
+ * in and out; points may repeat and need not be distinct from one another or from 0.  m == 0 gives zeros; k == 0 or cols == 0: SC_OK,
+ * nothing is enqueued.  Nothing between a column's k results and the next stride is written, nothing between a column's m coefficients
+ * and the next stride is read into a result.
+ * SC_ERR_BAD_ARG, before anything is enqueued: a NULL pointer with a non-zero count, ld_in < m or ld_out < k with cols > 1, m > 2^32,
+ * k * cols > 2^32, an output range that overlaps the coefficients or the points.
+ * The coefficients are cut into chunks of at least 2^"eval_chunk_log" (sc_set_tuning) coefficients; a first launch computes every
+ * chunk's own value -- coefficients across the lanes of a workgroup for fewer than "eval_points_across_min" points and for calls too small
+ * to fill the device, points across lanes otherwise -- and a second, small launch combines the chunks (skipped when there is one).  No workgroup waits for another and no
+ * atomics touch field elements: the results are exact and the same for every chunk length, form and schedule.
+ * The _dev form reads nothing back and only ENQUEUES on `stream` (NULL: the library stream).  Its temporaries are the call's own
+ * (returned to the pool behind the streams in use): no shared scratch, no one-stream rule -- the operands must be complete on
+ * `stream`, and calls on different streams do not disturb one another.  The host form takes host buffers and one column, works on the
+ * library stream and is synchronous. */
+int sc_poly_eval_points_dev(const void* d_coeffs, uint64_t m, uint64_t ld_in, uint64_t cols,
+                            const void* d_points, uint64_t k, void* d_out, uint64_t ld_out, void* stream);
+int sc_poly_eval_points(const void* coeffs, uint64_t m, const void* points, uint64_t k, void* out /* k values */);
 /* Polynomial.degree (code/univariate.py:7-17) of a coefficient vector in HBM: index of the last non-zero entry, -1 if none (synchronous) */
 int sc_vec_degree_dev(const void* d_v, uint64_t n, int64_t* degree_out, void* stream);
 /* The same for `cols` vectors of n entries each, column c at element c * ld of d_v (ld >= n; entries between the columns are not
@@ -378,6 +404,20 @@ int sc_polytree_interpolate_dev(sc_polytree_t* tree, const void* d_values, void*
  * column's length (ld_in < m, ld_in < k, ld_out < k): SC_ERR_BAD_ARG.  d_out may NOT overlap the input. */
 int sc_polytree_evaluate_columns_dev(sc_polytree_t* tree, const void* d_coeffs, uint64_t m, uint64_t ld_in, uint64_t cols, const void* d_points, void* d_out, uint64_t ld_out, void* stream);
 int sc_polytree_interpolate_columns_dev(sc_polytree_t* tree, const void* d_values, uint64_t ld_in, uint64_t cols, void* d_out, uint64_t ld_out, void* stream);
+/* Polynomial.interpolate_domain (code/univariate.py:107-121) for ANY points: the columns interpolation above with the weights
+ * inv0(Z'(d_i)) in place of 1 / Z'(d_i), where inv0 is the reference's Field.inverse (code/algebra.py:87-89), which maps 0 to 0.  The
+ * result is  sum_i v_i * inv0(Z'(d_i)) * Z(X) / (X - d_i)  with Z the zerofier of all points with their multiplicities: a repeated
+ * point (Z' = 0 there) drops its own terms and nothing fails; always k coefficients.  For distinct points the coefficients equal
+ * sc_polytree_interpolate_columns_dev's bit for bit.  The tree keeps this weight table beside the other one (one extra kernel, built by
+ * the first call; it IS the other table where that exists, since that was built without a zero derivative).  The existing entries
+ * keep their behaviour on a tree this entry has used: a repeated point is still SC_ERR_DIV_ZERO from sc_polytree_interpolate_dev and
+ * sc_polytree_interpolate_columns_dev, and nothing of theirs is kept.  Strides, overlap, sets of columns, cols == 0 and the
+ * SC_ERR_BAD_ARG cases: as sc_polytree_interpolate_columns_dev.  Only enqueues (the tree's inverse series is built on first use, which
+ * waits).  The weight table is built by the FIRST call, on that call's stream, and is not waited for: like every entry that takes a tree,
+ * calls on one tree belong on one stream, or the first call's stream is ordered before whoever uses the tree next.  The progression tables need no such entry: their points are distinct by construction.
+ * sc_interpolate_lagrange: host buffers, one column, k >= 1, k coefficients out, synchronous. */
+int sc_polytree_interpolate_lagrange_columns_dev(sc_polytree_t* tree, const void* d_values, uint64_t ld_in, uint64_t cols, void* d_out, uint64_t ld_out, void* stream);
+int sc_interpolate_lagrange(const void* points, const void* values, uint64_t k, void* out);
 int sc_polytree_free(sc_polytree_t* tree);
 
 /* ---- the same three functions on a GEOMETRIC PROGRESSION  x_i = first * ratio^i, i < n : code/ntt.py:66-130 as called by

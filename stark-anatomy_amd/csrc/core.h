@@ -7,6 +7,7 @@
 //   polytree_geo.hip  subproduct trees and geometric progressions (fast_zerofier / fast_evaluate / fast_interpolate)
 //   fourstep.hip      batched transforms, the sharded four-step plan, the RCCL communicator, the direct-store corner turn
 //   rescue.hip        the Rescue-Prime permutation (hash and trace) over many inputs
+//   polyeval.hip      polynomials in HBM evaluated at a list of points directly (csrc/polyeval.cuh)
 //   columns.hip       division, combination and one deferred verdict over a matrix of polynomial columns (csrc/columns.cuh); the
 //                     verifier's combination at the opened points as rows (csrc/combination.cuh)
 #pragma once
@@ -130,6 +131,9 @@ struct Ctx {
     int small_divisor_direct = 1;    // coset_divide_core evaluates a divisor of <= 8 coefficients point by point instead of transforming it (sc_set_tuning("small_divisor_direct", 0): A/B and tests)
     int div_cols_launch_log = 26;    // sc_coset_divide_columns_later_dev: log2 of the values one set of launches takes (COLS_ELEMS_PER_LAUNCH); smaller: a test hook for the chunk loop
     int tree_cols_launch_log = 26;   // sc_polytree_*_columns_dev: log2 of the elements one temporary of a set of columns holds (COLS_ELEMS_PER_LAUNCH); smaller: a test hook for the set loop
+    int eval_chunk_log = 8;          // sc_poly_eval_points_dev: log2 of the coefficients one workgroup takes at least (csrc/polyeval.hip); a test hook that decides how many chunks a small input goes through
+    int eval_points_across_min = 32; // sc_poly_eval_points_dev: the number of points (of a call, of a last part-wave) from which the points-across-lanes form is taken ...
+    int eval_across_min_products_log = 26;   // ... in calls of at least 2^this many modular products (0: in every call)
     int div_cols_chunk = 0;          // columns that share one batch inversion in pointwise_div_cols_kernel; 0: chosen by shape (columns.hip div_cols_chunk_for)
     std::vector<hipStream_t> seen_streams;   // those streams, most recent last (at most SEEN_STREAMS; more: device-wide waits)
     DevBuf scratch[8];       // 0: ntt work, 1..3: poly temporaries, 4: misc small, 5: merkle staging, 6: uploaded operands, 7: degree / exactness flag

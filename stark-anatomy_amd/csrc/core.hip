@@ -1059,6 +1059,9 @@ int sc_set_tuning(const char* key, int value) {
     else if (k == "div_cols_chunk") g.div_cols_chunk = value < 0 ? 0 : (value > 65535 ? 65535 : value);      // columns per workgroup row of pointwise_div_cols_kernel, 0 = by shape (csrc/columns.hip)
     else if (k == "div_cols_launch_log") g.div_cols_launch_log = value < 1 ? 1 : (value > 26 ? 26 : value);        // tests only: more chunks per call, never larger ones (csrc/columns.hip)
     else if (k == "tree_cols_launch_log") g.tree_cols_launch_log = value < 1 ? 1 : (value > 26 ? 26 : value);      // tests only: more sets per call, never larger ones (csrc/polytree_geo.hip)
+    else if (k == "eval_chunk_log") g.eval_chunk_log = value < 8 ? 8 : (value > 24 ? 24 : value);                  // tests only: more chunks per column (csrc/polyeval.hip); at least one Horner stride
+    else if (k == "eval_points_across_min") g.eval_points_across_min = value < 1 ? 1 : value;                     // which of the two forms of the evaluation kernel a number of points takes ...
+    else if (k == "eval_across_min_products_log") g.eval_across_min_products_log = value < 0 ? 0 : (value > 64 ? 64 : value);   // ... in calls of at least 2^value products
     else if (k == "verify_stage_kb") g.verify_stage_bytes = (size_t)(value < 16 ? 16 : value) << 10;           // (a chunk must hold one row of any depth)
     else if (k == "fri_tail_stall") g.fri_tail_stall = value;                               // tests only: see core.h
     else if (k == "pool_cap_mb") g_pool_cap = (size_t)(value < 0 ? 0 : value) << 20;       // what the free lists may keep from now on

@@ -203,6 +203,16 @@ __global__ void __launch_bounds__(256) pt_fill_kernel(Fe* __restrict__ out, uint
     if (i < n) out[i] = v;
 }
 
+// the weights of sc_polytree_interpolate_lagrange_columns_dev: w[i] = inv0(Z'(d_i)) as Montgomery forms, i < k, with the reference's
+// Field.inverse (code/algebra.py:87-89), which maps 0 to 0 -- a repeated point has Z'(d_i) = 0 and drops its own term.  Fermat's
+// x^(p-2) (mont_inv: 143 products) has that value at 0 by itself, so nothing is replaced before and nothing cleared after an
+// inversion, no flag travels to the host, and for distinct points the table is 1 / Z'(d_i), bit for bit the one the batch
+// inversion of polytree_weights leaves.  Once per tree.
+__global__ void __launch_bounds__(256) pt_inv0_kernel(const Fe* __restrict__ d, Fe* __restrict__ w, uint64_t k) {
+    uint64_t i = PT_INDEX();
+    if (i < k) w[i] = mont_inv(to_mont(d[i]));
+}
+
 // interpolation weights, transposing load: W[i][c] = v_c[i] / Z'(d_i) for i < k (winv_m: 1 / Z'(d_i) as Montgomery forms, shared by the
 // columns), 0 on the padding leaves and in the padding lanes; total = K * C'
 __global__ void __launch_bounds__(256) pt_weights_cols_kernel(const Fe* __restrict__ values, uint64_t ld_in, uint64_t cols, const Fe* __restrict__ winv_m, uint64_t k,

@@ -76,6 +76,7 @@ struct sc_polytree {
     Fe* invg_f;    // size-2K transform of rev(Z)^-1 mod y^K (built by the first evaluation)
     size_t zc_bytes, zf_bytes;
     Fe* winv_m = nullptr;   // k: 1 / Z'(d_i) as Montgomery forms, Z = the zerofier of the k real points (built by the first column interpolation)
+    Fe* winv0_m = nullptr;  // k: inv0(Z'(d_i)), 0 where the derivative is (built by the first Lagrange interpolation); IS winv_m where that existed already
 };
 
 namespace {
@@ -346,11 +347,38 @@ int polytree_weights(sc_polytree* t, hipStream_t st) {
     return SC_OK;
 }
 
-// polytree_interpolate for `cols` columns: column c's k values at d_values + c * ld_in, its k coefficients to d_out + c * ld_out
-int polytree_interpolate_columns(sc_polytree* t, const Fe* d_values, uint64_t ld_in, uint64_t cols, Fe* d_out, uint64_t ld_out, hipStream_t st) {
+// inv0(Z'(d_i)) for the k real points, once per tree (pt_inv0_kernel): the derivative of the zerofier at all leaves and one inversion
+// per point that keeps a zero.  Only enqueues (but the tree's inverse series is built on first use, which waits).  A table winv_m
+// that exists was built without a zero derivative and is the same table: it is shared.  The table is published as soon as its kernel
+// is enqueued (polytree_weights waits, for its verdict): valid in the order of `st`, which is the trees' one-stream rule.  Nothing here touches winv_m, so the
+// entries that answer a repeated point with SC_ERR_DIV_ZERO go on doing so.
+int polytree_weights_inv0(sc_polytree* t, hipStream_t st) {
+    if (t->winv0_m || t->L == 0) return SC_OK;
+    if (t->winv_m) { t->winv0_m = t->winv_m; return SC_OK; }
+    const uint64_t K = t->K, k = t->k;
+    PoolTmpAsync bx, by, tk, p;
+    SCCHK(bx.get(2 * K * sizeof(Fe)));
+    SCCHK(by.get(2 * K * sizeof(Fe)));
+    SCCHK(tk.get(K * sizeof(Fe)));
+    SCCHK(p.get(K * sizeof(Fe)));
+    hipLaunchKernelGGL(pt_deriv_kernel, dim3(pt_blocks(K)), dim3(256), 0, st, (const Fe*)(t->zc + (uint64_t)t->L * K), K, K - k, k, p.fe());
+    SCCHK(polytree_evaluate_all(t, p.fe(), k, tk.fe(), bx.fe(), by.fe(), p.fe(), st));
+    Fe* w = nullptr;
+    HIPCHK(pool_alloc((void**)&w, k * sizeof(Fe)));
+    hipLaunchKernelGGL(pt_inv0_kernel, dim3(pt_blocks(k)), dim3(256), 0, st, (const Fe*)tk.fe(), w, k);
+    if (hipGetLastError() != hipSuccess) { release_after_streams(w, k * sizeof(Fe)); return fail(SC_ERR_HIP, "weight table launch failed"); }
+    t->winv0_m = w;
+    return SC_OK;
+}
+
+// polytree_interpolate for `cols` columns: column c's k values at d_values + c * ld_in, its k coefficients to d_out + c * ld_out.
+// lagrange: the weights inv0(Z'(d_i)) instead of 1 / Z'(d_i) -- Polynomial.interpolate_domain's result for ANY points (a repeated
+// point drops its terms, code/univariate.py:107-121) where the other table fails the call; everything behind the weights is the same.
+int polytree_interpolate_columns(sc_polytree* t, const Fe* d_values, uint64_t ld_in, uint64_t cols, Fe* d_out, uint64_t ld_out, bool lagrange, hipStream_t st) {
     const uint64_t K = t->K, k = t->k, pad = K - k;
     const int L = t->L;
-    SCCHK(polytree_weights(t, st));
+    SCCHK(lagrange ? polytree_weights_inv0(t, st) : polytree_weights(t, st));
+    const Fe* winv = lagrange ? t->winv0_m : t->winv_m;
     const uint64_t per = 1ull << polytree_set_log(t, cols);
     const int logP = ilog2(per);
     PoolTmpAsync bx, by, tk, p;
@@ -366,7 +394,7 @@ int polytree_interpolate_columns(sc_polytree* t, const Fe* d_values, uint64_t ld
         Fe* cur = p.fe();
         Fe* nxt = tk.fe();
         if (L == 0) hipLaunchKernelGGL(pt_rev_poly_cols_kernel, dim3(pt_blocks(half)), dim3(256), 0, st, src, (uint64_t)1, ld_in, nc, cur, K, logC, half);   // one point: the value itself
-        else hipLaunchKernelGGL(pt_weights_cols_kernel, dim3(pt_blocks(half)), dim3(256), 0, st, src, ld_in, nc, (const Fe*)t->winv_m, k, cur, logC, half);
+        else hipLaunchKernelGGL(pt_weights_cols_kernel, dim3(pt_blocks(half)), dim3(256), 0, st, src, ld_in, nc, winv, k, cur, logC, half);
         // up: P = P_L * Z_R + P_R * Z_L
         for (int l = 0; l < L; ++l) {
             hipLaunchKernelGGL(pt_expand_cols_kernel, dim3(pt_blocks(2 * half)), dim3(256), 0, st, (const Fe*)cur, bx.fe(), half);
@@ -1069,7 +1097,15 @@ int sc_polytree_interpolate_columns_dev(sc_polytree_t* tree, const void* d_value
     if (!tree || !d_out || !d_values) return fail(SC_ERR_BAD_ARG, "null argument");
     if (cols > 1 && (ld_in < tree->k || ld_out < tree->k)) return fail(SC_ERR_BAD_ARG, "a column stride below the number of points");
     if (cols == 0) return SC_OK;
-    return polytree_interpolate_columns(tree, (const Fe*)d_values, ld_in, cols, (Fe*)d_out, ld_out, pick_stream(stream));
+    return polytree_interpolate_columns(tree, (const Fe*)d_values, ld_in, cols, (Fe*)d_out, ld_out, false, pick_stream(stream));
+}
+int sc_polytree_interpolate_lagrange_columns_dev(sc_polytree_t* tree, const void* d_values, uint64_t ld_in, uint64_t cols, void* d_out, uint64_t ld_out, void* stream) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    if (!tree || !d_out || !d_values) return fail(SC_ERR_BAD_ARG, "null argument");
+    if (cols > 1 && (ld_in < tree->k || ld_out < tree->k)) return fail(SC_ERR_BAD_ARG, "a column stride below the number of points");
+    if (cols == 0) return SC_OK;
+    return polytree_interpolate_columns(tree, (const Fe*)d_values, ld_in, cols, (Fe*)d_out, ld_out, true, pick_stream(stream));
 }
 int sc_polytree_free(sc_polytree_t* tree) {
     std::lock_guard<std::mutex> lk(g_mu);
@@ -1077,6 +1113,7 @@ int sc_polytree_free(sc_polytree_t* tree) {
     release_after_streams(tree->zc, tree->zc_bytes);
     release_after_streams(tree->zf, tree->zf_bytes);
     if (tree->invg_f) release_after_streams(tree->invg_f, 2 * tree->K * sizeof(Fe));
+    if (tree->winv0_m && tree->winv0_m != tree->winv_m) release_after_streams(tree->winv0_m, tree->k * sizeof(Fe));
     if (tree->winv_m) release_after_streams(tree->winv_m, tree->k * sizeof(Fe));
     delete tree;
     return SC_OK;
@@ -1192,6 +1229,30 @@ int sc_interpolate(const void* points, const void* values, uint64_t k, void* out
         if (rc == SC_OK) rc = upload(dv.p, values, k * sizeof(Fe), g.stream);
         if (rc == SC_OK) rc = polytree_interpolate(t, dv.fe(), dout.fe(), g.stream);
         if (rc == SC_OK) rc = download(out, dout.p, k * sizeof(Fe), g.stream);
+    }
+    sc_polytree_free(t);
+    return rc;
+}
+
+// Polynomial.interpolate_domain (code/univariate.py:107-121) on host buffers: always the tree (a progression has distinct points, for
+// which this is sc_interpolate's result anyway), one column
+int sc_interpolate_lagrange(const void* points, const void* values, uint64_t k, void* out) {
+    if (!points || !values || !out || !k) {
+        std::lock_guard<std::mutex> lk(g_mu);
+        return fail(SC_ERR_BAD_ARG, k ? "null argument" : "cannot interpolate between zero points");
+    }
+    sc_polytree_t* t = nullptr;
+    SCCHK(sc_polytree_build(points, k, &t));
+    int rc;
+    {
+        std::lock_guard<std::mutex> lk(g_mu);
+        PoolTmp dv, dout;
+        rc = dv.get(k * sizeof(Fe));
+        if (rc == SC_OK) rc = dout.get(k * sizeof(Fe));
+        if (rc == SC_OK) rc = upload(dv.p, values, k * sizeof(Fe), g.stream);
+        if (rc == SC_OK) rc = polytree_interpolate_columns(t, dv.fe(), k, 1, dout.fe(), k, true, g.stream);
+        if (rc == SC_OK) rc = download(out, dout.p, k * sizeof(Fe), g.stream);
+        else (void)hipStreamSynchronize(g.stream);
     }
     sc_polytree_free(t);
     return rc;

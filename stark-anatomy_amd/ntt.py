@@ -270,6 +270,16 @@ class DeviceDomain:
     def __len__(self):
         return self.tree.k
 
+    def points_vector(self):
+        """the points themselves as a DeviceVector: the tree's own copy, or -- a progression keeps none -- first * ratio^i made once"""
+        points = getattr(self.tree, "points", None) or getattr(self, "_points", None)
+        if points is None:
+            n = len(self)
+            firsts = DeviceVector.from_bytes(self.tree.first.to_bytes(16, "little") * n)
+            points = self._points = DeviceVector(n)
+            _sc._check(_sc.lib().sc_scale_dev(firsts.ptr, points.ptr, n, _sc.fe_bytes(self.tree.ratio), None))
+        return points
+
 
 class DevicePolynomial:
     """A coefficient list resident in HBM: what `Polynomial` is to the host path.  `len(p)` is the reference's LIST length
@@ -418,6 +428,21 @@ class DevicePolynomial:
         result = DevicePolynomial(out, self.field, length)
         result._degree = exponent * self._degree
         return result
+
+    def evaluate_points(self, points):
+        """[self.evaluate(x) for x in points] (Polynomial.evaluate_domain, code/univariate.py:104-105) as ONE library call that only
+        enqueues (sc_poly_eval_points_dev: len(self) * len(points) modular products, no tree, no transform) -> DeviceVector of
+        len(points) values.  points: a list of FieldElements or a DeviceDomain; they may repeat."""
+        _require_main_field(self.field)
+        xs = points.points_vector() if isinstance(points, DeviceDomain) else DeviceVector.from_bytes(_pack(points))
+        out = DeviceVector(max(xs.n, 1))
+        _sc._check(_sc.lib().sc_poly_eval_points_dev(self.vec.ptr if self.n else None, self.n, self.n, 1, xs.ptr, xs.n, out.ptr, xs.n, None))
+        return out if xs.n else DeviceVector(0)
+
+    def evaluate(self, point):
+        """Polynomial.evaluate (code/univariate.py:99-102) of a polynomial that stays in HBM -> FieldElement: one call of the
+        evaluation kernel and one 16-byte read (a resident quotient at one out-of-domain point; nothing else is downloaded)"""
+        return FieldElement(_sc.unpack(self.evaluate_points([point]).to_bytes(0, 1), 1)[0], point.field)
 
     def coset_evaluate(self, offset, generator, order):
         """fast_coset_evaluate (code/ntt.py:132-135) -> DeviceCodeword"""
@@ -956,6 +981,105 @@ def fast_interpolate_columns(domain, values_list, primitive_root, root_order):
     matrix = DeviceVector.from_bytes(b"".join(_pack(values) for values in values_list))
     flat = _unpack(tables.interpolate_columns(matrix, cols).to_bytes(), cols * n, primitive_root.field)
     return [Polynomial(flat[c * n:(c + 1) * n]) for c in range(cols)]
+
+
+def evaluate_points_device(polynomials, points):
+    """[p.evaluate_points(points) for p in polynomials] for DevicePolynomials as ONE library call (sc_poly_eval_points_dev with
+    one column per polynomial) -> DeviceVectors of len(points) values that are rows of one matrix.  Shorter polynomials count as
+    zero-padded to the longest; equally spaced rows of one matrix are read where they lie (_as_matrix), anything else is copied
+    into one.  points: a list of FieldElements or a DeviceDomain."""
+    polynomials = list(polynomials)
+    if not polynomials:
+        return []
+    _require_main_field(polynomials[0].field)
+    xs = points.points_vector() if isinstance(points, DeviceDomain) else DeviceVector.from_bytes(_pack(points))
+    k, cols, m = xs.n, len(polynomials), max(len(p) for p in polynomials)
+    holder, ld = _as_matrix(polynomials, m) if m else (None, 0)
+    out = DeviceVector(max(cols * k, 1))
+    _sc._check(_sc.lib().sc_poly_eval_points_dev(holder.ptr if m else None, m, ld, cols, xs.ptr, k, out.ptr, k, None))
+    return [DeviceVector.wrap(out.ptr + 16 * k * c, k, out) for c in range(cols)]
+
+
+# ---- Polynomial.evaluate_domain, interpolate_domain and zerofier_domain (code/univariate.py:104-128) on host lists: the same values
+# and list lengths as the host methods, for any points (repeated ones included), no root and no order to pass.
+# fast_evaluate_domain goes DIRECT (sc_poly_eval_points: m * k products) when either bound holds and through the domain's tree or
+# progression tables (_device_tree) otherwise.  Measured (tools/evaluate_timing.py, profiles/poly_evaluate/; DESIGN.md section 3.6e):
+# with host lists in and out the direct route beat the tree built in the call (the cold figure, which decides) at EVERY shape
+# measured, m = 16 .. 16 384 coefficients by k = 16 .. 4 096 points -- x1.8 at 4 096 x 4 096 and at 16 384 x 4 096, x61 at
+# 16 384 x 16 -- and the memoised tree (warm) at every shape too (x1.2 at 4 096 x 4 096).  The bounds are therefore the largest
+# values measured; beyond BOTH nothing was measured, and the tree's O(k log^2 k) is taken on trust.
+EVAL_DIRECT_MAX_POINTS = 4096
+EVAL_DIRECT_MAX_COEFFS = 16384
+
+
+def _domain_field(domain):
+    field = domain[0].field
+    _require_main_field(field)
+    return field
+
+
+def fast_evaluate_domain(polynomial, domain):
+    """Polynomial.evaluate_domain: [polynomial.evaluate(d) for d in domain], one value per point"""
+    if not domain:
+        return []
+    field = _domain_field(domain)
+    m, k = polynomial.degree() + 1, len(domain)
+    if m == 0:
+        return [field.zero() for _ in domain]
+    coeffs = _pack(polynomial.coefficients[:m])
+    if k <= EVAL_DIRECT_MAX_POINTS or m <= EVAL_DIRECT_MAX_COEFFS:
+        out = ctypes.create_string_buffer(16 * k)
+        _sc._check(_sc.lib().sc_poly_eval_points(coeffs, m, _pack(domain), k, out))
+        return _unpack(out.raw, k, field)
+    return _unpack(_device_tree(domain).evaluate(DeviceVector.from_bytes(coeffs)).to_bytes(), k, field)
+
+
+def fast_evaluate_domain_columns(polynomials, domain):
+    """[p.evaluate_domain(domain) for p in polynomials] as one upload, ONE evaluation of all columns and one download"""
+    polynomials = list(polynomials)
+    if not polynomials or not domain:
+        return [[] for _ in polynomials]
+    field = _domain_field(domain)
+    degrees = [p.degree() for p in polynomials]
+    m, k, cols = max(degrees) + 1, len(domain), len(polynomials)
+    if m == 0:
+        return [[field.zero() for _ in domain] for _ in polynomials]
+    matrix = DeviceVector.from_bytes(b"".join(_pack(p.coefficients[:d + 1]) + bytes(16 * (m - d - 1)) for p, d in zip(polynomials, degrees)))
+    if k <= EVAL_DIRECT_MAX_POINTS or m <= EVAL_DIRECT_MAX_COEFFS:
+        xs, out = DeviceVector.from_bytes(_pack(domain)), DeviceVector(cols * k)
+        _sc._check(_sc.lib().sc_poly_eval_points_dev(matrix.ptr, m, m, cols, xs.ptr, k, out.ptr, k, None))
+    else:
+        out = _device_tree(domain).evaluate_columns(matrix, m, cols)
+    flat = _unpack(out.to_bytes(), cols * k, field)
+    return [flat[c * k:(c + 1) * k] for c in range(cols)]
+
+
+def fast_interpolate_domain(domain, values):
+    """Polynomial.interpolate_domain: len(domain) coefficients; a repeated point drops its terms as inverse(0) = 0 makes the host
+    method drop them (sc_polytree_interpolate_lagrange_columns_dev), nothing is raised"""
+    return fast_interpolate_domain_columns(domain, [values])[0]
+
+
+def fast_interpolate_domain_columns(domain, values_list):
+    """[Polynomial.interpolate_domain(domain, v) for v in values_list] as one upload, ONE interpolation of all columns and one download"""
+    values_list = list(values_list)
+    n = len(domain)
+    for values in values_list:
+        assert n == len(values), "number of elements in domain does not match number of values -- cannot interpolate"
+    assert n > 0, "cannot interpolate between zero points"
+    if not values_list:
+        return []
+    field = _domain_field(domain)
+    cols = len(values_list)
+    matrix = DeviceVector.from_bytes(b"".join(_pack(values) for values in values_list))
+    flat = _unpack(_device_tree(domain).interpolate_lagrange_columns(matrix, cols).to_bytes(), cols * n, field)
+    return [Polynomial(flat[c * n:(c + 1) * n]) for c in range(cols)]
+
+
+def fast_zerofier_domain(domain):
+    """Polynomial.zerofier_domain: the len(domain) + 1 coefficients of prod (X - d), multiplicities included"""
+    field = _domain_field(domain)
+    return Polynomial(_unpack(_device_tree(domain).zerofier().to_bytes(), len(domain) + 1, field))
 
 
 def fast_coset_evaluate_device(polynomial, offset, generator, order):

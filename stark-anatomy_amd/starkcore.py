@@ -96,6 +96,8 @@ SIGNATURES = {
     "sc_poly_mul_columns_dev": (_int, [_vp, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _u64, _vp]),
     "sc_poly_pow_dev": (_int, [_vp, _u64, _u64, _vp, _vp]),
     "sc_poly_product_dev": (_int, [_vp, _u64, _u64, _u64, _vp, _vp]),
+    "sc_poly_eval_points_dev": (_int, [_vp, _u64, _u64, _u64, _vp, _u64, _vp, _u64, _vp]),
+    "sc_poly_eval_points": (_int, [_vp, _u64, _vp, _u64, _vp]),
     "sc_poly_divmod": (_int, [_vp, _u64, _vp, _u64, _vp, _vp]),
     "sc_poly_divmod_dev": (_int, [_vp, _u64, _vp, _u64, _vp, _vp, _vp]),
     "sc_poly_divmod_columns_dev": (_int, [_vp, _u64, _u64, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _vp]),
@@ -167,6 +169,8 @@ SIGNATURES = {
     "sc_polytree_interpolate_dev": (_int, [_vp, _vp, _vp, _vp]),
     "sc_polytree_evaluate_columns_dev": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _u64, _vp]),
     "sc_polytree_interpolate_columns_dev": (_int, [_vp, _vp, _u64, _u64, _vp, _u64, _vp]),
+    "sc_polytree_interpolate_lagrange_columns_dev": (_int, [_vp, _vp, _u64, _u64, _vp, _u64, _vp]),
+    "sc_interpolate_lagrange": (_int, [_vp, _vp, _u64, _vp]),
     "sc_polytree_free": (_int, [_vp]),
     "sc_geodomain_create": (_int, [_vp, _vp, _u64, ctypes.POINTER(_vp), _vp]),
     "sc_geodomain_points": (_u64, [_vp]),
@@ -697,6 +701,20 @@ class PolyTree:
         _check(lib().sc_polytree_interpolate_columns_dev(self._h, values_matrix.ptr, self.k, cols, out.ptr, self.k, None))
         return out
 
+    def interpolate_lagrange(self, values):
+        """values: DeviceVector of k values -> DeviceVector of the k coefficients Polynomial.interpolate_domain gives for ANY points:
+        a repeated point drops its terms (inverse(0) = 0, code/algebra.py:87-89) where `interpolate` raises; the same coefficients
+        for distinct points"""
+        assert values.n == self.k
+        return self.interpolate_lagrange_columns(values, 1)
+
+    def interpolate_lagrange_columns(self, values_matrix, cols):
+        """`interpolate_columns` with those weights (sc_polytree_interpolate_lagrange_columns_dev)"""
+        assert values_matrix.n >= cols * self.k
+        out = DeviceVector(max(cols * self.k, 1))
+        _check(lib().sc_polytree_interpolate_lagrange_columns_dev(self._h, values_matrix.ptr, self.k, cols, out.ptr, self.k, None))
+        return out
+
     def free(self):
         if self._h is not None and _lib is not None:
             _lib.sc_polytree_free(self._h)
@@ -777,6 +795,11 @@ class GeoDomain:
         out = DeviceVector(max(cols * self.k, 1))
         _check(lib().sc_geodomain_interpolate_columns_dev(self._h, values_matrix.ptr, self.k, cols, out.ptr, self.k, None))
         return out
+
+    # the points of a progression are distinct, so Polynomial.interpolate_domain's interpolant is the interpolant: the names
+    # PolyTree has for it, so that what domain_tables returns is interchangeable
+    interpolate_lagrange = interpolate
+    interpolate_lagrange_columns = interpolate_columns
 
     def free(self):
         if self._h is not None and _lib is not None:

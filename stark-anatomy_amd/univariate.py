@@ -3,8 +3,8 @@
 Mirrors the interface and list-length conventions of reference code/univariate.py:3-160 (coefficient
 lists are little-endian, may carry trailing zeros; `degree()` ignores them, equality ignores them).
 Quadratic paths here (schoolbook multiply / long division / Lagrange) are the reference's own
-small-degree fallbacks and test oracles; the fast paths live in ntt.py and run on the GPU (`*` and
-`divide` / `/` / `%` hand long operands to them).
+small-degree fallbacks and test oracles; the fast paths live in ntt.py and run on the GPU (`*`, `^`,
+`divide` / `/` / `%`, and evaluate_domain / interpolate_domain / zerofier_domain hand long operands to them).
 Arithmetic is done on plain ints and wrapped back into FieldElement at the boundary.
 """
 from algebra import *
@@ -210,6 +210,9 @@ class Polynomial:
 
     # -- evaluation / interpolation ----------------------------------------------------------
     def evaluate(self, point):
+        """The value at ONE point stays on the host on purpose: packing a coefficient for an upload costs as much Python as its
+        Horner step below (0.35 us against 0.3 us), so a device route has nothing to gain from host lists.  A polynomial that
+        already lies in HBM is evaluated there: ntt.DevicePolynomial.evaluate."""
         field = point.field
         p = field.p
         x = point.value
@@ -218,7 +221,35 @@ class Polynomial:
             acc = (acc * x + v) % p
         return FieldElement(acc, field)
 
+    # The three quadratic methods below hand over to the GPU (ntt.fast_evaluate_domain, fast_interpolate_domain, fast_zerofier_domain:
+    # the same values and list lengths for any points, repeated ones included) from these thresholds on, in the main field only.
+    # FAST_EVAL_DOMAIN_MIN applies to the number of points AND to degree + 1.  Never below 32: the suite without a GPU and RescuePrime
+    # (27 points) run on machines without one, as FAST_DIV_MIN_LEN states.  10**9: switched off.
+    # Measured (tools/evaluate_timing.py, profiles/poly_evaluate/; DESIGN.md section 3.6e), host lists in and out, the rule being the
+    # smallest power of two from which the device route is at least 1.5x faster at every larger shape measured (32 .. 4 096 points).
+    # The COLD figure decides: the device side with ntt's memo cleared, so that the domain's tree, its inverse series and the weights
+    # are built in the call, as a first call on a new domain builds them (the memo holds 8 domains).  zerofier_domain: x0.5 at 32
+    # points (0.10 ms on the host against 0.19), x1.6 at 64 (0.36 against 0.22), x680 at 4 096; interpolate_domain: x1.0 at 32 (0.58
+    # against 0.61), x2.9 at 64 (2.1 against 0.71), x2 100 at 4 096 (8.0 s against 3.8 ms).  On a memoised domain (warm) both would
+    # pass at 32 (x1.9 and x3.8); that is not what decides.  evaluate_domain takes the direct kernel at these shapes and builds no
+    # tree: x2.0 at 32 points by 32 coefficients, x1 200 at 4 096 by 4 096, x42 and x16 at the lopsided 32 by 4 096 and 4 096 by 32.
+    # Nothing below 32 was measured, and nothing below 32 is allowed.
+    FAST_EVAL_DOMAIN_MIN = 32
+    FAST_INTERPOLATE_MIN_POINTS = 64
+    FAST_ZEROFIER_MIN_POINTS = 64
+
     def evaluate_domain(self, domain):
+        """[self.evaluate(d) for d in domain] (univariate.py:104-105); many points against a long polynomial in the main field are
+        evaluated on the GPU"""
+        least = Polynomial.FAST_EVAL_DOMAIN_MIN
+        if len(domain) >= least and len(self.coefficients) >= least and domain[0].field.p == Field.P_MAIN and self.coefficients[0].field.p == Field.P_MAIN:
+            # decide on the DEGREE, not the list length (lists may carry trailing zeros)
+            if self.degree() + 1 >= least:
+                from ntt import fast_evaluate_domain
+                return fast_evaluate_domain(self, domain)
+        return self._evaluate_domain_host(domain)
+
+    def _evaluate_domain_host(self, domain):
         return [self.evaluate(d) for d in domain]
 
     @staticmethod
@@ -230,6 +261,14 @@ class Polynomial:
         return out
 
     def interpolate_domain(domain, values):
+        """the interpolant of univariate.py:107-121, len(domain) coefficients; many points in the main field are interpolated on the
+        GPU, repeated abscissas included"""
+        if len(domain) >= Polynomial.FAST_INTERPOLATE_MIN_POINTS and len(domain) == len(values) and domain[0].field.p == Field.P_MAIN:
+            from ntt import fast_interpolate_domain
+            return fast_interpolate_domain(domain, values)
+        return Polynomial._interpolate_domain_host(domain, values)
+
+    def _interpolate_domain_host(domain, values):
         """Lagrange interpolation with the results (values AND list length len(domain)) of univariate.py:107-121, in
         O(n^2) instead of its O(n^3): the master polynomial Z = prod (X - x_j) once, then for every point the synthetic
         division Z / (X - x_i) weighted by y_i / prod_{j != i} (x_i - x_j).  The reference inverts each difference through
@@ -257,6 +296,14 @@ class Polynomial:
         return Polynomial(_wrap(out, field))
 
     def zerofier_domain(domain):
+        """prod (X - d) over the domain, len(domain) + 1 coefficients (univariate.py:123-128); many points in the main field are
+        multiplied up on the GPU"""
+        if len(domain) >= Polynomial.FAST_ZEROFIER_MIN_POINTS and domain[0].field.p == Field.P_MAIN:
+            from ntt import fast_zerofier_domain
+            return fast_zerofier_domain(domain)
+        return Polynomial._zerofier_domain_host(domain)
+
+    def _zerofier_domain_host(domain):
         """prod (X - d) over the domain, len(domain) + 1 coefficients (univariate.py:123-128)"""
         field = domain[0].field
         return Polynomial(_wrap(Polynomial._zerofier_ints([d.value for d in domain], field.p), field))
