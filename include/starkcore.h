@@ -382,7 +382,9 @@ int sc_scale_slab_dev(const void* d_in, void* d_out, uint64_t rows, uint64_t col
 int sc_zerofier(const void* points, uint64_t k, void* out);                                   /* out: k + 1 coefficients of prod (X - d_i) */
 int sc_evaluate(const void* coeffs, uint64_t m, const void* points, uint64_t k, void* out);   /* out[i] = poly(points[i]), any m */
 int sc_interpolate(const void* points, const void* values, uint64_t k, void* out);            /* out: k coefficients (degree < k) */
-/* the same on device pointers with the tree kept between calls (one tree serves any number of evaluations / interpolations) */
+/* the same on device pointers with the tree kept between calls (one tree serves any number of evaluations / interpolations).
+ * sc_polytree_build / sc_polytree_build_dev take 1 <= k <= 2^30 points (SC_ERR_BAD_ARG for k == 0, SC_ERR_UNSUPPORTED above 2^30);
+ * the tree pads them to K = the power of two >= k leaves and keeps about 3 * K * log2(K) elements. */
 int sc_polytree_build(const void* points, uint64_t k, sc_polytree_t** tree);                  /* k >= 1 */
 int sc_polytree_build_dev(const void* d_points, uint64_t k, sc_polytree_t** tree, void* stream);
 uint64_t sc_polytree_points(const sc_polytree_t* tree);
@@ -425,7 +427,9 @@ int sc_polytree_free(sc_polytree_t* tree);
  * Zerofier, values and interpolant are unique, so on such a domain they are computed with O(1) transforms of length
  * M = pow2 >= 2n - 1 (Bluestein / Bostan-Schost) instead of a tree: same outputs as sc_polytree_* / the reference's recursion.
  * create: n >= 2, distinct points required (SC_ERR_UNSUPPORTED otherwise: use the tree, which reproduces the reference's
- * behaviour for repeated points).  The *_dev calls only ENQUEUE on `stream` (NULL: the library stream): results are valid in
+ * behaviour for repeated points).  Accepted are 2 <= n with 2n - 1 <= 2^28 (M <= 2^28, so n <= 2^27), first and ratio non-zero
+ * residues below p, and ord(ratio) >= n: the full subgroup n = ord(ratio) is a progression, n = ord(ratio) + 1 repeats its first
+ * point.  Everything else is SC_ERR_UNSUPPORTED with *domain untouched and nothing kept.  The *_dev calls only ENQUEUE on `stream` (NULL: the library stream): results are valid in
  * stream order; nothing waits, temporaries are returned behind the stream.
  * detect: is d_points[i+1] == d_points[i] * ratio for all i (ratio = points[1] / points[0])?  one small kernel + one sync. */
 int sc_geodomain_create(const uint64_t first[2], const uint64_t ratio[2], uint64_t n, sc_geodomain_t** domain, void* stream);

@@ -23,6 +23,9 @@ def root_of(n):
     return po.primitive_nth_root(n)
 
 
+C_TRANSFORM_FROM = 64        # columns at least this long go to the C oracle's transform: the same numbers, in time for K = 1024
+
+
 def ntt_cols(a, length, batch, inverse=False):
     """transform along axis 0 of the [length][batch] array `a` (flat list), natural order in and out"""
     if length == 1:
@@ -31,7 +34,11 @@ def ntt_cols(a, length, batch, inverse=False):
     out = [0] * (length * batch)
     for b in range(batch):
         col = a[b::batch]
-        res = po.intt(r, col) if inverse else po.ntt(r, col)
+        if length >= C_TRANSFORM_FROM:
+            raw = (po.C.intt if inverse else po.C.ntt)(r, b"".join(x.to_bytes(16, "little") for x in col), length)
+            res = [int.from_bytes(raw[i:i + 16], "little") for i in range(0, 16 * length, 16)]
+        else:
+            res = po.intt(r, col) if inverse else po.ntt(r, col)
         out[b::batch] = res
     return out
 
@@ -95,6 +102,18 @@ class Tree:
             D = [C[f * B + (i >> 1)] * zf[((n - f) % n) * 2 * B + (i ^ 1)] % P for f in range(n) for i in range(2 * B)]
             c = ntt_cols(D, n, 2 * B, inverse=True)[:K]               # first n/2 rows of [n][2B]
         return c[:self.k]
+
+    def evaluate_chunked(self, coeffs, points):
+        """polytree_evaluate for any number of coefficients: Horner over chunks of K with y_i = x_i^K (pt_pow2_kernel, pt_horner_kernel)"""
+        K = self.K
+        if len(coeffs) <= K:
+            return self.evaluate(coeffs)
+        y = [pow(x, K, P) for x in points]
+        chunks = [coeffs[j:j + K] for j in range(0, len(coeffs), K)]
+        acc = self.evaluate(chunks[-1])
+        for chunk in reversed(chunks[:-1]):
+            acc = [(a * yi + e) % P for a, yi, e in zip(acc, y, self.evaluate(chunk))]
+        return acc
 
     def interpolate(self, values):
         k, K, L, pad = self.k, self.K, self.L, self.pad
