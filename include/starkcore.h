@@ -495,7 +495,8 @@ int sc_mpoly_eval_columns_dev(const void* d_vals, uint64_t nvars, uint64_t n, ui
 int sc_scale_columns_dev(const void* d_in, uint64_t ld_in, void* d_out, uint64_t ld_out, uint64_t n, uint64_t cols, const uint64_t factor[2], void* stream);
 
 /* ---- Rescue-Prime : code/rescue_prime.py:25-60 (hash), :62-104 (trace) ----------------------- */
-/* The permutation of the tutorial's hash over n inputs, one lane each.  The state width is fixed: m = 2 (rate 1, capacity 1), alpha = 3.
+/* The permutation of the tutorial's hash over n inputs, one lane each.  In these two entries the state width is fixed: m = 2 (rate 1,
+ * capacity 1), alpha = 3; the entries below them take any width.
  * d_in: n elements (reduced mod p on load).  params: HOST pointer to 4 + 4 * rounds packed canonical residues -- the MDS matrix
  * (row-major, 2 x 2), then the 2 m rounds round constants (round r: [4 r, 4 r + 2) after the cube, [4 r + 2, 4 r + 4) after the
  * inverse cube).  params is read for exactly 4 + 4 * rounds words: what lies behind them is neither read nor checked.
@@ -505,6 +506,32 @@ int sc_scale_columns_dev(const void* d_in, uint64_t ld_in, void* d_out, uint64_t
  * SC_ERR_BAD_ARG: rounds == 0 or > 27, a constant not below p, params NULL, or a NULL buffer with n > 0. */
 int sc_rescue_prime_hash_dev(const void* d_in, uint64_t n, const void* params, uint64_t rounds, void* d_out, void* stream);
 int sc_rescue_prime_trace_dev(const void* d_in, uint64_t n, const void* params, uint64_t rounds, void* d_out, void* stream);
+/* The same permutation at any state width m = 2 .. 8 (alpha = 3), one lane per input, the state in registers.  Matrices are
+ * COALESCED: register s of input k is element s * ld + k of its matrix, ld >= n.  params: HOST pointer to m * m + 2 * m * rounds
+ * packed canonical residues -- the MDS matrix (row-major, m x m), then the round constants (round r: [2 r m, 2 r m + m) after the
+ * cube, [2 r m + m, 2 (r + 1) m) after the inverse cube) -- read for exactly that many words during the call.  Every input word is
+ * reduced mod p on load.  n == 0: SC_OK, nothing is launched.
+ * permute:      d_out[s * ld_out + k] = register s of the permuted state of input k (m rows each).  d_out may be d_in with
+ *               ld_out == ld_in (in place: every element is read by the lane that writes it).
+ * sponge:       the state starts at zero; for each of `blocks` >= 1 blocks the message elements b * rate .. b * rate + rate - 1 of
+ *               input k (element j at d_msg[j * ld_msg + k], blocks * rate rows) are added into registers 0 .. rate - 1, then the
+ *               state is permuted; afterwards registers 0 .. out_len - 1 go to d_out[j * ld_out + k], 1 <= out_len <= rate,
+ *               1 <= rate <= m - 1.  Padding is the caller's.  m = 2, rate = 1, blocks = 1, out_len = 1: sc_rescue_prime_hash_dev's
+ *               result, bit for bit.
+ * trace_states: all rounds + 1 states of n initial states (m rows of d_in), register s of input k's state t at
+ *               d_out[(m * k + s) * (rounds + 1) + t] (m n (rounds + 1) elements): one input's registers are m adjacent columns.
+ * SC_ERR_BAD_ARG, before anything is enqueued: m outside 2 .. 8, rate outside 1 .. m - 1, out_len outside 1 .. rate, blocks == 0,
+ * rounds outside 1 .. 27, a constant not below p, params NULL, a NULL buffer with n > 0, a stride below n, an output that overlaps
+ * an input (other than permute in place as above).
+ * The calls only enqueue on `stream` and wait for nothing.  The constants travel as kernel arguments into a block of the call's own
+ * (returned to the pool behind the streams in use): no shared scratch, no one-stream rule -- the operands must be complete on
+ * `stream`, and calls on different streams do not disturb one another. */
+int sc_rescue_prime_permute_dev(const void* d_in, uint64_t ld_in, void* d_out, uint64_t ld_out, uint64_t n, uint64_t m,
+                                const void* params, uint64_t rounds, void* stream);
+int sc_rescue_prime_sponge_dev(const void* d_msg, uint64_t ld_msg, uint64_t blocks, void* d_out, uint64_t ld_out, uint64_t out_len,
+                               uint64_t n, uint64_t m, uint64_t rate, const void* params, uint64_t rounds, void* stream);
+int sc_rescue_prime_trace_states_dev(const void* d_in, uint64_t ld_in, uint64_t n, uint64_t m, const void* params, uint64_t rounds,
+                                     void* d_out, void* stream);
 
 /* ---- FRI split-and-fold : code/fri.py:85 ---------------------------------------------------- */
 /* out[i] = 2^-1 * ((1 + alpha/(offset*omega^i)) * in[i] + (1 - alpha/(offset*omega^i)) * in[N/2+i]), i < N/2 */

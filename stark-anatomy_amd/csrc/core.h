@@ -6,7 +6,7 @@
 //   merkle_fri.hip    Merkle trees and forests of them, the FRI fold and commit loop, the Fiat-Shamir transcript, openings
 //   polytree_geo.hip  subproduct trees and geometric progressions (fast_zerofier / fast_evaluate / fast_interpolate)
 //   fourstep.hip      batched transforms, the sharded four-step plan, the RCCL communicator, the direct-store corner turn
-//   rescue.hip        the Rescue-Prime permutation (hash and trace) over many inputs
+//   rescue.hip        the Rescue-Prime permutation (hash and trace; permutation, sponge and states at any width 2 .. 8) over many inputs
 //   polyeval.hip      polynomials in HBM evaluated at a list of points directly (csrc/polyeval.cuh)
 //   columns.hip       division, combination and one deferred verdict over a matrix of polynomial columns (csrc/columns.cuh); the
 //                     verifier's combination at the opened points as rows (csrc/combination.cuh)

@@ -1,5 +1,6 @@
 // rescue_prime.cuh -- the Rescue-Prime permutation of the tutorial's signature scheme (reference code/rescue_prime.py:25-60 hash,
-// :62-104 trace) for state width m = 2 (rate 1, capacity 1), alpha = 3, one lane per input.
+// :62-104 trace) for state width m = 2 (rate 1, capacity 1), alpha = 3, one lane per input; below it the same permutation for any
+// width 2 .. 8 with its constants in memory (permutation, sponge, all states).
 //
 // Host-and-device code like field.cuh: g++ compiles the same functions for the CPU emulation test (tests/emu/rescue_emu.cpp), hipcc
 // for rescue_kernel (csrc/rescue.hip).  Everything runs in the Montgomery domain: the input is converted once on load, every value
@@ -108,6 +109,169 @@ SC_HD void rp_permute(const RescueParams& P, int rounds, Fe x, Fe* hash_out, Fe*
         }
     }
     if (!TRACE) *hash_out = from_mont(a);
+}
+
+// ---- any state width 2 <= M <= 8 (sc_rescue_prime_permute_dev / _sponge_dev / _trace_states_dev) ---------------------------------
+//
+// The same permutation for a compile-time width M: one lane per input, the M state elements in registers, alpha = 3.  The state goes
+// through rp_cube2 / rp_invcube2 two elements at a time; an odd width leaves one element over, which takes the one-chain forms
+// below (the same addition chain through mont_mul).  Modular products per permutation: per round and element 2 + 142, and two
+// M x M matrix products: (144 M + 2 M^2) * rounds (M = 2, 27 rounds: the 7 992 above), plus one conversion per element loaded or stored.
+//
+// The constants no longer fit a kernel argument (M = 8, 27 rounds: 64 + 432 elements, 7 936 bytes): they are read from memory, at
+// addresses every lane of a wave shares (scalar loads on the device).  `C`: M * M matrix entries, row-major, then 2 M rounds round
+// constants (round r: [2 r M, 2 r M + M) after the cube, [2 r M + M, 2 (r + 1) M) after the inverse cube), all in Montgomery form.
+//
+// Register pressure is what bounds the width: the inverse cube of a pair keeps ten chain values next to the M state elements, the
+// matrix product keeps the old and the new state.  So the pair loop and the loop over the matrix rows stay ROLLED -- the state
+// (the new state) rotates through fixed registers, about 3 M^2 element moves per round next to its 72 M + M^2 paired products --
+// and the chain's code exists once per kernel, not M / 2 times.
+constexpr int RP_MAX_M = 8;
+
+#if defined(__clang__)
+#define SC_RP_ROLLED _Pragma("clang loop unroll(disable)")
+#define SC_RP_UNROLLED _Pragma("unroll")
+#else
+#define SC_RP_ROLLED
+#define SC_RP_UNROLLED
+#endif
+
+SC_HD Fe rp_reduce(Fe x) {                                     // x mod p for any 128-bit x (2^128 < 2p)
+    if (fe_ge_p(x)) x = Fe{x.lo - P_LO, x.hi - P_HI - (x.lo < P_LO)};
+    return x;
+}
+
+// the one-chain forms of rp_sqr2_n, rp_block2, rp_cube2 and rp_invcube2 (the element an odd width leaves over)
+SC_HD void rp_sqr1_n(Fe& a, int n) {
+    for (int i = 0; i < n; ++i) a = mont_mul(a, a);
+}
+SC_HD void rp_block1(Fe& a, Fe a0, int k) {
+    rp_sqr1_n(a, 2 * k);
+    a = mont_mul(a, a0);
+}
+SC_HD void rp_cube1(Fe& a) {
+    a = mont_mul(mont_mul(a, a), a);
+}
+SC_HD void rp_invcube1(Fe& a) {
+    const Fe a1 = a;
+    Fe a2 = a;  rp_block1(a2, a1, 1);
+    Fe a3 = a2; rp_block1(a3, a1, 1);
+    Fe a5 = a3; rp_block1(a5, a2, 2);
+    Fe ac = a5; rp_block1(ac, a2, 2);                          // B_7
+    rp_block1(ac, ac, 7);
+    rp_block1(ac, ac, 14);
+    rp_block1(ac, ac, 28);
+    rp_block1(ac, a3, 3);                                      // B_59
+    const Fe ay = ac;
+    const Fe az = mont_mul(ay, a1);
+    rp_sqr1_n(ac, 1); ac = mont_mul(ac, az);
+    rp_sqr1_n(ac, 3); ac = mont_mul(ac, ay);
+    rp_sqr1_n(ac, 2); ac = mont_mul(ac, az);
+    rp_sqr1_n(ac, 1); ac = mont_mul(ac, az);
+    rp_sqr1_n(ac, 1); ac = mont_mul(ac, az);
+    rp_sqr1_n(ac, 1); ac = mont_mul(ac, a1);
+    rp_sqr1_n(ac, 1); a = mont_mul(ac, a1);
+}
+
+// s <- s rotated left by K places (constant indices only: the state stays in registers)
+template <int M, int K>
+SC_HD void rp_rotate(Fe (&s)[M]) {
+    Fe t[K];
+    SC_RP_UNROLLED
+    for (int i = 0; i < K; ++i) t[i] = s[i];
+    SC_RP_UNROLLED
+    for (int i = 0; i + K < M; ++i) s[i] = s[i + K];
+    SC_RP_UNROLLED
+    for (int i = 0; i < K; ++i) s[M - K + i] = t[i];
+}
+
+// every element to its cube (INV: to its alphainv-th power).  Pairs go through s[0], s[1] and the state rotates by two; after M / 2
+// pairs and the single element of an odd width the state has gone round once.
+template <int M, bool INV>
+SC_HD void rp_sbox_w(Fe (&s)[M]) {
+    SC_RP_ROLLED
+    for (int q = 0; q < M / 2; ++q) {
+        if (INV) rp_invcube2(s[0], s[1]);
+        else rp_cube2(s[0], s[1]);
+        rp_rotate<M, 2>(s);
+    }
+    if (M & 1) {
+        if (INV) rp_invcube1(s[0]);
+        else rp_cube1(s[0]);
+        rp_rotate<M, 1>(s);
+    }
+}
+
+// s <- MDS s + c: row i of the matrix against the state, two products at a time (the last one of an odd width alone), the sums
+// collected in t, which rotates by one per row
+template <int M>
+SC_HD void rp_mix_w(const Fe* mds, const Fe* c, Fe (&s)[M]) {
+    Fe t[M];
+    SC_RP_UNROLLED
+    for (int i = 0; i < M; ++i) t[i] = fe_zero();
+    SC_RP_ROLLED
+    for (int i = 0; i < M; ++i) {
+        const Fe* row = mds + i * M;
+        Fe acc = c[i];
+        SC_RP_UNROLLED
+        for (int j = 0; j + 1 < M; j += 2) {
+            Fe u, v;
+            mont_mul2(row[j], s[j], row[j + 1], s[j + 1], u, v);
+            acc = fe_add(acc, fe_add(u, v));
+        }
+        if (M & 1) acc = fe_add(acc, mont_mul(row[M - 1], s[M - 1]));
+        rp_rotate<M, 1>(t);
+        t[M - 1] = acc;
+    }
+    SC_RP_UNROLLED
+    for (int i = 0; i < M; ++i) s[i] = t[i];
+}
+
+// One round on a Montgomery-form state: cube, mix, constants; inverse cube, mix, constants.
+template <int M>
+SC_HD void rp_round_w(const Fe* C, int r, Fe (&s)[M]) {
+    const Fe* rc = C + M * M + 2 * M * r;
+    rp_sbox_w<M, false>(s);
+    rp_mix_w<M>(C, rc, s);
+    rp_sbox_w<M, true>(s);
+    rp_mix_w<M>(C, rc + M, s);
+}
+
+// What one lane does for input k of the three entries.  The state starts at zero; for each of `blocks` blocks, element j < rate of
+// the block (any 128-bit value, reduced mod p) at in[(b * rate + j) * ld_in + k] is added into register j, then the state is
+// permuted.  Afterwards registers 0 .. out_len - 1 go to out[j * ld_out + k] (canonical).  A plain permutation is one block of
+// rate M with out_len M: the sum with the zero state is the load.  TRACE (one block): all rounds + 1 states instead, register s of
+// state t at trace[s * (rounds + 1) + t].
+template <int M, bool TRACE>
+SC_HD void rp_sponge_w(const Fe* C, int rounds, const Fe* in, uint64_t ld_in, uint64_t blocks, int rate,
+                       Fe* out, uint64_t ld_out, int out_len, Fe* trace) {
+    Fe s[M];
+    SC_RP_UNROLLED
+    for (int j = 0; j < M; ++j) s[j] = fe_zero();
+    for (uint64_t b = 0; b < blocks; ++b) {
+        SC_RP_UNROLLED
+        for (int j = 0; j < M; ++j)
+            if (j < rate) {
+                const Fe x = rp_reduce(in[(b * (uint64_t)rate + j) * ld_in]);
+                if (TRACE) trace[(uint64_t)j * (rounds + 1)] = x;
+                s[j] = fe_add(s[j], to_mont(x));
+            } else if (TRACE) {
+                trace[(uint64_t)j * (rounds + 1)] = fe_zero();
+            }
+        SC_RP_ROLLED
+        for (int r = 0; r < rounds; ++r) {
+            rp_round_w<M>(C, r, s);
+            if (TRACE) {
+                SC_RP_UNROLLED
+                for (int j = 0; j < M; ++j) trace[(uint64_t)j * (rounds + 1) + r + 1] = from_mont(s[j]);
+            }
+        }
+    }
+    if (!TRACE) {
+        SC_RP_UNROLLED
+        for (int j = 0; j < M; ++j)
+            if (j < out_len) out[(uint64_t)j * ld_out] = from_mont(s[j]);
+    }
 }
 
 }  // namespace sc

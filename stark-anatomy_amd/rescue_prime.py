@@ -1,8 +1,9 @@
 """The Rescue-Prime hash of the tutorial's signature scheme (interface of reference code/rescue_prime.py:5-155).
 
 `RescuePrime()` with `hash`, `trace`, `boundary_constraints`, `round_constants_polynomials` and `transition_constraints`, the
-reference's call signatures and results.  The parameters (state width m = 2, capacity 1, N = 27 rounds, alpha = 3) are the
-reference's; the constants are DERIVED here the way the public Rescue-Prime specification defines them, not copied:
+reference's call signatures and results.  The default parameters (state width m = 2, capacity 1, N = 27 rounds, alpha = 3) are the
+reference's; `RescuePrime(m, capacity, rounds, security_level)` is the same construction at any width 2 .. 8 (rate = m - capacity;
+the round count is the caller's).  The constants are DERIVED here the way the public Rescue-Prime specification defines them, not copied:
 
 - round constants: SHAKE-256(b"Rescue-XLIX(p,m,capacity,security_level)") read as 2 m N chunks of ceil(128 / 8) + 1 = 17 bytes,
   each a little-endian integer mod p;
@@ -11,7 +12,10 @@ reference's; the constants are DERIVED here the way the public Rescue-Prime spec
 
 `hash` and `trace` are the host mirror of the reference (the same results for any caller).  The batched forms run on the MI355X
 (csrc/rescue_prime.cuh through sc_rescue_prime_hash_dev / sc_rescue_prime_trace_dev): `hash_batch`, `hash_device`, `trace_device`
-(a DeviceTrace FastStark.prove takes as it is) and `trace_batch_device`.
+(a DeviceTrace FastStark.prove takes as it is) and `trace_batch_device`.  At any other width, or with more than one input element,
+they go through the generic-width entries (sc_rescue_prime_permute_dev / _sponge_dev / _trace_states_dev), as do
+`permutation_device`, `sponge_device`, `sponge_batch` and `compress`; `permutation` and `sponge` are their host model on plain
+integers.  The sponge pads every message with a single 1, then zeros up to a multiple of the rate.
 
 `transition_constraints` returns the reference's MPolynomial dictionaries (the prover's byte parity depends on them), cached per
 omicron, as RescueConstraint objects whose `evaluator()` -- what FastStark.verify and verify_batch call at every opened point --
@@ -123,15 +127,16 @@ class RescueConstraint(MPolynomial):
 
 
 class RescuePrime:
-    def __init__(self):
+    def __init__(self, m=2, capacity=1, rounds=27, security_level=128):
+        assert 2 <= m <= 8 and 1 <= capacity < m and 1 <= rounds <= 27, "state width 2 .. 8, capacity 1 .. m - 1, 1 .. 27 rounds"
         self.p = 407 * (1 << 119) + 1
         self.field = Field(self.p)
-        self.m = 2
-        self.rate = 1
-        self.capacity = 1
-        self.N = 27
+        self.m = m
+        self.rate = m - capacity
+        self.capacity = capacity
+        self.N = rounds
         self.alpha = 3
-        self.security_level = 128
+        self.security_level = security_level
         mds, mds_inv, constants, self.alphainv = derive_parameters(self.p, self.m, self.capacity, self.security_level, self.N, self.alpha)
         fe = lambda v: FieldElement(v, self.field)
         self.MDS = [[fe(v) for v in row] for row in mds]
@@ -142,28 +147,67 @@ class RescuePrime:
         self._constraints = {}
 
     # ---- the host mirror (code/rescue_prime.py:25-104), on residues
-    def _states(self, value):
+    def _residues(self, inputs, limit):
+        """one element or a list of up to `limit` elements (FieldElements or ints) as residues"""
+        values = list(inputs) if isinstance(inputs, (list, tuple)) else [inputs]
+        assert 1 <= len(values) <= limit, "1 .. %d elements expected" % limit
+        return [int(getattr(v, "value", v)) % self.p for v in values]
+
+    def _round(self, state, r):
+        """round r on a state of residues: cube, mix, constants; inverse cube, mix, constants"""
         p, m, mds, rc = self.p, self.m, self._mds, self._constants
-        state = [value % p] + [0] * (m - 1)
+        for exponent, offset in ((self.alpha, 2 * r * m), (self.alphainv, 2 * r * m + m)):
+            powered = [pow(s, exponent, p) for s in state]
+            state = [(sum(mds[i][j] * powered[j] for j in range(m)) + rc[offset + i]) % p for i in range(m)]
+        return state
+
+    def _states(self, inputs):
+        """the N + 1 states from the rate part `inputs` (one residue or up to `rate` of them; the other registers start at zero)"""
+        values = self._residues(inputs, self.rate)
+        state = values + [0] * (self.m - len(values))
         yield state
         for r in range(self.N):
-            for exponent, offset in ((self.alpha, 2 * r * m), (self.alphainv, 2 * r * m + m)):
-                powered = [pow(s, exponent, p) for s in state]
-                state = [(sum(mds[i][j] * powered[j] for j in range(m)) + rc[offset + i]) % p for i in range(m)]
+            state = self._round(state, r)
             yield state
+
+    def permutation(self, state):
+        """the N rounds on a whole state of m plain integers"""
+        state = self._residues(state, self.m)
+        assert len(state) == self.m, "a state of m elements"
+        for r in range(self.N):
+            state = self._round(state, r)
+        return state
+
+    def pad(self, elements):
+        """the message, a single 1, then zeros up to a multiple of the rate -- always at least the 1, so that messages of different
+        lengths never share a padded form"""
+        values = [int(getattr(v, "value", v)) % self.p for v in elements] + [1]
+        return values + [0] * (-len(values) % self.rate)
+
+    def sponge(self, elements, out_len=1):
+        """the digest (out_len plain integers, 1 <= out_len <= rate) of a message of any length: padded, absorbed `rate` elements
+        per permutation into a zero state, registers 0 .. out_len - 1 squeezed"""
+        assert 1 <= out_len <= self.rate, "1 <= out_len <= rate"
+        padded = self.pad(elements)
+        state = [0] * self.m
+        for b in range(0, len(padded), self.rate):
+            block = padded[b:b + self.rate]
+            state = self.permutation([(s + v) % self.p for s, v in zip(state, block)] + state[self.rate:])
+        return state[:out_len]
 
     def hash(self, input_element):
         last = None
-        for last in self._states(input_element.value):
+        for last in self._states(input_element):
             pass
         return FieldElement(last[0], self.field)
 
     def trace(self, input_element):
-        return [[FieldElement(s, self.field) for s in state] for state in self._states(input_element.value)]
+        return [[FieldElement(s, self.field) for s in state] for state in self._states(input_element)]
 
     def boundary_constraints(self, output_element):
-        # at the start the capacity is zero; at the end the rate part is the given output element
-        return [(0, 1, self.field.zero()), (self.N, 0, output_element)]
+        # at the start the capacity is zero; at the end the first rate element is the given output element.  (FastStark wants at
+        # least one condition per register: at a rate above 1 the caller adds (0, s, input s) for the inputs that are public.)
+        return [(0, s, self.field.zero()) for s in range(self.rate, self.m)] + [(self.N, 0, output_element)]
 
     def round_constants_polynomials(self, omicron):
         domain = [omicron ^ r for r in range(0, self.N)]
@@ -208,7 +252,7 @@ class RescuePrime:
         domain = [omicron ^ i for i in range(self.N, self.N + num_randomizers)]
         return MPolynomial.lift(Polynomial.zerofier_domain(domain), 0)
 
-    # ---- batched on the MI355X (sc_rescue_prime_hash_dev / sc_rescue_prime_trace_dev)
+    # ---- batched on the MI355X (sc_rescue_prime_hash_dev / sc_rescue_prime_trace_dev; any other width: the generic-width entries)
     def _launch(self, entry, vec, out):
         import starkcore as sc
         sc._check(getattr(sc.lib(), entry)(vec.ptr if vec.n else None, vec.n, self._params, self.N, out.ptr if out.n else None, None))
@@ -217,6 +261,9 @@ class RescuePrime:
     def hash_device(self, vec):
         """DeviceVector of n inputs -> DeviceVector of their n hashes (enqueued on the library stream)"""
         import starkcore as sc
+        if self.m != 2:                             # register 0 of the permuted states (input, 0 .. 0)
+            out = self.permutation_device(self._initial_states(vec, vec.n), vec.n)
+            return sc.DeviceVector.wrap(out.ptr, vec.n, out)
         return self._launch("sc_rescue_prime_hash_dev", vec, sc.DeviceVector(vec.n))
 
     def hash_batch(self, elements):
@@ -228,18 +275,76 @@ class RescuePrime:
         out = self.hash_device(sc.DeviceVector.from_bytes(sc.pack([e.value for e in elements])))
         return [FieldElement(v, self.field) for v in sc.unpack(out.to_bytes())]
 
-    def trace_batch_device(self, vec):
-        """the traces of n inputs as one DeviceVector of 2 n (N + 1) elements: register s of input k's state t at
-        (2 k + s) (N + 1) + t -- one input's column is one run"""
+    def permutation_device(self, matrix, n):
+        """n states as a DeviceVector of m n elements, register s of state k at s n + k -> their permutations, laid out the same"""
         import starkcore as sc
-        return self._launch("sc_rescue_prime_trace_dev", vec, sc.DeviceVector(2 * vec.n * (self.N + 1)))
+        assert matrix.n == self.m * n, "m rows of n elements"
+        out = sc.DeviceVector(self.m * n)
+        sc._check(sc.lib().sc_rescue_prime_permute_dev(matrix.ptr if n else None, n, out.ptr if n else None, n, n, self.m, self._params, self.N, None))
+        return out
+
+    def sponge_device(self, matrix, n, blocks, out_len=1):
+        """n padded messages of `blocks` blocks as a DeviceVector of blocks * rate * n elements, element j of message k at j n + k
+        -> their digests as out_len * n elements, element j of digest k at j n + k"""
+        import starkcore as sc
+        assert matrix.n == blocks * self.rate * n, "blocks * rate rows of n elements"
+        out = sc.DeviceVector(out_len * n)
+        sc._check(sc.lib().sc_rescue_prime_sponge_dev(matrix.ptr if n else None, n, blocks, out.ptr if n else None, n, out_len, n, self.m, self.rate,
+                                                      self._params, self.N, None))
+        return out
+
+    def sponge_batch(self, messages, out_len=1):
+        """[self.sponge(msg, out_len) for msg in messages] for messages of one length, in one launch"""
+        import starkcore as sc
+        padded = [self.pad(msg) for msg in messages]
+        if not padded:
+            return []
+        n, rows = len(padded), len(padded[0])
+        assert all(len(msg) == rows for msg in padded), "messages of one length"
+        assert 1 <= out_len <= self.rate, "1 <= out_len <= rate"
+        matrix = sc.DeviceVector.from_bytes(sc.pack([msg[j] for j in range(rows) for msg in padded]))
+        got = sc.unpack(self.sponge_device(matrix, n, rows // self.rate, out_len).to_bytes())
+        return [[got[j * n + k] for j in range(out_len)] for k in range(n)]
+
+    def compress(self, left, right):
+        """two-to-one: [self.sponge([l, r]) for l, r in zip(left, right)] in one launch"""
+        assert self.rate >= 2, "compressing two elements into one needs a rate of at least 2"
+        left, right = list(left), list(right)
+        assert len(left) == len(right), "as many left as right elements"
+        return self.sponge_batch([[l, r] for l, r in zip(left, right)])
+
+    def _initial_states(self, vec, n):
+        """rows of n rate elements each (a DeviceVector of rows * n, 1 <= rows <= rate) -> the m n initial states: the other registers zero"""
+        import starkcore as sc
+        rows = vec.n // n if n else 1
+        assert vec.n == rows * n and 1 <= rows <= self.rate, "1 .. rate rows of n elements"
+        states = sc.DeviceVector.zeros(self.m * n)
+        if n:
+            sc._check(sc.lib().sc_memcpy_dev(states.ptr, vec.ptr, vec.n, None))
+        return states
+
+    def trace_batch_device(self, vec, n=None):
+        """the traces of n inputs as one DeviceVector of m n (N + 1) elements: register s of input k's state t at
+        (m k + s) (N + 1) + t -- one input's column is one run.  vec: the n inputs; with `n` given, 1 .. rate rows of n elements
+        (element j of input k at j n + k) that fill registers 0 .. rows - 1"""
+        import starkcore as sc
+        if self.m == 2 and n is None:
+            return self._launch("sc_rescue_prime_trace_dev", vec, sc.DeviceVector(2 * vec.n * (self.N + 1)))
+        n = vec.n if n is None else n
+        states = self._initial_states(vec, n)
+        out = sc.DeviceVector(self.m * n * (self.N + 1))
+        sc._check(sc.lib().sc_rescue_prime_trace_states_dev(states.ptr if n else None, n, n, self.m, self._params, self.N, out.ptr if n else None, None))
+        return out
 
     def trace_device(self, input_element):
-        """self.trace(input_element) as a DeviceTrace (two columns of N + 1 rows in HBM): what FastStark.prove takes as its trace"""
+        """self.trace(input_element) as a DeviceTrace (m columns of N + 1 rows in HBM): what FastStark.prove takes as its trace.
+        input_element: one element or a list of up to `rate` elements"""
         import starkcore as sc
         from fast_stark import DeviceTrace
         rows = self.N + 1
-        whole = self.trace_batch_device(sc.DeviceVector.from_bytes(sc.fe_bytes(input_element.value % self.p)))
+        values = self._residues(input_element, self.rate)
+        vec = sc.DeviceVector.from_bytes(sc.pack(values))
+        whole = self.trace_batch_device(vec) if len(values) == 1 else self.trace_batch_device(vec, 1)
         base = whole.ptr
         columns = [sc.DeviceVector.wrap(base + 16 * rows * s, rows, whole) for s in range(self.m)]
         return DeviceTrace(columns, self.field)

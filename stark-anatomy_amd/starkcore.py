@@ -54,6 +54,9 @@ SIGNATURES = {
     "sc_urandom_prefetch": (_int, [_u64, ctypes.c_uint32]),
     "sc_rescue_prime_hash_dev": (_int, [_vp, _u64, _vp, _u64, _vp, _vp]),
     "sc_rescue_prime_trace_dev": (_int, [_vp, _u64, _vp, _u64, _vp, _vp]),
+    "sc_rescue_prime_permute_dev": (_int, [_vp, _u64, _vp, _u64, _u64, _u64, _vp, _u64, _vp]),
+    "sc_rescue_prime_sponge_dev": (_int, [_vp, _u64, _u64, _vp, _u64, _u64, _u64, _u64, _u64, _vp, _u64, _vp]),
+    "sc_rescue_prime_trace_states_dev": (_int, [_vp, _u64, _u64, _u64, _vp, _u64, _vp, _vp]),
     "sc_ntt": (_int, [_vp, _vp, _u64, _vp, _int]),
     "sc_ntt_dev": (_int, [_vp, _vp, _u64, _vp, _int, _vp]),
     "sc_ntt_columns_dev": (_int, [_vp, _vp, _u64, _u64, _vp, _int, _vp]),
