@@ -62,7 +62,7 @@ int sc_stream(void** stream_out);
 int sc_stream_join(void* other_stream);
 /* tuning knobs for experiments (defaults are the measured optimum; -1 = choose by size where applicable): key in
  * {"max_tile_log","loge","max_col_log","min_tiles_log","single_pass_max_log","max_digit_log","direct_tw_max_log",
- *  "xcd_remap","fixed_shapes","merkle_big_nlev","wave_local","prio_balance","loge_cols","tw_on_load","prune","fast_fixups","fri_tail","fri_tail_stall","small_divisor_direct","verify_stage_kb","forest_four_lane_wgs","div_cols_chunk","div_cols_launch_log","tree_cols_launch_log","eval_chunk_log","eval_points_across_min","eval_across_min_products_log"}.  Plans are re-derived on the next
+ *  "xcd_remap","fixed_shapes","merkle_big_nlev","wave_local","prio_balance","loge_cols","tw_on_load","prune","fast_fixups","fri_tail","fri_tail_stall","small_divisor_direct","verify_stage_kb","forest_four_lane_wgs","div_cols_chunk","div_cols_launch_log","tree_cols_launch_log","eval_chunk_log","eval_points_across_min","eval_across_min_products_log","rescue_tree_split_max_nodes"}.  Plans are re-derived on the next
  * call; results never depend on the tuning ("fri_tail_stall" = k >= 0 is a test hook: the host withholds the challenge after round k of
  * the persistent tail kernel, whose wait then gives up after 2^13 polls; -1 = off; "small_divisor_direct" = 0: sc_coset_divide* transforms a
  * divisor of <= 8 coefficients like any other instead of evaluating it point by point; "verify_stage_kb" = the size of the staging buffer
@@ -79,7 +79,8 @@ int sc_stream_join(void* other_stream);
  * them, a small input goes; "eval_points_across_min" = the number of points from which sc_poly_eval_points_dev takes its points-across-lanes kernel
  * instead of the coefficients-across-lanes one, 32 by default, at least 1; "eval_across_min_products_log" = log2 of the modular products
  * (m * k * cols) a call must have for that to apply, 26 by default, 0 .. 64 -- smaller calls do not fill the device and always spread a chunk
- * over a workgroup; 0 with "eval_points_across_min" = 1 takes the points-across-lanes kernel everywhere, which is how the tests reach it).  Two keys manage the device-memory pool instead (freed vectors and trees are kept
+ * over a workgroup; 0 with "eval_points_across_min" = 1 takes the points-across-lanes kernel everywhere, which is how the tests reach it; "rescue_tree_split_max_nodes" = a level of a Rescue-Prime Merkle tree, or a batch of paths of sc_rescue_merkle_verify_batch, of at most
+ * this many nodes runs one lane per state register instead of one lane per node, 0 = never, 2147483647 = always, -1 = the default, 65536: the largest level width of the measured sweep at which that form is the faster one by more than the spread of the repetitions at every state width measured, profiles/rescue_merkle).  Two keys manage the device-memory pool instead (freed vectors and trees are kept
  * on exact-size free lists, by default up to a quarter of the device's memory divided by the processes sharing the device;
  * environment STARKCORE_POOL_CAP_MB): "pool_cap_mb" = what the lists may keep from now on, "pool_trim" = hand everything on them
  * back to the device now (a caller whose own allocator -- torch's -- ran out of memory). */
@@ -532,6 +533,46 @@ int sc_rescue_prime_sponge_dev(const void* d_msg, uint64_t ld_msg, uint64_t bloc
                                uint64_t n, uint64_t m, uint64_t rate, const void* params, uint64_t rounds, void* stream);
 int sc_rescue_prime_trace_states_dev(const void* d_in, uint64_t ld_in, uint64_t n, uint64_t m, const void* params, uint64_t rounds,
                                      void* d_out, void* stream);
+
+/* ---- Merkle trees over the Rescue-Prime sponge (csrc/rescue_merkle.cuh) ----------------------- */
+/* A tree over the N rows (N a power of two, N >= 1) of a matrix, whose leaves and nodes are digests of digest_len = d field elements:
+ *   leaf(row) = sponge(row, out_len = d),  node(left, right) = sponge(left + right, out_len = d)
+ * with the sponge of the entries above at width m, rate 2 .. m - 1, 1 <= d <= rate, padded HERE (a single 1, then zeros up to a
+ * multiple of the rate; never in memory): width / rate + 1 permutations per leaf, 2 d / rate + 1 per node.  No domain separation
+ * between leaves and nodes.  Level j has N >> j nodes; node k of level j + 1 is node(level_j[2k], level_j[2k + 1]); a path's entry j is
+ * node (index >> j) ^ 1 of level j (log2 N entries, the sibling leaf's digest first).  params: as above, a HOST pointer.
+ * build_dev:  element j of row i at d_rows[j * ld + i], ld >= N (the `width` columns of a matrix of codewords, each contiguous, are
+ *             the rows of the tree); every word is reduced mod p on load.  Only enqueues on `stream` -- one upload of the constants
+ *             (kernel arguments, into a block of the call's own) and one launch per level -- and waits for nothing: no shared
+ *             scratch, no one-stream rule; the rows must be complete on `stream`, and builds on different streams do not disturb one another.
+ *             A level of at most sc_set_tuning("rescue_tree_split_max_nodes") nodes runs one lane per state REGISTER, a wider one
+ *             one lane per node; the results are the same bits.
+ * root:       waits for the build; digest_len canonical residues to the host.
+ * open_batch: k paths in one launch; item t, level j, element e at paths_out[((t * log2 N) + j) * digest_len + e] (host, canonical).
+ * level_copy_dev: level j as digest_len rows of N >> j elements (element e of node k at d_out[e * (N >> j) + k]), enqueued on
+ *             `stream` behind the build.
+ * verify_batch: HOST arrays, item-major: roots[t * digest_len + e], paths[((t * depth) + j) * digest_len + e], rows[t * width + e],
+ *             every word reduced mod p; verdicts_out[t] = 1 if the path leads from the row to the root, else 0.  All items share
+ *             depth (<= 63; 0 compares the leaf digest with the root), width and parameters; an item's whole walk runs inside one
+ *             launch, one lane per state register when k <= "rescue_tree_split_max_nodes", one lane per item otherwise.  Runs on
+ *             the library stream and waits.  k == 0: SC_OK, nothing is launched.
+ * SC_ERR_BAD_ARG, before anything is enqueued or allocated (*tree and the outputs stay as they were): m outside 2 .. 8, rate outside
+ * 2 .. m - 1, digest_len outside 1 .. rate, rounds outside 1 .. 27, width == 0, N zero or no power of two, ld < N, a NULL pointer
+ * where one is needed, a constant not below p, an index not below N (open) or 1 << depth (verify), depth > 63, a level above
+ * log2 N, byte counts that wrap. */
+typedef struct sc_rescue_tree sc_rescue_tree_t;   /* device-resident Rescue-Prime Merkle tree, all levels kept */
+int sc_rescue_merkle_build_dev(const void* d_rows, uint64_t ld, uint64_t width, uint64_t N, uint64_t digest_len,
+                               uint64_t m, uint64_t rate, const void* params, uint64_t rounds,
+                               sc_rescue_tree_t** tree, void* stream);
+int sc_rescue_merkle_root(sc_rescue_tree_t* tree, void* root_out /* digest_len elements, host */);
+int sc_rescue_merkle_open_batch(const sc_rescue_tree_t* tree, const uint64_t* indices, uint64_t k,
+                                void* paths_out /* host: k * log2 N * digest_len elements */);
+int sc_rescue_merkle_level_copy_dev(const sc_rescue_tree_t* tree, uint64_t level, void* d_out, void* stream);
+int sc_rescue_merkle_verify_batch(const void* roots, const uint64_t* indices, const void* paths, const void* rows,
+                                  uint64_t k, uint64_t depth, uint64_t width, uint64_t digest_len,
+                                  uint64_t m, uint64_t rate, const void* params, uint64_t rounds, uint8_t* verdicts_out);
+uint64_t sc_rescue_merkle_leaves(const sc_rescue_tree_t* tree);
+int sc_rescue_merkle_free(sc_rescue_tree_t* tree);
 
 /* ---- FRI split-and-fold : code/fri.py:85 ---------------------------------------------------- */
 /* out[i] = 2^-1 * ((1 + alpha/(offset*omega^i)) * in[i] + (1 - alpha/(offset*omega^i)) * in[N/2+i]), i < N/2 */

@@ -7,6 +7,7 @@
 //   polytree_geo.hip  subproduct trees and geometric progressions (fast_zerofier / fast_evaluate / fast_interpolate)
 //   fourstep.hip      batched transforms, the sharded four-step plan, the RCCL communicator, the direct-store corner turn
 //   rescue.hip        the Rescue-Prime permutation (hash and trace; permutation, sponge and states at any width 2 .. 8) over many inputs
+//   rescue_merkle.hip Merkle trees over the Rescue-Prime sponge: build, root, openings, batched path verification (csrc/rescue_merkle.cuh)
 //   polyeval.hip      polynomials in HBM evaluated at a list of points directly (csrc/polyeval.cuh)
 //   columns.hip       division, combination and one deferred verdict over a matrix of polynomial columns (csrc/columns.cuh); the
 //                     verifier's combination at the opened points as rows (csrc/combination.cuh)
@@ -134,6 +135,7 @@ struct Ctx {
     int eval_chunk_log = 8;          // sc_poly_eval_points_dev: log2 of the coefficients one workgroup takes at least (csrc/polyeval.hip); a test hook that decides how many chunks a small input goes through
     int eval_points_across_min = 32; // sc_poly_eval_points_dev: the number of points (of a call, of a last part-wave) from which the points-across-lanes form is taken ...
     int eval_across_min_products_log = 26;   // ... in calls of at least 2^this many modular products (0: in every call)
+    int rescue_tree_split_max_nodes = -1;    // sc_rescue_merkle_*: a level (a batch of paths) of at most this many nodes runs one lane per state register; 0: never, INT32_MAX: always, -1: the measured default (csrc/rescue_merkle.hip SPLIT_MAX_NODES_DEFAULT)
     int div_cols_chunk = 0;          // columns that share one batch inversion in pointwise_div_cols_kernel; 0: chosen by shape (columns.hip div_cols_chunk_for)
     std::vector<hipStream_t> seen_streams;   // those streams, most recent last (at most SEEN_STREAMS; more: device-wide waits)
     DevBuf scratch[8];       // 0: ntt work, 1..3: poly temporaries, 4: misc small, 5: merkle staging, 6: uploaded operands, 7: degree / exactness flag

@@ -1062,6 +1062,7 @@ int sc_set_tuning(const char* key, int value) {
     else if (k == "eval_chunk_log") g.eval_chunk_log = value < 8 ? 8 : (value > 24 ? 24 : value);                  // tests only: more chunks per column (csrc/polyeval.hip); at least one Horner stride
     else if (k == "eval_points_across_min") g.eval_points_across_min = value < 1 ? 1 : value;                     // which of the two forms of the evaluation kernel a number of points takes ...
     else if (k == "eval_across_min_products_log") g.eval_across_min_products_log = value < 0 ? 0 : (value > 64 ? 64 : value);   // ... in calls of at least 2^value products
+    else if (k == "rescue_tree_split_max_nodes") g.rescue_tree_split_max_nodes = value < -1 ? -1 : value;      // which form of the Rescue-Prime tree kernels a level takes (csrc/rescue_merkle.hip); -1 = the default
     else if (k == "verify_stage_kb") g.verify_stage_bytes = (size_t)(value < 16 ? 16 : value) << 10;           // (a chunk must hold one row of any depth)
     else if (k == "fri_tail_stall") g.fri_tail_stall = value;                               // tests only: see core.h
     else if (k == "pool_cap_mb") g_pool_cap = (size_t)(value < 0 ? 0 : value) << 20;       // what the free lists may keep from now on

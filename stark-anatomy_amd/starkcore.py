@@ -57,6 +57,13 @@ SIGNATURES = {
     "sc_rescue_prime_permute_dev": (_int, [_vp, _u64, _vp, _u64, _u64, _u64, _vp, _u64, _vp]),
     "sc_rescue_prime_sponge_dev": (_int, [_vp, _u64, _u64, _vp, _u64, _u64, _u64, _u64, _u64, _vp, _u64, _vp]),
     "sc_rescue_prime_trace_states_dev": (_int, [_vp, _u64, _u64, _u64, _vp, _u64, _vp, _vp]),
+    "sc_rescue_merkle_build_dev": (_int, [_vp, _u64, _u64, _u64, _u64, _u64, _u64, _vp, _u64, _vp, _vp]),
+    "sc_rescue_merkle_root": (_int, [_vp, _vp]),
+    "sc_rescue_merkle_open_batch": (_int, [_vp, _vp, _u64, _vp]),
+    "sc_rescue_merkle_level_copy_dev": (_int, [_vp, _u64, _vp, _vp]),
+    "sc_rescue_merkle_verify_batch": (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _u64, _vp, _u64, _vp]),
+    "sc_rescue_merkle_leaves": (_u64, [_vp]),
+    "sc_rescue_merkle_free": (_int, [_vp]),
     "sc_ntt": (_int, [_vp, _vp, _u64, _vp, _int]),
     "sc_ntt_dev": (_int, [_vp, _vp, _u64, _vp, _int, _vp]),
     "sc_ntt_columns_dev": (_int, [_vp, _vp, _u64, _u64, _vp, _int, _vp]),
