@@ -79,8 +79,8 @@ int sc_stream_join(void* other_stream);
  * them, a small input goes; "eval_points_across_min" = the number of points from which sc_poly_eval_points_dev takes its points-across-lanes kernel
  * instead of the coefficients-across-lanes one, 32 by default, at least 1; "eval_across_min_products_log" = log2 of the modular products
  * (m * k * cols) a call must have for that to apply, 26 by default, 0 .. 64 -- smaller calls do not fill the device and always spread a chunk
- * over a workgroup; 0 with "eval_points_across_min" = 1 takes the points-across-lanes kernel everywhere, which is how the tests reach it; "rescue_tree_split_max_nodes" = a level of a Rescue-Prime Merkle tree, or a batch of paths of sc_rescue_merkle_verify_batch, of at most
- * this many nodes runs one lane per state register instead of one lane per node, 0 = never, 2147483647 = always, -1 = the default, 65536: the largest level width of the measured sweep at which that form is the faster one by more than the spread of the repetitions at every state width measured, profiles/rescue_merkle).  Two keys manage the device-memory pool instead (freed vectors and trees are kept
+ * over a workgroup; 0 with "eval_points_across_min" = 1 takes the points-across-lanes kernel everywhere, which is how the tests reach it; "rescue_tree_split_max_nodes" = a level of a Rescue-Prime Merkle tree, or a batch of paths of sc_rescue_merkle_verify_batch or sc_rescue_merkle_path_trace_dev, of at most
+ * this many nodes runs one lane per state register instead of one lane per node, 0 = never, 2147483647 = always, -1 = the default, 65536: the largest level width of the measured sweep at which that form is the faster one by more than the spread of the repetitions at every state width measured, profiles/rescue_merkle; the path trace has no key of its own: at depth 20 that form is the faster one at every batch measured up to 65536, profiles/rescue_membership).  Two keys manage the device-memory pool instead (freed vectors and trees are kept
  * on exact-size free lists, by default up to a quarter of the device's memory divided by the processes sharing the device;
  * environment STARKCORE_POOL_CAP_MB): "pool_cap_mb" = what the lists may keep from now on, "pool_trim" = hand everything on them
  * back to the device now (a caller whose own allocator -- torch's -- ran out of memory). */
@@ -556,10 +556,25 @@ int sc_rescue_prime_trace_states_dev(const void* d_in, uint64_t ld_in, uint64_t 
  *             depth (<= 63; 0 compares the leaf digest with the root), width and parameters; an item's whole walk runs inside one
  *             launch, one lane per state register when k <= "rescue_tree_split_max_nodes", one lane per item otherwise.  Runs on
  *             the library stream and waits.  k == 0: SC_OK, nothing is launched.
+ * path_trace_dev: every state of k walks from a leaf DIGEST to the root, for trees whose node is one permutation (2 * digest_len <
+ *             rate), as the execution trace a STARK proves membership with (rescue_membership.py).  HOST inputs, item-major like
+ *             verify_batch's with the leaf digests in the place of the rows: leaves[t * digest_len + e], indices[t],
+ *             paths[((t * depth) + j) * digest_len + e], every word reduced mod p.  DEVICE output of k * W * T elements,
+ *             W = m + digest_len + 1 registers (the state, the sibling, the direction bit), T = depth * (rounds + 1) + 1 rows:
+ *             register s of item t's row r at d_out[((W * t + s) * T) + r], canonical residues -- one register of one item is one
+ *             run.  Row 0: the leaf digest, zeros elsewhere.  Row 1 + j * (rounds + 1): the digest reached and paths[..j..] in the
+ *             order bit j of the index says (the walk's own digest first when the bit is 0), then 1, then zeros; the `rounds` rows
+ *             behind it: the state after each round; all rounds + 1 rows carry paths[..j..] and the bit in registers m .. m + d.
+ *             Registers 0 .. d - 1 of row T - 1 are the root the walk reaches.  One launch, one lane per state register when
+ *             k <= "rescue_tree_split_max_nodes", one lane per item otherwise; the same bits.  The call only enqueues on `stream`,
+ *             apart from staging its inputs: up to 8 KiB per array they travel as kernel arguments and nothing is waited for,
+ *             larger ones are copied into a block of the call's own and `stream` is waited for once, BEFORE the kernel is
+ *             enqueued.  No shared scratch, no one-stream rule: calls on different streams do not disturb one another.  k == 0:
+ *             SC_OK, nothing is launched.
  * SC_ERR_BAD_ARG, before anything is enqueued or allocated (*tree and the outputs stay as they were): m outside 2 .. 8, rate outside
  * 2 .. m - 1, digest_len outside 1 .. rate, rounds outside 1 .. 27, width == 0, N zero or no power of two, ld < N, a NULL pointer
- * where one is needed, a constant not below p, an index not below N (open) or 1 << depth (verify), depth > 63, a level above
- * log2 N, byte counts that wrap. */
+ * where one is needed, a constant not below p, an index not below N (open) or 1 << depth (verify, path_trace), depth > 63, a level
+ * above log2 N, byte counts that wrap; path_trace also: depth == 0, 2 * digest_len >= rate. */
 typedef struct sc_rescue_tree sc_rescue_tree_t;   /* device-resident Rescue-Prime Merkle tree, all levels kept */
 int sc_rescue_merkle_build_dev(const void* d_rows, uint64_t ld, uint64_t width, uint64_t N, uint64_t digest_len,
                                uint64_t m, uint64_t rate, const void* params, uint64_t rounds,
@@ -571,6 +586,9 @@ int sc_rescue_merkle_level_copy_dev(const sc_rescue_tree_t* tree, uint64_t level
 int sc_rescue_merkle_verify_batch(const void* roots, const uint64_t* indices, const void* paths, const void* rows,
                                   uint64_t k, uint64_t depth, uint64_t width, uint64_t digest_len,
                                   uint64_t m, uint64_t rate, const void* params, uint64_t rounds, uint8_t* verdicts_out);
+int sc_rescue_merkle_path_trace_dev(const void* leaves, const uint64_t* indices, const void* paths, uint64_t k, uint64_t depth,
+                                    uint64_t digest_len, uint64_t m, uint64_t rate, const void* params, uint64_t rounds,
+                                    void* d_out, void* stream);
 uint64_t sc_rescue_merkle_leaves(const sc_rescue_tree_t* tree);
 int sc_rescue_merkle_free(sc_rescue_tree_t* tree);
 

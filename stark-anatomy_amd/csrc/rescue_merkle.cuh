@@ -15,6 +15,10 @@
 //          the other registers' powers across the lanes of its node for the mix and computes its own row of the matrix.  A lone
 //          wave's time goes with the instructions of one lane: a narrow level takes a half (M = 3, 4) to a quarter (M = 8) of the
 //          wide form's time -- 2 / M, not 1 / M, the wide lane's pairs being two independent chains side by side.
+//
+// Below the sponges, in both forms again: the TRACE of a path -- every state of the walk from a leaf digest to the root, with the
+// sibling and the direction bit beside it -- as the execution trace of a membership proof (rm_path_trace_w, rm_path_trace_split;
+// DESIGN.md 3.9c).
 #pragma once
 #include "rescue_prime.cuh"
 
@@ -118,6 +122,73 @@ SC_HD uint64_t rm_split_constant(int M, int round, int h, int r) {
     return (uint64_t)M * M + 2ull * M * round + (uint64_t)h * M + r;
 }
 
+// ---- the trace of a path (sc_rescue_merkle_path_trace_dev): every state of the walk from a leaf DIGEST to the root, for trees whose
+// node is one permutation (2 d < rate: the padded message left + right + [1] + zeros is one block).  W = M + d + 1 registers -- the
+// state, the sibling, the direction bit -- and T = depth * (rounds + 1) + 1 rows, register s of row t at out[s * T + t], canonical:
+//   row 0                      the leaf digest in registers 0 .. d - 1, zeros elsewhere
+//   row 1 + lvl (rounds + 1)   the first state of level lvl: the digest reached and path[lvl], in the order bit lvl of the index says,
+//                              then 1, then zeros; the `rounds` rows behind it hold the state after each round
+// and every row of a level carries path[lvl] and the bit in the sibling and bit registers.  The digest a level starts from is
+// registers 0 .. d - 1 of the row before its first: row lvl (rounds + 1).
+SC_HD uint64_t rm_trace_rows(int depth, int rounds) { return (uint64_t)depth * (rounds + 1) + 1; }
+// which element of a digest register r of a level's first state holds (r < 2 d; 0 otherwise, so that everybody may load one)
+SC_HD int rm_trace_element(int r, int d) { return r < d ? r : (r < 2 * d ? r - d : 0); }
+// register r of a level's first state, canonical; own, sib: element rm_trace_element(r, d) of the digest reached and of the sibling
+SC_HD Fe rm_trace_first(Fe own, Fe sib, int r, int d, unsigned bit) {
+    if (r < 2 * d) {
+        const bool walk = (unsigned)(r >= d) == bit;
+        return Fe{walk ? own.lo : sib.lo, walk ? own.hi : sib.hi};
+    }
+    return r == 2 * d ? fe_one() : fe_zero();
+}
+// column `col` (one run of T elements) from row t0 on: `count` copies of v
+SC_HD void rm_trace_fill(Fe* col, uint64_t t0, int count, Fe v) {
+    for (int i = 0; i < count; ++i) col[t0 + i] = v;
+}
+
+// wide: one lane walks the whole path.  The hand-over between two levels needs no buffer: the digest reached is read back from the
+// row the lane has just written (its own store, in program order), so the state array is only ever indexed by constants.
+template <int M>
+SC_HD void rm_path_trace_w(const Fe* C, int rounds, int d, const Fe* leaf, uint64_t index, const Fe* path, int depth, Fe* out, uint64_t T) {
+    SC_RP_UNROLLED
+    for (int j = 0; j < M; ++j) out[(uint64_t)j * T] = j < d ? rp_reduce(leaf[j]) : fe_zero();
+    for (int e = 0; e <= d; ++e) out[(uint64_t)(M + e) * T] = fe_zero();
+    // the sibling and bit columns first, the walk behind them: the walk then reads its siblings and bits from the trace itself, and
+    // the round loop keeps one pointer next to the state instead of three and the index
+    SC_RP_ROLLED
+    for (int lvl = 0; lvl < depth; ++lvl) {
+        const uint64_t t0 = (uint64_t)lvl * (rounds + 1);
+        for (int e = 0; e < d; ++e) rm_trace_fill(out + (uint64_t)(M + e) * T, t0 + 1, rounds + 1, rp_reduce(path[(uint64_t)lvl * d + e]));
+        rm_trace_fill(out + (uint64_t)(M + d) * T, t0 + 1, rounds + 1, Fe{(index >> lvl) & 1, 0});
+    }
+    Fe s[M];
+    SC_RP_ROLLED
+    for (int lvl = 0; lvl < depth; ++lvl) {
+        const uint64_t t0 = (uint64_t)lvl * (rounds + 1);
+        const unsigned bit = (unsigned)out[(uint64_t)(M + d) * T + t0 + 1].lo;
+        SC_RP_UNROLLED
+        for (int j = 0; j < M; ++j) {
+            const int e = rm_trace_element(j, d);
+            const Fe x = rm_trace_first(out[(uint64_t)e * T + t0], out[(uint64_t)(M + e) * T + t0 + 1], j, d, bit);
+            out[(uint64_t)j * T + t0 + 1] = x;
+            s[j] = to_mont(x);
+        }
+        SC_RP_ROLLED
+        for (int r = 0; r < rounds; ++r) {
+            rp_round_w<M>(C, r, s);
+            // a ROLLED store loop, the state rotating through s[0] like rp_sbox_w's: one running address instead of M column
+            // addresses kept across the round (16 VGPRs at M = 8, which the round does not have to spare)
+            Fe* q = out + t0 + 2 + r;
+            SC_RP_ROLLED
+            for (int j = 0; j < M; ++j) {
+                *q = from_mont(s[0]);
+                q += T;
+                rp_rotate<M, 1>(s);
+            }
+        }
+    }
+}
+
 #if defined(__HIPCC__)
 // The exchange on the device: every lane of the wave hands `mine` in and reads the M values of lanes base .. base + M - 1.
 // Shuffles (ds_bpermute through __shfl), not LDS: 4 M dwords per half round next to the 2 or 142 Montgomery products of the power,
@@ -162,6 +233,48 @@ __device__ __forceinline__ Fe rm_sponge_split(const Fe* __restrict__ C, int roun
         }
     }
     return s;
+}
+
+// One lane's share of the trace of a path (the layout above): the column of ITS state register r, and -- the item's own lanes, no
+// others -- the sibling column M + r where r < d and the bit column where r == d (d < M always: 2 d < rate < M).  The digest reached
+// stays with lanes 0 .. d - 1 of the item and reaches the lanes that start from it by a shuffle EVERY lane executes; a lane that is
+// not live runs along on register 0's constants, loads and stores nothing.
+template <int M>
+__device__ __forceinline__ void rm_path_trace_split(const Fe* __restrict__ C, int rounds, int d, const Fe* leaf, uint64_t index, const Fe* path, int depth,
+                                                    Fe* out, uint64_t T, int r, int base, bool live) {
+    Fe row[M];
+    SC_RP_UNROLLED
+    for (int j = 0; j < M; ++j) row[j] = C[r * M + j];
+    const int e = rm_trace_element(r, d);
+    const bool state_of_path = live && r < 2 * d, sibling_column = live && r < d, bit_column = live && r == d;
+    Fe* mine = out + (uint64_t)r * T;                 // the lane's state column
+    Fe* side = out + (uint64_t)(M + r) * T;           // its sibling or bit column (written only where r <= d)
+    Fe own = sibling_column ? rp_reduce(leaf[r]) : fe_zero();
+    if (live) mine[0] = own;
+    if (sibling_column || bit_column) side[0] = fe_zero();
+    SC_RP_ROLLED
+    for (int lvl = 0; lvl < depth; ++lvl) {
+        const unsigned bit = (unsigned)((index >> lvl) & 1);
+        const uint64_t t0 = (uint64_t)lvl * (rounds + 1);
+        const Fe sib = state_of_path ? rp_reduce(path[(uint64_t)lvl * d + e]) : fe_zero();
+        const Fe reached = rm_shfl(own, base + e);                                // every lane
+        const Fe x = rm_trace_first(reached, sib, r, d, bit);
+        if (live) mine[t0 + 1] = x;
+        if (sibling_column) rm_trace_fill(side, t0 + 1, rounds + 1, sib);
+        if (bit_column) rm_trace_fill(side, t0 + 1, rounds + 1, Fe{bit, 0});
+        Fe s = to_mont(x);
+        SC_RP_ROLLED
+        for (int rd = 0; rd < rounds; ++rd) {
+            SC_RP_ROLLED
+            for (int h = 0; h < 2; ++h) {
+                Fe pw[M];
+                rm_exchange<M>(rm_split_power(s, h != 0), base, pw);
+                s = rm_split_mix<M>(row, C[rm_split_constant(M, rd, h, r)], pw);
+            }
+            own = from_mont(s);
+            if (live) mine[t0 + 2 + rd] = own;
+        }
+    }
 }
 #endif
 

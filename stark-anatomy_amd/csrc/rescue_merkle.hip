@@ -1,5 +1,6 @@
 // rescue_merkle.hip -- Merkle trees whose hash is the Rescue-Prime sponge (csrc/rescue_merkle.cuh): build over the rows of a
-// coalesced matrix, all levels kept in HBM; root, openings, level copies; batched verification of authentication paths.
+// coalesced matrix, all levels kept in HBM; root, openings, level copies; batched verification of authentication paths, and the
+// traces of such walks for membership proofs.
 #include "core.h"
 #include "rescue_merkle.cuh"
 
@@ -142,6 +143,34 @@ rescue_tree_verify_split_kernel(const Fe* __restrict__ C, const VerifyArgs a) {
     if (L.live && L.r == 0) a.verdicts[L.node] = ((bad >> L.base) & ((1ull << M) - 1)) == 0;
 }
 
+// ---- the trace of a path: every state of an item's walk (depth permutations in sequence) inside one launch.  Item t's W = M + d + 1
+// columns of T rows lie one behind the other at out + W T t (rescue_merkle.cuh: the layout).
+struct TraceArgs {
+    const Fe* leaves;       // item-major: leaves[t * d + e]
+    const uint64_t* idx;
+    const Fe* paths;        // paths[((t * depth) + j) * d + e]
+    Fe* out;
+    uint64_t k, T;
+    int depth, d, rounds;
+};
+// wide: one lane per item (rm_path_trace_w)
+template <int M>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4)))
+rescue_path_trace_wide_kernel(const Fe* __restrict__ C, const TraceArgs a) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= a.k) return;
+    rm_path_trace_w<M>(C, a.rounds, a.d, a.leaves + t * a.d, a.idx[t], a.paths + t * a.depth * a.d, a.depth, a.out + (uint64_t)(M + a.d + 1) * a.T * t, a.T);
+}
+// split: one lane per register of an item's state (rm_path_trace_split), 64 / M items per wave
+template <int M>
+__global__ void __launch_bounds__(256)
+rescue_path_trace_split_kernel(const Fe* __restrict__ C, const TraceArgs a) {
+    const SplitLane<M> L(a.k);
+    const uint64_t index = L.live ? a.idx[L.node] : 0;
+    rm_path_trace_split<M>(C, a.rounds, a.d, a.leaves + L.node * a.d, index, a.paths + L.node * a.depth * a.d, a.depth,
+                           a.out + (uint64_t)(M + a.d + 1) * a.T * L.node, a.T, L.r, L.base, L.live);
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
 struct Shape {
     uint64_t m, rate, d, rounds;
@@ -201,6 +230,11 @@ template <int M>
 static void verify_enqueue(bool split, const Fe* C, const VerifyArgs& a, hipStream_t st) {
     if (split) hipLaunchKernelGGL((rescue_tree_verify_split_kernel<M>), dim3(split_grid(a.k, M)), dim3(256), 0, st, C, a);
     else hipLaunchKernelGGL((rescue_tree_verify_wide_kernel<M>), dim3(wide_grid(a.k)), dim3(256), 0, st, C, a);
+}
+template <int M>
+static void trace_enqueue(bool split, const Fe* C, const TraceArgs& a, hipStream_t st) {
+    if (split) hipLaunchKernelGGL((rescue_path_trace_split_kernel<M>), dim3(split_grid(a.k, M)), dim3(256), 0, st, C, a);
+    else hipLaunchKernelGGL((rescue_path_trace_wide_kernel<M>), dim3(wide_grid(a.k)), dim3(256), 0, st, C, a);
 }
 #define RM_DISPATCH(m, call, ...)                  \
     switch (m) {                               \
@@ -350,6 +384,62 @@ int sc_rescue_merkle_verify_batch(const void* roots, const uint64_t* indices, co
     RM_DISPATCH(m, verify_enqueue, split_wanted(k), C, a, st);
     HIPCHK(hipGetLastError());
     return download(verdicts_out, a.verdicts, k, st);
+}
+
+int sc_rescue_merkle_path_trace_dev(const void* leaves, const uint64_t* indices, const void* paths, uint64_t k, uint64_t depth, uint64_t digest_len,
+                                    uint64_t m, uint64_t rate, const void* params, uint64_t rounds, void* d_out, void* stream) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    const std::string what = "rescue merkle path trace: ";
+    const Shape s{m, rate, digest_len, rounds};
+    SCCHK(check_shape(what, s, params));
+    if (2 * digest_len >= rate) return fail(SC_ERR_BAD_ARG, what + "a node of one permutation expected: 2 * digest_len < rate");
+    if (depth == 0 || depth > 63) return fail(SC_ERR_BAD_ARG, what + "a depth of 1 .. 63 expected");
+    if (k && (!leaves || !indices || !paths || !d_out)) return fail(SC_ERR_BAD_ARG, what + "null argument");
+    // What depends on k alone comes before the scan of the indices: an absurd k is refused without a look at the arrays.
+    // One block of the call's own: [constants][leaves][paths][indices], every part a multiple of 16 bytes.
+    const uint64_t W = m + digest_len + 1, T = depth * (rounds + 1) + 1;                  // at most 12 registers, 1765 rows
+    const u128 leaf_b = (u128)k * digest_len * sizeof(Fe), path_b = leaf_b * depth, idx_b = ((u128)k * 8 + 15) & ~(u128)15;
+    const u128 in_b = (u128)MAX_CONSTANTS * sizeof(Fe) + leaf_b + path_b + idx_b, out_b = (u128)k * W * T * sizeof(Fe);
+    if (in_b >> 62 || out_b >> 62 || (u128)(uintptr_t)d_out + out_b > ((u128)1 << 64) || (k + 255) / 256 > 0x7FFFFFFFull || (k + 7) / 8 > 4 * 0x7FFFFFFFull)
+        return fail(SC_ERR_BAD_ARG, what + "the byte counts wrap");
+    for (uint64_t i = 0; i < k; ++i) if (indices[i] >> depth) return fail(SC_ERR_BAD_ARG, what + "cannot trace invalid index");
+    Fe host[MAX_CONSTANTS];
+    const uint64_t count = constants_to_mont(s, params, host);
+    if (!count) return fail(SC_ERR_BAD_ARG, what + "a constant is not below p");
+    if (k == 0) return SC_OK;
+    hipStream_t st = pick_stream(stream);
+    PoolTmpAsync block;
+    SCCHK(block.get((size_t)in_b));
+    char* p = (char*)block.p;
+    const Fe* C = (const Fe*)p;               p += sizeof host;
+    TraceArgs a;
+    a.leaves = (const Fe*)p;                  p += (size_t)leaf_b;
+    a.paths = (const Fe*)p;                   p += (size_t)path_b;
+    a.idx = (const uint64_t*)p;
+    a.out = (Fe*)d_out;
+    a.k = k; a.T = T; a.depth = (int)depth; a.d = (int)digest_len; a.rounds = (int)rounds;
+    if (!upload_small((void*)C, host, count * sizeof(Fe), st)) return fail(SC_ERR_HIP, what + "the constants could not be enqueued");
+    // The inputs are the caller's pageable memory.  Few of them travel as kernel arguments and nothing is waited for; otherwise they
+    // are copied and the copies -- nothing behind them -- are waited for before the call returns.
+    const bool small = upload_small((void*)a.leaves, leaves, (size_t)leaf_b, st) && upload_small((void*)a.paths, paths, (size_t)path_b, st) &&
+                       upload_small((void*)a.idx, indices, k * 8, st);
+    if (!small) {
+        (void)hipGetLastError();
+        SCCHK(upload((void*)a.leaves, leaves, (size_t)leaf_b, st));
+        SCCHK(upload((void*)a.paths, paths, (size_t)path_b, st));
+        SCCHK(upload((void*)a.idx, indices, k * 8, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    switch (m) {
+        case 4: trace_enqueue<4>(split_wanted(k), C, a, st); break;
+        case 5: trace_enqueue<5>(split_wanted(k), C, a, st); break;
+        case 6: trace_enqueue<6>(split_wanted(k), C, a, st); break;
+        case 7: trace_enqueue<7>(split_wanted(k), C, a, st); break;
+        default: trace_enqueue<8>(split_wanted(k), C, a, st); break;
+    }
+    HIPCHK(hipGetLastError());
+    return SC_OK;
 }
 
 uint64_t sc_rescue_merkle_leaves(const sc_rescue_tree_t* tree) { return tree ? tree->N : 0; }

@@ -243,6 +243,11 @@ class FastStark:
         variables = 1 + 2 * self.num_registers
         bounds = []
         for constraint in transition_constraints:
+            offered = getattr(constraint, "degree_bound", None)
+            if offered is not None:
+                # a constraint with public columns (multivariate.XColumnsConstraint) has no dictionary to read: it knows its bound
+                bounds.append(offered(trace_degree, self.num_registers))
+                continue
             monomial_degrees = [sum(exponents[:1]) + trace_degree * sum(exponents[1:variables]) for exponents in constraint.dictionary]
             bounds.append(max(monomial_degrees))
         return bounds
@@ -661,6 +666,19 @@ class FastStark:
         _sc._check(lib.sc_coset_evaluate_columns_dev(coefficients.ptr, m, count, _sc.fe_bytes(self.generator.value), _sc.fe_bytes(self.omega.value), order, values.ptr, None))
         return [DeviceCodeword(DeviceVector.wrap(values.ptr + 16 * order * c, order, values), self.field) for c in range(count)]
 
+    @staticmethod
+    def _with_public_columns(constraints, points):
+        """Constraints with public columns (multivariate.XColumnsConstraint) that all share ONE set of columns, as the value-domain AIR
+        takes them: their inner polynomials (small exponents, a dictionary each) over points extended by the columns' DevicePolynomials
+        -- every member's point by the same objects, so that a batch evaluates them once, like X.  The columns are then variables like
+        any other: all constraints of an order share one evaluation of the point and, in a batch, one AIR launch.  Any other list of
+        constraints, and its points, come back as they are."""
+        columns = getattr(constraints[0], "columns", None) if constraints else None
+        if columns is None or not points or any(getattr(a, "columns", None) is not columns for a in constraints):
+            return constraints, points
+        lifted = columns.device(points[0][0].field)
+        return [a.inner for a in constraints], [list(point) + lifted for point in points]
+
     def _transition_quotients_on_device(self, constraints, point, tz_dev, pending=None, batched=False):
         """fast_stark.py:107-113 -- `a.evaluate_symbolic(point)` divided by the transition zerofier -- without ever building the
         transition polynomial: on the coset g * <root'> (root' of the order code/ntt.py:155-157 shrinks to, taken from the degree
@@ -675,6 +693,7 @@ class FastStark:
         (evaluate_symbolic, then coset_divide_device), as does any shape the kernel does not take (sharded_stark.py does the same
         on slabs)."""
         field = self.field
+        constraints, (point,) = self._with_public_columns(list(constraints), [point])
         reference_way = lambda a: coset_divide_device(a.evaluate_symbolic(point), tz_dev, self.generator, self.omicron, self.omicron_domain_length)
         degrees = [q.degree() for q in point]
         dr = tz_dev.degree()
@@ -756,7 +775,7 @@ class FastStark:
         rows of one matrix.  What the batched calls do not serve goes through the per-member method, unchanged: a (member, constraint)
         whose interpolant is longer than bound - deg Z (a false witness), a constraint of a shape or bound the value domain does not
         take, and members whose points differ in length or structure; members of different degrees are batched among their likes."""
-        constraints, points = list(transition_constraints), [list(point) for point in points]
+        constraints, points = self._with_public_columns(list(transition_constraints), [list(point) for point in points])
         tz_dev = self._lift(transition_zerofier)
         in_runs = self.num_registers >= FastStark.COLUMN_BATCH_MIN          # (as `prove` decides it)
         one_member = lambda m, some: self._transition_quotients_on_device(some, points[m], tz_dev, pending, in_runs)

@@ -244,3 +244,106 @@ class MPolynomial:
         for i, c in enumerate(polynomial.coefficients):
             acc = acc + MPolynomial.constant(c) * (x ^ i)
         return acc
+
+
+class XColumns:
+    """The public columns of one AIR: polynomials in X that every constraint of the AIR shares (a selector, round constants per row).
+    Their degrees are the TRUE degrees; their values at a point are computed once per point for all constraints (Horner on
+    residues), and they are lifted to the device once."""
+
+    def __init__(self, polynomials):
+        self.polynomials = list(polynomials)
+        self.degrees = [q.degree() for q in self.polynomials]
+        self._coefficients = [[c.value for c in q.coefficients[:d + 1]] for q, d in zip(self.polynomials, self.degrees)]
+        self._device = None
+        self._at = (None, None)
+
+    def __len__(self):
+        return len(self.polynomials)
+
+    def device(self, field):
+        if self._device is None:
+            from ntt import DevicePolynomial
+            self._device = [DevicePolynomial.from_polynomial(q, field) for q in self.polynomials]
+        return self._device
+
+    def values(self, x, p):
+        """the residues of every column at the residue x (the last x is remembered: the constraints of an AIR ask one after the other)"""
+        if self._at[0] != (x, p):
+            out = []
+            for coefficients in self._coefficients:
+                acc = 0
+                for c in reversed(coefficients):
+                    acc = (acc * x + c) % p
+                out.append(acc)
+            self._at = ((x, p), out)
+        return self._at[1]
+
+
+class XColumnsConstraint(MPolynomial):
+    """A transition constraint whose per-row public values are COLUMNS, not powers of X: an inner MPolynomial over
+    [X, previous state (W), next state (W), column_0 .. column_(a-1)] with small exponents, and the a column polynomials in X
+    (an XColumns, shared by the constraints of one AIR).  Substituting the columns would give an ordinary AIR polynomial whose
+    X-exponents run into the thousands -- more than mpoly_eval_kernel, `value_domain_terms` and the combination kernel hold (255) --
+    so the substitution is never made: `evaluate_symbolic` extends the point by the columns and hands it to the inner polynomial
+    (the value-domain route, for host and device points alike), `evaluator()` extends the point by the columns' values.
+    `dictionary` is None and `value_domain_terms` declines, so whoever holds an unextended point takes the fall-back it has for a
+    constraint without a dictionary (the symbolic value, then a division; the host loop of verify_batch at the opened points).  The
+    device prover extends its points itself when all constraints share one XColumns (FastStark._with_public_columns) and hands the
+    inner polynomials to the value-domain AIR, where the columns are variables like any other: one evaluation of the point per
+    order and, in a batch, one AIR launch for all constraints and members.  FastStark.transition_degree_bounds asks `degree_bound`.
+    inner_evaluator: point -> residue, a structured form of the inner polynomial's value (optional; the same value)."""
+
+    def __init__(self, inner, columns, inner_evaluator=None):
+        self.dictionary = None
+        self.inner, self.columns, self._inner_evaluator = inner, columns, inner_evaluator
+
+    def _unsupported(self, *_):
+        raise TypeError("an XColumnsConstraint has no dictionary: arithmetic is done on its inner polynomial")
+
+    __add__ = __sub__ = __mul__ = __xor__ = _unsupported
+
+    def __neg__(self):
+        self._unsupported()
+
+    def is_zero(self):
+        return self.inner.is_zero()
+
+    def value_domain_terms(self, degrees):
+        return NotImplemented
+
+    def degree_bound(self, trace_degree, num_registers):
+        """the degree bound of the constraint once X (degree 1), the 2 * num_registers trace polynomials (trace_degree each) and the
+        columns (their true degrees) are substituted: the worst monomial of the inner polynomial decides, as in
+        FastStark.transition_degree_bounds.  A monomial with a column that is the zero polynomial vanishes."""
+        variables = 1 + 2 * num_registers
+        bound = -1
+        for exponents in self.inner.dictionary:
+            extra = exponents[variables:]
+            if any(e and self.columns.degrees[j] < 0 for j, e in enumerate(extra)):
+                continue
+            bound = max(bound, sum(exponents[:1]) + trace_degree * sum(exponents[1:variables]) + sum(e * self.columns.degrees[j] for j, e in enumerate(extra)))
+        return bound
+
+    def evaluate_symbolic(self, point):
+        if any(hasattr(q, "vec") for q in point):
+            field = next(q.field for q in point if hasattr(q, "vec"))
+            return self.inner.evaluate_symbolic(list(point) + self.columns.device(field))
+        return self.inner.evaluate_symbolic(list(point) + self.columns.polynomials)
+
+    def evaluator(self):
+        columns = self.columns
+        if self._inner_evaluator is not None:
+            structured = self._inner_evaluator
+
+            def run(point):
+                field = point[0].field
+                vals = [q.value for q in point]
+                return FieldElement(structured(vals + columns.values(vals[0], field.p), field.p) % field.p, field)
+            return run
+        inner = self.inner.evaluator()
+
+        def run(point):
+            field = point[0].field
+            return inner(list(point) + [FieldElement(v, field) for v in columns.values(point[0].value, field.p)])
+        return run

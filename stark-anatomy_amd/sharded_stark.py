@@ -373,6 +373,7 @@ class ShardedFastStark(FastStark):
     # -- prover (fast_stark.py:76-178) -------------------------------------------------------------------
     def prove(self, trace, transition_constraints, boundary, transition_zerofier, transition_zerofier_layer, proof_stream=None):
         """trace: the reference's list of rows, or a fast_stark.DeviceTrace (columns resident in HBM)"""
+        assert(all(type(getattr(a, "dictionary", None)) is dict for a in transition_constraints)), "the sharded prover takes constraints with a dictionary only (no public columns)"
         with self._on_stream():
             return self._prove(trace, transition_constraints, boundary, transition_zerofier, transition_zerofier_layer, proof_stream)
 

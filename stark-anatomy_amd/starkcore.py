@@ -62,6 +62,7 @@ SIGNATURES = {
     "sc_rescue_merkle_open_batch": (_int, [_vp, _vp, _u64, _vp]),
     "sc_rescue_merkle_level_copy_dev": (_int, [_vp, _u64, _vp, _vp]),
     "sc_rescue_merkle_verify_batch": (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _u64, _vp, _u64, _vp]),
+    "sc_rescue_merkle_path_trace_dev": (_int, [_vp, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _vp, _u64, _vp, _vp]),
     "sc_rescue_merkle_leaves": (_u64, [_vp]),
     "sc_rescue_merkle_free": (_int, [_vp]),
     "sc_ntt": (_int, [_vp, _vp, _u64, _vp, _int]),
