@@ -128,12 +128,15 @@ int emu_rm_verify(int m, const void* roots, const uint64_t* idx, const void* pat
 }
 
 #ifdef RESCUE_MERKLE_MAIN
-// Every width 3 .. 8 on heap buffers of exactly the size the layout promises (a sanitizer build reports any access past them):
+// Every width 3 .. 8 and the long digests on heap buffers of exactly the size the layout promises (a sanitizer build reports any access past them):
 // a strided matrix, both forms build the same tree, every leaf's path verifies in both forms and no longer does with one word changed.
 int main() {
     const int rounds = 2;
-    for (int m = 3; m <= RP_MAX_M; ++m) {
-        const int rate = m - 1, d = m > 4 ? 2 : 1;
+    // {m, d} at capacity 1: every width at d = 1 or 2, then the long digests (tests/rescue_merkle_cases.py LONG_SHAPES: node messages
+    // whose right child lies across two blocks, and d = rate)
+    const int shapes[][2] = {{3, 1}, {4, 1}, {5, 2}, {6, 2}, {7, 2}, {8, 2}, {8, 4}, {5, 3}, {7, 5}, {6, 4}, {8, 7}, {3, 2}};
+    for (const auto& shape : shapes) {
+        const int m = shape[0], rate = m - 1, d = shape[1];
         const uint64_t N = 8, ld = N + 3, width = rate + 1;
         const int depth = 3;
         std::vector<Fe> params(m * m + 2 * m * rounds);
@@ -143,7 +146,7 @@ int main() {
         std::vector<Fe> wide(d * (2 * N - 1)), split(wide.size());
         if (emu_rm_build(m, rows.data(), ld, width, N, d, rate, params.data(), rounds, wide.data(), 0)) return 1;
         if (emu_rm_build(m, rows.data(), ld, width, N, d, rate, params.data(), rounds, split.data(), 1)) return 1;
-        if (memcmp(wide.data(), split.data(), wide.size() * sizeof(Fe))) return printf("m = %d: the forms differ\n", m), 2;
+        if (memcmp(wide.data(), split.data(), wide.size() * sizeof(Fe))) return printf("m = %d d = %d: the forms differ\n", m, d), 2;
         std::vector<Fe> roots(N * d), paths(N * depth * d), items(N * width);
         std::vector<uint64_t> idx(N);
         for (uint64_t t = 0; t < N; ++t) {
@@ -157,12 +160,12 @@ int main() {
             std::vector<uint8_t> verdicts(N, 7);
             if (emu_rm_verify(m, roots.data(), idx.data(), paths.data(), items.data(), N, depth, width, d, rate, params.data(), rounds, verdicts.data(), form)) return 1;
             for (uint64_t t = 0; t < N; ++t)
-                if (verdicts[t] != 1) return printf("m = %d form %d: path %d does not verify\n", m, form, (int)t), 3;
+                if (verdicts[t] != 1) return printf("m = %d d = %d form %d: path %d does not verify\n", m, d, form, (int)t), 3;
             std::vector<Fe> bad = paths;
             bad[(3 * depth + 1) * d].lo ^= 1;
             emu_rm_verify(m, roots.data(), idx.data(), bad.data(), items.data(), N, depth, width, d, rate, params.data(), rounds, verdicts.data(), form);
             for (uint64_t t = 0; t < N; ++t)
-                if (verdicts[t] != (t != 3)) return printf("m = %d form %d: a changed path\n", m, form), 4;
+                if (verdicts[t] != (t != 3)) return printf("m = %d d = %d form %d: a changed path\n", m, d, form), 4;
             // depth 0: the leaf digest against the root
             std::vector<Fe> leaf_roots(N * d);
             for (uint64_t t = 0; t < N; ++t)
@@ -170,7 +173,7 @@ int main() {
             std::vector<uint64_t> zeros(N, 0);
             emu_rm_verify(m, leaf_roots.data(), zeros.data(), nullptr, items.data(), N, 0, width, d, rate, params.data(), rounds, verdicts.data(), form);
             for (uint64_t t = 0; t < N; ++t)
-                if (verdicts[t] != 1) return printf("m = %d form %d: depth 0\n", m, form), 5;
+                if (verdicts[t] != 1) return printf("m = %d d = %d form %d: depth 0\n", m, d, form), 5;
         }
     }
     printf("rescue merkle ok\n");
