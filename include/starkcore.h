@@ -62,7 +62,7 @@ int sc_stream(void** stream_out);
 int sc_stream_join(void* other_stream);
 /* tuning knobs for experiments (defaults are the measured optimum; -1 = choose by size where applicable): key in
  * {"max_tile_log","loge","max_col_log","min_tiles_log","single_pass_max_log","max_digit_log","direct_tw_max_log",
- *  "xcd_remap","fixed_shapes","merkle_big_nlev","wave_local","prio_balance","loge_cols","tw_on_load","prune","fast_fixups","fri_tail","fri_tail_stall","small_divisor_direct","verify_stage_kb","forest_four_lane_wgs","div_cols_chunk","div_cols_launch_log","tree_cols_launch_log","eval_chunk_log","eval_points_across_min","eval_across_min_products_log","rescue_tree_split_max_nodes"}.  Plans are re-derived on the next
+ *  "xcd_remap","fixed_shapes","merkle_big_nlev","wave_local","prio_balance","loge_cols","tw_on_load","prune","fast_fixups","fri_tail","fri_tail_stall","small_divisor_direct","verify_stage_kb","forest_four_lane_wgs","div_cols_chunk","div_cols_launch_log","tree_cols_launch_log","eval_chunk_log","eval_points_across_min","eval_across_min_products_log","rescue_tree_split_max_nodes","grind_window","grind_unrolled"}.  Plans are re-derived on the next
  * call; results never depend on the tuning ("fri_tail_stall" = k >= 0 is a test hook: the host withholds the challenge after round k of
  * the persistent tail kernel, whose wait then gives up after 2^13 polls; -1 = off; "small_divisor_direct" = 0: sc_coset_divide* transforms a
  * divisor of <= 8 coefficients like any other instead of evaluating it point by point; "verify_stage_kb" = the size of the staging buffer
@@ -80,7 +80,9 @@ int sc_stream_join(void* other_stream);
  * instead of the coefficients-across-lanes one, 32 by default, at least 1; "eval_across_min_products_log" = log2 of the modular products
  * (m * k * cols) a call must have for that to apply, 26 by default, 0 .. 64 -- smaller calls do not fill the device and always spread a chunk
  * over a workgroup; 0 with "eval_points_across_min" = 1 takes the points-across-lanes kernel everywhere, which is how the tests reach it; "rescue_tree_split_max_nodes" = a level of a Rescue-Prime Merkle tree, or a batch of paths of sc_rescue_merkle_verify_batch or sc_rescue_merkle_path_trace_dev, of at most
- * this many nodes runs one lane per state register instead of one lane per node, 0 = never, 2147483647 = always, -1 = the default, 65536: the largest level width of the measured sweep at which that form is the faster one by more than the spread of the repetitions at every state width measured, profiles/rescue_merkle; the path trace has no key of its own: at depth 20 that form is the faster one at every batch measured up to 65536, profiles/rescue_membership).  Two keys manage the device-memory pool instead (freed vectors and trees are kept
+ * this many nodes runs one lane per state register instead of one lane per node, 0 = never, 2147483647 = always, -1 = the default, 65536: the largest level width of the measured sweep at which that form is the faster one by more than the spread of the repetitions at every state width measured, profiles/rescue_merkle; the path trace has no key of its own: at depth 20 that form is the faster one at every batch measured up to 65536, profiles/rescue_membership; "grind_window" = the trials one launch of sc_grind / sc_grind_batch
+ * tests per seed, -1 (or anything below 1) = the default, 4194304, from the sweep in profiles/grinding; results do not depend on it; "grind_unrolled" = 1: the
+ * grinding kernel with rounds 1 .. 22 of the permutation fully unrolled instead of one loop over them, 0 = the default, an A/B knob).  Two keys manage the device-memory pool instead (freed vectors and trees are kept
  * on exact-size free lists, by default up to a quarter of the device's memory divided by the processes sharing the device;
  * environment STARKCORE_POOL_CAP_MB): "pool_cap_mb" = what the lists may keep from now on, "pool_trim" = hand everything on them
  * back to the device now (a caller whose own allocator -- torch's -- ran out of memory). */
@@ -592,6 +594,26 @@ int sc_rescue_merkle_path_trace_dev(const void* leaves, const uint64_t* indices,
 uint64_t sc_rescue_merkle_leaves(const sc_rescue_tree_t* tree);
 int sc_rescue_merkle_free(sc_rescue_tree_t* tree);
 
+/* ---- proof-of-work grinding on the transcript (grinding.py) ------------------------------------------------------
+ * pow_value(seed, nonce) = the little-endian u64 of SHAKE-256(seed (32 bytes) || nonce (8 bytes, little-endian)).digest(8): one
+ * Keccak-f[1600] per trial.  A nonce is accepted at `bits` iff pow_value >> (64 - bits) == 0.
+ * sc_grind:       the SMALLEST accepted nonce in [start, start + max_nonces) into *nonce_out and *found_out = 1; *found_out = 0 (and
+ *                 *nonce_out untouched) when the range holds none.  The search runs on the device in windows of "grind_window" trials,
+ *                 ascending, one lane per trial, and stops behind the first window with a hit (one more window may have been queued);
+ *                 the result does not depend on the window.  The call returns when the answer is on the host; meanwhile other
+ *                 threads may call the library (another search on another stream included).  The temporaries are the call's own: no
+ *                 shared scratch, no one-stream rule.  max_nonces == 0: SC_OK, *found_out = 0.
+ * sc_grind_batch: the same for `count` seeds (seeds: count * 32 bytes) over the same range, in shared launches: the members ride one
+ *                 grid, a member with a hit is left out of the launches that follow, and the call ends when every member has a hit
+ *                 or the range is exhausted.  nonces_out[m] is written only where found_out[m] = 1.  count == 0: SC_OK, nothing is
+ *                 touched.  At most 65535 seeds.
+ * sc_grind_host:  sc_grind on one host core (csrc/transcript.h's Keccak-f): the baseline of the measurement, no device needed.
+ * SC_ERR_BAD_ARG, before anything is enqueued: bits outside 1 .. 63, start + max_nonces above 2^64, a NULL pointer where one is needed. */
+int sc_grind(const uint8_t seed32[32], int bits, uint64_t start, uint64_t max_nonces, uint64_t* nonce_out, int* found_out, void* stream);
+int sc_grind_batch(const uint8_t* seeds, uint64_t count, int bits, uint64_t start, uint64_t max_nonces, uint64_t* nonces_out,
+                   uint8_t* found_out, void* stream);
+int sc_grind_host(const uint8_t seed32[32], int bits, uint64_t start, uint64_t max_nonces, uint64_t* nonce_out, int* found_out);
+
 /* ---- FRI split-and-fold : code/fri.py:85 ---------------------------------------------------- */
 /* out[i] = 2^-1 * ((1 + alpha/(offset*omega^i)) * in[i] + (1 - alpha/(offset*omega^i)) * in[N/2+i]), i < N/2 */
 int sc_fri_fold(const void* in, uint64_t N, const uint64_t alpha[2], const uint64_t offset[2], const uint64_t omega[2], void* out);
@@ -649,6 +671,17 @@ int sc_fri_prove_dev(const void* d_codeword, uint64_t N, const uint64_t offset[2
                      sc_vec_t** vecs_out, sc_merkle_t** trees_out, uint8_t* roots_out, uint64_t* alphas_out,
                      void* last_codeword_out, uint64_t* top_indices_out, uint64_t* extra_indices_out,
                      void* answers, uint64_t answers_bytes, void* stream);
+/* sc_fri_prove_dev for a Fri with grinding (Fri(..., grinding_bits), grinding.py): the same arguments, then grinding_bits (0 .. 63;
+ * 0 = sc_fri_prove_dev exactly) and nonce_out.  Between the seed over the transcript with the last codeword and the sampling of the
+ * indices the call finds the smallest nonce accepted at grinding_bits with that seed (sc_grind's search, on `stream`), writes it to
+ * *nonce_out, appends it to the transcript as the plain integer the prover pushes, and samples the indices from the hash of that
+ * transcript.  The caller pushes the nonce between the last codeword and the query phase's objects. */
+int sc_fri_prove_grind_dev(const void* d_codeword, uint64_t N, const uint64_t offset[2], const uint64_t omega[2], uint32_t rounds, uint32_t num_tests,
+                           const void* prior_data, const uint32_t* prior_lens, uint64_t prior_count,
+                           uint64_t extra_count, const sc_merkle_t* const* extra_trees, const void* const* extra_vecs, uint64_t extra_shift,
+                           sc_vec_t** vecs_out, sc_merkle_t** trees_out, uint8_t* roots_out, uint64_t* alphas_out,
+                           void* last_codeword_out, uint64_t* top_indices_out, uint64_t* extra_indices_out,
+                           void* answers, uint64_t answers_bytes, void* stream, int grinding_bits, uint64_t* nonce_out);
 /* pinned, device-visible host memory from a pool kept by the library (an allocation of megabytes costs hundreds of microseconds):
  * what sc_fri_prove_dev's query kernel writes a proof's openings to */
 /* diagnostics of the persistent tail kernel of the commit phase (csrc/fri_tail.cuh): out[0] = launches so far, out[1] = launches

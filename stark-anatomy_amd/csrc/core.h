@@ -136,6 +136,8 @@ struct Ctx {
     int eval_points_across_min = 32; // sc_poly_eval_points_dev: the number of points (of a call, of a last part-wave) from which the points-across-lanes form is taken ...
     int eval_across_min_products_log = 26;   // ... in calls of at least 2^this many modular products (0: in every call)
     int rescue_tree_split_max_nodes = -1;    // sc_rescue_merkle_*: a level (a batch of paths) of at most this many nodes runs one lane per state register; 0: never, INT32_MAX: always, -1: the measured default (csrc/rescue_merkle.hip SPLIT_MAX_NODES_DEFAULT)
+    int grind_window = -1;           // sc_grind*: trials per launch and member; -1: the measured default (csrc/grind.hip GRIND_WINDOW_DEFAULT)
+    int grind_unrolled = 0;          // sc_grind*: 1 = the kernel with rounds 1 .. 22 fully unrolled instead of one loop over them (A/B, csrc/grind.cuh)
     int div_cols_chunk = 0;          // columns that share one batch inversion in pointwise_div_cols_kernel; 0: chosen by shape (columns.hip div_cols_chunk_for)
     std::vector<hipStream_t> seen_streams;   // those streams, most recent last (at most SEEN_STREAMS; more: device-wide waits)
     DevBuf scratch[8];       // 0: ntt work, 1..3: poly temporaries, 4: misc small, 5: merkle staging, 6: uploaded operands, 7: degree / exactness flag
@@ -265,6 +267,11 @@ int host_pool_get(size_t bytes, void** out);
 int host_pool_put(void* p);
 bool host_pool_holds(const void* p, size_t bytes);
 int verify_stage_buffer(size_t bytes, uint8_t** out);   // the batched verifier's pinned staging buffer, grown to `bytes` (one per process; callers hold g_mu)
+
+// ---- grind.hip
+// sc_grind_batch for a caller that holds g_mu (and keeps it: sc_fri_prove_grind_dev searches in the middle of its own call)
+int grind_seeds_locked(const std::string& what, const void* seeds, uint64_t count, int bits, uint64_t start, uint64_t max_nonces, uint64_t* nonces_out,
+                       uint8_t* found_out, void* stream);
 
 // ---- polytree_geo.hip
 Fe canonical_root(int logn);

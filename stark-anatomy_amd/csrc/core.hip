@@ -1063,6 +1063,8 @@ int sc_set_tuning(const char* key, int value) {
     else if (k == "eval_points_across_min") g.eval_points_across_min = value < 1 ? 1 : value;                     // which of the two forms of the evaluation kernel a number of points takes ...
     else if (k == "eval_across_min_products_log") g.eval_across_min_products_log = value < 0 ? 0 : (value > 64 ? 64 : value);   // ... in calls of at least 2^value products
     else if (k == "rescue_tree_split_max_nodes") g.rescue_tree_split_max_nodes = value < -1 ? -1 : value;      // which form of the Rescue-Prime tree kernels a level takes (csrc/rescue_merkle.hip); -1 = the default
+    else if (k == "grind_window") g.grind_window = value < 1 ? -1 : value;                                    // trials per launch and member of sc_grind / sc_grind_batch (csrc/grind.hip); -1 = the default
+    else if (k == "grind_unrolled") g.grind_unrolled = value > 0 ? 1 : 0;                                     // A/B: the grinding kernel with its middle rounds fully unrolled (csrc/grind.cuh)
     else if (k == "verify_stage_kb") g.verify_stage_bytes = (size_t)(value < 16 ? 16 : value) << 10;           // (a chunk must hold one row of any depth)
     else if (k == "fri_tail_stall") g.fri_tail_stall = value;                               // tests only: see core.h
     else if (k == "pool_cap_mb") g_pool_cap = (size_t)(value < 0 ? 0 : value) << 20;       // what the free lists may keep from now on

@@ -797,13 +797,18 @@ static inline uint64_t fri_openings_of_codeword(uint32_t j, uint32_t rounds, uin
 // `answers`: [elements 16 B each, padded to 256 B][paths][indices u64]; a buffer of sc_host_alloc is written by the kernel
 // directly (no staging, no copy engine; the last workgroup flags completion in a pinned word the host polls), any other host
 // pointer is served through device scratch and two copies.
-int sc_fri_prove_dev(const void* d_codeword, uint64_t N, const uint64_t offset[2], const uint64_t omega[2], uint32_t rounds, uint32_t num_tests,
+//
+// grinding_bits > 0 (sc_fri_prove_grind_dev; Fri(grinding_bits), grinding.py): between the seed over the transcript with the last
+// codeword and the sampling, the smallest nonce accepted with that seed is searched on the call's stream (csrc/grind.hip), appended
+// to the transcript as the plain integer the prover pushes, and the indices are sampled from the hash of THAT transcript.
+static int fri_prove(const void* d_codeword, uint64_t N, const uint64_t offset[2], const uint64_t omega[2], uint32_t rounds, uint32_t num_tests,
                      const void* prior_data, const uint32_t* prior_lens, uint64_t prior_count,
                      uint64_t extra_count, const sc_merkle_t* const* extra_trees, const void* const* extra_vecs, uint64_t extra_shift,
                      sc_vec_t** vecs_out, sc_merkle_t** trees_out, uint8_t* roots_out, uint64_t* alphas_out,
                      void* last_codeword_out, uint64_t* top_indices_out, uint64_t* extra_indices_out,
-                     void* answers, uint64_t answers_bytes, void* stream) {
+                     void* answers, uint64_t answers_bytes, void* stream, int grinding_bits, uint64_t* nonce_out) {
     std::unique_lock<std::mutex> lk(g_mu);
+    if (grinding_bits < 0 || grinding_bits > 63 || (grinding_bits && !nonce_out)) return fail(SC_ERR_BAD_ARG, "fri prove: 0 .. 63 grinding bits and a place for the nonce expected");
     if (!last_codeword_out || !top_indices_out || !answers || (extra_count && (!extra_trees || !extra_vecs || !extra_indices_out)) || !num_tests)
         return fail(SC_ERR_BAD_ARG, "null argument");
     if (rounds < 1 || rounds > 60 || N < 2 || !is_pow2(N)) return fail(SC_ERR_NOT_POW2, "codeword length must be a power of two >= 2 that survives the folds");
@@ -855,12 +860,16 @@ int sc_fri_prove_dev(const void* d_codeword, uint64_t N, const uint64_t offset[2
     { const uint64_t plo = P_LO, phi = P_HI; memcpy(modulus, &plo, 8); memcpy(modulus + 8, &phi, 8); }
     pk.moduli = modulus; pk.nfields = 1; pk.modulus_bytes = 17;
     pk.bytes_at = &bytes_at;
+    ProofPickler pk_nonce = pk;    // a pickler's memo is that of ONE run: the transcript with the nonce is written by a second one
+    ProofPickler* writer = &pk;
     bool pickled = false, pickle_ok = false;
+    bool with_nonce = false;       // the transcript once more, with the nonce of the proof of work behind the last codeword
+    uint64_t nonce = 0;
     auto pickle_transcript = [&] {
         std::vector<uint8_t> ops;
         auto put32 = [&](uint32_t v) { for (int i = 0; i < 4; ++i) ops.push_back((uint8_t)(v >> (8 * i))); };
-        ops.reserve(16 + 72 * (prior_count + rounds) + 29 * n_last);
-        ops.push_back('L'); put32((uint32_t)(prior_count + rounds + 1));
+        ops.reserve(32 + 72 * (prior_count + rounds) + 29 * n_last);
+        ops.push_back('L'); put32((uint32_t)(prior_count + rounds + 1 + (with_nonce ? 1 : 0)));
         const uint8_t* p = (const uint8_t*)prior_data;
         for (uint64_t i = 0; i < prior_count; ++i) { ops.push_back('B'); put32(prior_lens[i]); ops.insert(ops.end(), p, p + prior_lens[i]); p += prior_lens[i]; }
         for (uint32_t r = 0; r < rounds; ++r) { ops.push_back('B'); put32(64); ops.insert(ops.end(), roots_out + 64 * r, roots_out + 64 * r + 64); }
@@ -871,8 +880,12 @@ int sc_fri_prove_dev(const void* d_codeword, uint64_t N, const uint64_t offset[2
             const uint8_t* v = (const uint8_t*)last_codeword_out + 16 * i;
             ops.insert(ops.end(), v, v + 16);
         }
+        if (with_nonce) {
+            ops.push_back('I');
+            for (int b = 0; b < 8; ++b) ops.push_back((uint8_t)(nonce >> (8 * b)));
+        }
         bytes_at.clear();
-        pickle_ok = pk.run(ops.data(), ops.size()) && bytes_at.size() == prior_count + rounds;
+        pickle_ok = writer->run(ops.data(), ops.size()) && bytes_at.size() == prior_count + rounds;
         pickled = true;
     };
     const std::function<void()> on_last = pickle_transcript;
@@ -905,6 +918,19 @@ int sc_fri_prove_dev(const void* d_codeword, uint64_t N, const uint64_t offset[2
     }
     uint8_t seed[32];
     shake256(pk.base, pk.used, seed, 32);
+    if (grinding_bits) {
+        // fri.py's prove with grinding: grind on the seed, push the nonce, take the seed of the indices over the stream with it
+        uint8_t found = 0;
+        rc = grind_seeds_locked("fri prove: ", seed, 1, grinding_bits, 0, ~0ull, &nonce, &found, stream);
+        if (rc != SC_OK) return undo(rc);
+        if (!found) return undo(fail(SC_ERR_UNSUPPORTED, "fri prove: no nonce below 2^64 - 1 is accepted"));
+        *nonce_out = nonce;
+        with_nonce = true;
+        writer = &pk_nonce;
+        pickle_transcript();
+        if (!pickle_ok) return undo(fail(SC_ERR_UNSUPPORTED, "transcript not described"));
+        shake256(pk_nonce.base, pk_nonce.used, seed, 32);
+    }
     stamp(3);
     if (!fri_sample_indices(seed, 32, N / 2, n_last, s, top_indices_out)) return undo(fail(SC_ERR_UNSUPPORTED, "cannot sample that many indices"));
     stamp(7);
@@ -1014,6 +1040,26 @@ int sc_fri_prove_dev(const void* d_codeword, uint64_t N, const uint64_t offset[2
                         "wait for the openings (%s) %.1f | total %.1f us\n", ilog2(N), us(0, 1), us(1, 2), us(2, 3), us(3, 7), us(7, 4), us(4, 5), direct ? "pinned" : "staged", us(5, 6), us(0, 6));
     }
     return SC_OK;
+}
+
+int sc_fri_prove_dev(const void* d_codeword, uint64_t N, const uint64_t offset[2], const uint64_t omega[2], uint32_t rounds, uint32_t num_tests,
+                     const void* prior_data, const uint32_t* prior_lens, uint64_t prior_count,
+                     uint64_t extra_count, const sc_merkle_t* const* extra_trees, const void* const* extra_vecs, uint64_t extra_shift,
+                     sc_vec_t** vecs_out, sc_merkle_t** trees_out, uint8_t* roots_out, uint64_t* alphas_out,
+                     void* last_codeword_out, uint64_t* top_indices_out, uint64_t* extra_indices_out,
+                     void* answers, uint64_t answers_bytes, void* stream) {
+    return fri_prove(d_codeword, N, offset, omega, rounds, num_tests, prior_data, prior_lens, prior_count, extra_count, extra_trees, extra_vecs, extra_shift,
+                     vecs_out, trees_out, roots_out, alphas_out, last_codeword_out, top_indices_out, extra_indices_out, answers, answers_bytes, stream, 0, nullptr);
+}
+int sc_fri_prove_grind_dev(const void* d_codeword, uint64_t N, const uint64_t offset[2], const uint64_t omega[2], uint32_t rounds, uint32_t num_tests,
+                           const void* prior_data, const uint32_t* prior_lens, uint64_t prior_count,
+                           uint64_t extra_count, const sc_merkle_t* const* extra_trees, const void* const* extra_vecs, uint64_t extra_shift,
+                           sc_vec_t** vecs_out, sc_merkle_t** trees_out, uint8_t* roots_out, uint64_t* alphas_out,
+                           void* last_codeword_out, uint64_t* top_indices_out, uint64_t* extra_indices_out,
+                           void* answers, uint64_t answers_bytes, void* stream, int grinding_bits, uint64_t* nonce_out) {
+    return fri_prove(d_codeword, N, offset, omega, rounds, num_tests, prior_data, prior_lens, prior_count, extra_count, extra_trees, extra_vecs, extra_shift,
+                     vecs_out, trees_out, roots_out, alphas_out, last_codeword_out, top_indices_out, extra_indices_out, answers, answers_bytes, stream,
+                     grinding_bits, nonce_out);
 }
 
 int sc_merkle_build(const void* elems, uint64_t N, uint8_t root_out[64], sc_merkle_t** tree) {

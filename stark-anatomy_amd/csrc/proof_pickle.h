@@ -25,6 +25,7 @@
 //   'B' u32 len  bytes       a bytes object
 //   'D' u32 depth  64*depth  a list of `depth` bytes objects of 64 bytes each (an authentication path, merkle.py:16-27)
 //   'T'                      a tuple of the 3 items that follow
+//   'I' u64 value            a plain int, 0 <= value < 2^64 (the nonce of a proof of work, grinding.py); pickle does not memoise ints
 //   'E' u32 field  u64 key  16 bytes   a FieldElement: `key` names the OBJECT (equal keys = the same object, pickled once and
 //                            referred to afterwards), value = two u64 limbs; `field` indexes the table of field moduli
 // and, inside a list only, two ops that stand for MANY of its items with their payload packed (what the provers push):
@@ -393,6 +394,11 @@ struct ProofPickler {
                 memcpy(&key, p, 8);
                 save_element(f, key, p + 8);
                 return p + 24;
+            }
+            case 'I': {
+                if (end - p < 8) return nullptr;
+                save_uint(p, 8);
+                return p + 8;
             }
             default: return nullptr;
         }

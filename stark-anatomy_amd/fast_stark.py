@@ -18,6 +18,7 @@ from ntt import *
 from ntt import _View, _shrink_order
 import starkcore as _sc
 import proof_objects as _po
+from grinding import MAX_BITS as MAX_GRINDING_BITS
 
 
 def draw_random_bytes(count, width=17):
@@ -123,15 +124,19 @@ def device_powers(base, count):
 
 
 class FastStark:
-    def __init__(self, field, expansion_factor, num_colinearity_checks, security_level, num_registers, num_cycles, transition_constraints_degree=2):
+    def __init__(self, field, expansion_factor, num_colinearity_checks, security_level, num_registers, num_cycles, transition_constraints_degree=2, grinding_bits=0):
+        """grinding_bits (not in the reference; 0 = the reference's protocol): bits of proof of work on the transcript before FRI's
+        query indices (grinding.py, Fri(grinding_bits)); each bit stands in for half a colinearity check in the security level"""
         assert(field.p.bit_length() >= security_level), "p must have at least as many bits as security level"
         assert(expansion_factor & (expansion_factor - 1) == 0), "expansion factor must be a power of 2"
         assert(expansion_factor >= 4), "expansion factor must be 4 or greater"
-        assert(num_colinearity_checks * 2 >= security_level), "number of colinearity checks must be at least half of security level"
+        assert(type(grinding_bits) is int and 0 <= grinding_bits <= MAX_GRINDING_BITS), "grinding_bits must be an integer of 0 .. %d" % MAX_GRINDING_BITS
+        assert(num_colinearity_checks * 2 + grinding_bits >= security_level), "number of colinearity checks must be at least half of security level" + (" less the grinding bits" if grinding_bits else "")
 
         # parameters (names are the reference's, fast_stark.py:14-35: callers read them)
         self.field, self.security_level = field, security_level
         self.expansion_factor, self.num_colinearity_checks = expansion_factor, num_colinearity_checks
+        self.grinding_bits = grinding_bits
         self.num_registers, self.original_trace_length = num_registers, num_cycles
         self.num_randomizers = 4 * num_colinearity_checks
         self.randomized_trace_length = num_cycles + self.num_randomizers
@@ -148,7 +153,7 @@ class FastStark:
         self._lifted = {}                 # id(host Polynomial) -> (the Polynomial, its DevicePolynomial): lifted once, not per proof
         self._zerofier_values = {}        # transform order -> (the transition zerofier, its values on that order's coset)
 
-        self.fri = Fri(self.generator, self.omega, self.fri_domain_length, expansion_factor, num_colinearity_checks)
+        self.fri = Fri(self.generator, self.omega, self.fri_domain_length, expansion_factor, num_colinearity_checks, grinding_bits)
 
     @property
     def omicron_domain(self):

@@ -17,6 +17,7 @@ from ntt import *
 from univariate import *
 import starkcore as _sc
 import proof_objects as _po
+import grinding as _grinding
 from starkcore import DeviceCodeword, DeviceVector, query_codewords
 
 
@@ -335,10 +336,15 @@ class BatchChecks:
 
 
 class Fri:
-    def __init__(self, offset, omega, initial_domain_length, expansion_factor, num_colinearity_tests):
+    def __init__(self, offset, omega, initial_domain_length, expansion_factor, num_colinearity_tests, grinding_bits=0):
+        """grinding_bits (not in the reference; 0 = the reference's protocol, byte for byte): a proof of work of that many bits on
+        the transcript between the last codeword and the query indices (grinding.py) -- the prover pushes the smallest accepted
+        nonce, the verifier checks it, and the indices are sampled from the transcript with it"""
         self.offset, self.omega, self.field = offset, omega, omega.field
         self.domain_length = initial_domain_length
         self.expansion_factor, self.num_colinearity_tests = expansion_factor, num_colinearity_tests
+        assert(type(grinding_bits) is int and 0 <= grinding_bits <= _grinding.MAX_BITS), "grinding_bits must be an integer of 0 .. %d" % _grinding.MAX_BITS
+        self.grinding_bits = grinding_bits
         assert(self.num_rounds() >= 1), "cannot do FRI with less than one round"
 
     def num_rounds(self):
@@ -492,9 +498,25 @@ class Fri:
         if top_level_indices is not None:
             return top_level_indices
         codewords = self.commit(codeword, proof_stream)
+        self.grind(proof_stream)
         top_level_indices = self.sample_indices(proof_stream.prover_fiat_shamir(), len(codewords[0]) // 2, len(codewords[-1]), self.num_colinearity_tests)
         self._query_all(codewords, top_level_indices, proof_stream, also_open)
         return top_level_indices
+
+    def grind(self, proof_stream):
+        """the proof of work between the commit phase and the query indices: the smallest nonce accepted with the seed over the
+        stream so far (searched on the GPU), pushed as a plain int; nothing at all at grinding_bits == 0"""
+        if self.grinding_bits:
+            nonce = _grinding.grind(proof_stream.prover_fiat_shamir(), self.grinding_bits)
+            assert(nonce is not None), "no nonce is accepted"
+            proof_stream.push(nonce)
+
+    def _check_grinding(self, proof_stream):
+        """the verifier's side: the seed over what it has read so far, then the nonce"""
+        if not self.grinding_bits:
+            return True
+        seed = proof_stream.verifier_fiat_shamir()
+        return _grinding.check(seed, proof_stream.pull(), self.grinding_bits)
 
     def _batchable(self, codewords):
         """what the forest path serves: the main field, at least two rounds (fri.py:122 reads codewords[1]), a power-of-two length,
@@ -568,6 +590,13 @@ class Fri:
             last = DeviceCodeword(None, self.field, elements=[FieldElement(v, self.field) for v in _sc.unpack(last_raw[16 * n_last * m:16 * n_last * (m + 1)], n_last)])
             holders.append([first] + middle + [last])
             stream.push(last._full)                              # the last codeword in the clear (fri.py:91)
+        if self.grinding_bits:
+            # the members' proofs of work in shared launches: every member's seed through its own stream, one search for all
+            nonces = _grinding.grind_batch([stream.prover_fiat_shamir() for stream in streams], self.grinding_bits)
+            assert(None not in nonces), "no nonce is accepted"
+            for stream, nonce in zip(streams, nonces):
+                stream.push(nonce)
+        for stream in streams:
             top.append(self.sample_indices(stream.prover_fiat_shamir(), N // 2, n_last, s))
         # query phase (fri.py:124-128): codeword j opens its round's a and b positions and the c positions of the round before
         per_round, requests = [], [[] for _ in range(rounds)]
@@ -657,13 +686,18 @@ class Fri:
         # proof_stream.objects.detach() (proof_objects.LazyProofObjects.detach) to hold plain objects instead.
         answers = _sc.HostBuffer(el_bytes + path_bytes + 8 * total)
         extra_trees = [cw.tree() for cw in extra]
+        nonce = ctypes.c_uint64(0)
         # no handle of the commit phase comes back (vecs_out = trees_out = NULL): nothing reads the folded codewords or their trees
         # once the openings are on the host, and the library hands their memory back before it returns
-        rc = _sc.lib().sc_fri_prove_dev(codeword.vec.ptr, N, _sc.fe_bytes(self.offset.value), _sc.fe_bytes(self.omega.value), rounds, s,
-                                        b"".join(prior), (ctypes.c_uint32 * max(1, k))(*map(len, prior)), k,
-                                        ne, (ctypes.c_void_p * max(1, ne))(*[t._h for t in extra_trees]),
-                                        (ctypes.c_void_p * max(1, ne))(*[cw.vec.ptr for cw in extra]), int(also_open.shift) if ne else 0,
-                                        None, None, roots, None, last_raw, top, quad, answers.ptr, answers.nbytes, None)
+        arguments = (codeword.vec.ptr, N, _sc.fe_bytes(self.offset.value), _sc.fe_bytes(self.omega.value), rounds, s,
+                     b"".join(prior), (ctypes.c_uint32 * max(1, k))(*map(len, prior)), k,
+                     ne, (ctypes.c_void_p * max(1, ne))(*[t._h for t in extra_trees]),
+                     (ctypes.c_void_p * max(1, ne))(*[cw.vec.ptr for cw in extra]), int(also_open.shift) if ne else 0,
+                     None, None, roots, None, last_raw, top, quad, answers.ptr, answers.nbytes, None)
+        if self.grinding_bits:                                   # the same call with the proof of work between the last codeword and the indices
+            rc = _sc.lib().sc_fri_prove_grind_dev(*arguments, self.grinding_bits, ctypes.byref(nonce))
+        else:
+            rc = _sc.lib().sc_fri_prove_dev(*arguments)
         if rc == _sc.SC_ERR_UNSUPPORTED:
             return None
         _sc._check(rc)
@@ -674,6 +708,8 @@ class Fri:
         holders = [_po.entries_of(codeword)] + [_po.DetachedEntries(self.field) for _ in range(rounds - 1)]
         lazy = _po.lazy_objects(proof_stream)
         lazy.add(_po.ElementList(holders[-1], last_raw.raw))
+        if self.grinding_bits:
+            lazy.append(int(nonce.value))                        # the nonce the library found and hashed into the seed of the indices
         # the query phase's objects (fri.py:104-113): described by the answers as they lie in the pinned buffer
         data = answers.array
         own = sum(counts[:rounds])                               # openings of the commit phase's codewords; the caller's come behind them
@@ -784,6 +820,8 @@ class Fri:
         if observed > allowed:
             return Fri._reject("last codeword does not correspond to polynomial of low enough degree", "observed degree: %s" % observed,
                                "but should be: %s" % allowed)
+        if not self._check_grinding(proof_stream):
+            return Fri._reject("proof of work fails")
         # the query phase: consistency of consecutive codewords at the sampled positions
         top_level_indices = self.sample_indices(proof_stream.verifier_fiat_shamir(), self.domain_length >> 1, self.domain_length >> (rounds - 1), s)
         omega, offset = self.omega, self.offset
@@ -838,6 +876,8 @@ class Fri:
         allowed = len(last_codeword) // self.expansion_factor - 1
         observed = self._last_codeword_degree(last_codeword, last_omega, last_offset)
         if observed > allowed:
+            return False
+        if not self._check_grinding(proof_stream):
             return False
         # the query phase: consistency of consecutive codewords at the sampled positions
         top_level_indices = self.sample_indices(proof_stream.verifier_fiat_shamir(), self.domain_length >> 1, self.domain_length >> (rounds - 1), s)

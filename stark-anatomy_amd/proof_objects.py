@@ -312,6 +312,9 @@ class _Real:
             elif type(o) is list and all(type(x) is bytes and len(x) == 64 for x in o):
                 out.append(b"D" + len(o).to_bytes(4, "little") + b"".join(o))
                 fresh = o + [o]
+            elif type(o) is int and 0 <= o < (1 << 64):    # (the nonce of a proof of work; pickle does not memoise ints)
+                out.append(b"I" + o.to_bytes(8, "little"))
+                fresh = []
             else:
                 # a FieldElement object (or anything holding one) may be THE SAME object as one a lazy segment describes by
                 # (codeword, index): only the pickler walking real objects gets that right

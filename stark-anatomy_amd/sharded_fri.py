@@ -254,6 +254,7 @@ class ShardedFri:
         (replicated): such rounds are bound by launch and hashing latency on any number of ranks, a collective per round only
         adds to it, and on the HIP engine the rest of the commit phase is then ONE library call (0: only when one row is left)."""
         self.fri, self.R, self.rank, self.world, self.device, self.group = fri, int(R), rank, world, device, group
+        assert(getattr(fri, "grinding_bits", 0) == 0), "the sharded provers do not grind: a Fri with grinding_bits > 0 proves on one GPU (Fri.prove / Fri.prove_batch)"
         assert R % world == 0 and fri.domain_length % R == 0
         self.Rw = self.R // world
         self.engine = engine if engine is not None else HipFriEngine(device)

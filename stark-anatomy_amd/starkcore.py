@@ -65,6 +65,9 @@ SIGNATURES = {
     "sc_rescue_merkle_path_trace_dev": (_int, [_vp, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _vp, _u64, _vp, _vp]),
     "sc_rescue_merkle_leaves": (_u64, [_vp]),
     "sc_rescue_merkle_free": (_int, [_vp]),
+    "sc_grind": (_int, [_vp, _int, _u64, _u64, ctypes.POINTER(_u64), ctypes.POINTER(_int), _vp]),
+    "sc_grind_batch": (_int, [_vp, _u64, _int, _u64, _u64, _vp, _vp, _vp]),
+    "sc_grind_host": (_int, [_vp, _int, _u64, _u64, ctypes.POINTER(_u64), ctypes.POINTER(_int)]),
     "sc_ntt": (_int, [_vp, _vp, _u64, _vp, _int]),
     "sc_ntt_dev": (_int, [_vp, _vp, _u64, _vp, _int, _vp]),
     "sc_ntt_columns_dev": (_int, [_vp, _vp, _u64, _u64, _vp, _int, _vp]),
@@ -134,6 +137,8 @@ SIGNATURES = {
     "sc_fri_commit_dev": (_int, [_vp, _u64, _vp, _vp, ctypes.c_uint32, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "sc_fri_prove_dev": (_int, [_vp, _u64, _vp, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp,
                                 _vp, _vp, _vp, _vp, _u64, _vp]),
+    "sc_fri_prove_grind_dev": (_int, [_vp, _u64, _vp, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp,
+                                      _vp, _vp, _vp, _vp, _u64, _vp, _int, ctypes.POINTER(_u64)]),
     "sc_fri_tail_stats": (_int, [_vp]),
     "sc_host_alloc": (_int, [_u64, _vp]),
     "sc_host_free": (_int, [_vp]),
