@@ -68,7 +68,7 @@ int sc_stream_join(void* other_stream);
  * divisor of <= 8 coefficients like any other instead of evaluating it point by point; "verify_stage_kb" = the size of the staging buffer
  * of sc_merkle_verify_batch / sc_fri_colinearity_batch, 65536 by default, at least 16; "forest_four_lane_wgs" = a launch of a Merkle forest of
  * at most this many workgroups runs its narrow levels four lanes per BLAKE2b compression, 0 = never; "fast_fixups" = 1: the eight-element
- * batch kernels correct by +-p on two limbs and an exact kernel redoes the tiles they flag, 0: exact arithmetic on every tile, 2: both
+ * batch kernel corrects by +-p on two limbs and repairs a dropped carry where it occurs, 0: exact arithmetic on every tile, 2: both
  * kernels on every tile (a test hook) -- see sc_ntt_columns_dev; "div_cols_chunk" = columns that share one batch inversion in
  * sc_pointwise_div_columns_later_dev / sc_coset_divide_columns_later_dev with a shared divisor, 0 = chosen by shape; "div_cols_launch_log" = log2 of the values
  * one set of launches of sc_coset_divide_columns_later_dev (and of sc_poly_divmod_columns_dev, sc_poly_mul_columns_dev, sc_poly_product_dev) takes, 26 by default and at most, at least 1: a test hook that makes the entry
@@ -107,7 +107,10 @@ int sc_field_selftest(int op, const void* a, const void* b, void* out, uint64_t 
  * thread i, so a wave is the 64 consecutive elements 64w .. 64w+63; the last wave may be partial.  The value of a flagged lane is undefined.
  * op 0: mont_mul2 -> a*b*2^-128, c*d*2^-128 (a, c < 2^128; b, d < p)      1: fe_addsub2 -> a+b, a-b, c+d, c-d
  *    2: fe_add_fast -> a+b   3: fe_sub_fast -> a-b   4: mont_mul_fast -> a*b*2^-128
- *    5: mont_mul2_fast -> as op 0   6: fe_addsub2_fast -> as op 1   7: fe_neg -> -a */
+ *    5: mont_mul2_fast -> as op 0   6: fe_addsub2_fast -> as op 1   7: fe_neg -> -a
+ * The self-repairing top-limb forms the batch kernel runs (always the canonical result, word[i] = 0; 8..15 are not codes):
+ *   16: fe_add_fix -> a+b   17: fe_sub_fix -> a-b   18: mont_mul_fix -> a*b*2^-128
+ *   19: mont_mul2_fix -> as op 0   20: fe_addsub2_fix -> as op 1 */
 int sc_field_selftest2(int op, const void* a, const void* b, const void* c, const void* d, void* out, uint32_t* word, uint64_t n);
 
 /* ---- device vectors ----------------------------------------------------------------------- */
@@ -139,12 +142,11 @@ int sc_ntt_dev(const void* d_in, void* d_out, uint64_t n, const uint64_t root[2]
  * while those of another finish, and the 2^12-element tiles of a batch run two workgroups per CU (a lone 2^20 transform is one
  * workgroup per CU with every CU in the same phase: 30 G elements/s; 16-64 columns: 43-44; 64 columns of 2^16: 45-49 against 3.4
  * one at a time -- DESIGN.md 3.1).
- * The time of a batched transform depends a little on its DATA: the eight-element kernels correct by +-p on the top and bottom 32-bit
- * limbs only and flag the tile when the carry between them would have mattered (probability 2^-32 per lane and operation on the
- * values a transform carries after its first twiddles); a flagged 2^12-element tile is transformed again by an exact kernel behind
- * the pass.  A column whose first butterflies see u - v = -1 -- a 0/1-valued trace whose halves differ, say -- redoes every tile of
- * its first pass.  sc_set_tuning("fast_fixups", 0) restores data-independent work (exact arithmetic on every tile); results are the
- * same bits either way. */
+ * The eight-element kernels correct by +-p on the top and bottom 32-bit limbs only; where the carry between them matters
+ * (probability 2^-32 per lane and operation on the values a transform carries after its first twiddles) the operation ripples it
+ * through the middle limbs on the spot, behind a wave-uniform branch, so every stored value is the canonical one and a pass is one
+ * launch.  sc_set_tuning("fast_fixups", 0) runs the exact four-limb corrections on every tile instead; results are the same bits
+ * either way. */
 int sc_ntt_columns_dev(const void* d_in, void* d_out, uint64_t n, uint64_t cols, const uint64_t root[2], int inverse, void* stream);
 
 /* ---- building blocks of the multi-GPU four-step NTT (no reference counterpart: the reference is single-process;

@@ -142,8 +142,7 @@ struct Ctx {
     std::vector<hipStream_t> seen_streams;   // those streams, most recent last (at most SEEN_STREAMS; more: device-wide waits)
     DevBuf scratch[8];       // 0: ntt work, 1..3: poly temporaries, 4: misc small, 5: merkle staging, 6: uploaded operands, 7: degree / exactness flag
     std::map<hipStream_t, DevBuf> ntt_work;   // the work buffer of a multi-pass transform, one per stream: transforms on DIFFERENT streams may be in flight together
-    std::map<hipStream_t, DevBuf> ntt_flags;  // tile flags of the eight-element pass kernels (core.hip pass_flags), one set per stream like the work buffer
-    int fast_fixups = 1;     // eight-element kernels: 1 = top-limb corrections + exact redo of flagged tiles, 0 = exact arithmetic on every tile, 2 = both on every tile (tests)
+    int fast_fixups = 1;     // eight-element kernels: 1 = self-repairing top-limb corrections, 0 = exact arithmetic on every tile, 2 = both kernels on every tile (tests)
     int num_cus = 256;
     int xcd_remap = 1;
     int fixed_shapes = 1;    // use the geometry-specialised kernel instantiations where one matches

@@ -76,10 +76,11 @@ __global__ void __launch_bounds__(1 << (GLR + GLC - LOGE)) ntt_pass_kernel_fixed
 // while the other loads or drains.  Global accesses are  s[base] + 32-bit lane offset  (Round::SPLIT_ADDR), so the launch needs every
 // per-thread offset below 4 GiB (fixed_offsets_fit).  No trace, no second destination (those launches take the generic kernel).
 //
-// This kernel runs the rounds with the top-limb field corrections (FixedRounds FAST, field.cuh): a correction by +-p touches limbs 0
-// and 3 only, and the carry that limbs 1 and 2 would have passed on -- there with probability 2^-32 per lane on transform data --
-// is collected in one SGPR mask.  A wave that ends with the mask set marks its workgroup in flags[grid index]; the launch is
-// followed by ntt_pass_redo8_kernel, which transforms the marked tiles again from the pass's input with the exact arithmetic.
+// This kernel runs the rounds with the self-repairing top-limb field corrections (FixedRounds ARITH_FIX, field_asm.cuh): a correction
+// by +-p touches limbs 0 and 3 only, and the carry that limbs 1 and 2 would have passed on -- there with probability 2^-32 per lane on
+// transform data -- is rippled through them where it occurs, behind a wave-uniform branch on the carry-out mask.  Every value that
+// reaches LDS or memory is the canonical one: no flags, no second launch, and the pass's input need not survive (in-place passes
+// run here too).
 template <int GLR, int GLC>
 __device__ __forceinline__ uint32_t fixed8_tile(const PassParams& P, uint32_t index, uint32_t ntiles, int xcd_remap) {
     uint32_t wg = index, colbits = 0;
@@ -90,7 +91,7 @@ __device__ __forceinline__ uint32_t fixed8_tile(const PassParams& P, uint32_t in
 }
 template <int GLR, int GLC>
 __global__ void __launch_bounds__(1 << (GLR + GLC - 3)) __attribute__((amdgpu_waves_per_eu(4)))
-ntt_pass_kernel_fixed8(const PassParams P, uint32_t ntiles, int xcd_remap, int wave_local, uint32_t* flags) {
+ntt_pass_kernel_fixed8(const PassParams P, uint32_t ntiles, int xcd_remap, int wave_local) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     Fe* lds = reinterpret_cast<Fe*>(smem_raw);
     const uint32_t tile = fixed8_tile<GLR, GLC>(P, blockIdx.x, ntiles, xcd_remap);
@@ -98,30 +99,22 @@ ntt_pass_kernel_fixed8(const PassParams P, uint32_t ntiles, int xcd_remap, int w
     auto stamp = [](int) {};
     auto sync = [] { __syncthreads(); };
     auto wsync = [] { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); };
-    rare_t rare = 0;
-    FixedRounds<3, GLR, GLC, 0, false, true>::run(P, tile, threadIdx.x, lds, tw, sync, wsync, stamp, wave_local != 0, rare);
-    // wave-uniform; the lanes of a flagged wave all store the same word to the same place (idempotent, no atomics)
-    if (rare_any(rare)) Round<3, 3, GLR, GLC>::store_word_at(flags + blockIdx.x, 0u, 1u);
+    rare_t none = 0;
+    FixedRounds<3, GLR, GLC, 0, false, ARITH_FIX>::run(P, tile, threadIdx.x, lds, tw, sync, wsync, stamp, wave_local != 0, none);
 }
 
-// The exact rounds (today's arithmetic) on the tiles the fast kernel marked, or on every tile (`all`: an in-place pass, whose input
-// the fast kernel would have overwritten, the first pass of an LDE, sc_set_tuning("fast_fixups", 0 / 2)).  Same grid as the pass, one
-// tile per workgroup: an unmarked workgroup reads its flag and leaves.  (A resident grid of two workgroups per CU striding over the
-// flags keeps the loop's state live across the rounds: 117 VGPRs and 97 SGPRs spilled, the all-tiles launch at 0.57 of today's speed.)
-// Leaves its flag zero.
+// The same tiles with the exact four-limb corrections: the first pass of an LDE (coset scaling and pruned stages sit under per-lane
+// tests, fast_pass_ok) and sc_set_tuning("fast_fixups", 0); with "fast_fixups" = 2 it runs after the kernel above on every tile.
 template <int GLR, int GLC>
 __global__ void __launch_bounds__(1 << (GLR + GLC - 3)) __attribute__((amdgpu_waves_per_eu(4)))
-ntt_pass_redo8_kernel(const PassParams P, uint32_t ntiles, int xcd_remap, int wave_local, uint32_t* flags, int all) {
+ntt_pass_kernel_exact8(const PassParams P, uint32_t ntiles, int xcd_remap, int wave_local) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    if (!all && flags[blockIdx.x] == 0) return;               // the same word for every thread: cleared only behind the barrier below
     Fe* lds = reinterpret_cast<Fe*>(smem_raw);
     Fe* tw = lds + (1u << (GLR + GLC));
     auto stamp = [](int) {};
     auto sync = [] { __syncthreads(); };
     auto wsync = [] { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); };
     FixedRounds<3, GLR, GLC, 0, false>::run(P, fixed8_tile<GLR, GLC>(P, blockIdx.x, ntiles, xcd_remap), threadIdx.x, lds, tw, sync, wsync, stamp, wave_local != 0);
-    if (!all) __syncthreads();                                 // every thread has read the flag
-    if (threadIdx.x == 0) flags[blockIdx.x] = 0;
 }
 
 __global__ void __launch_bounds__(256) pow_table_kernel(Fe* out, uint64_t count, Fe base_m, uint64_t step, Fe scale_m) {
@@ -367,6 +360,12 @@ __global__ void __launch_bounds__(256) field_selftest2_kernel(int op, const Fe* 
         case 4: r0 = mont_mul_fast(x, y, rare); flags = selftest_word<SC_ASM_MUL != 0>(rare); break;
         case 5: mont_mul2_fast(x, y, z, w, r0, r1, rare); flags = selftest_word<SC_ASM_MUL != 0>(rare); break;
         case 6: fe_addsub2_fast(x, y, z, w, r0, r1, r2, r3, rare); flags = selftest_word<SC_ASM_ADDSUB != 0>(rare); break;
+        // the self-repairing forms (codes 16..20; 8..15 stay unknown): no flag, word = 0
+        case 16: r0 = fe_add_fix(x, y); break;
+        case 17: r0 = fe_sub_fix(x, y); break;
+        case 18: r0 = mont_mul_fix(x, y); break;
+        case 19: mont_mul2_fix(x, y, z, w, r0, r1); break;
+        case 20: fe_addsub2_fix(x, y, z, w, r0, r1, r2, r3); break;
         default: r0 = fe_neg(x); break;
     }
     out[i] = r0; out[n + i] = r1; out[2 * n + i] = r2; out[3 * n + i] = r3;
@@ -680,18 +679,6 @@ int plan_batched_direct(NttPlanDesc& d, BatchKind kind, int loglen, int logbatch
     return SC_OK;
 }
 
-// the tile flags of the eight-element kernels on stream st: one word per workgroup of the grid, all zero between launches
-int pass_flags(hipStream_t st, uint32_t nwg, uint32_t** out) {
-    DevBuf& b = g.ntt_flags[st];
-    const void* before = b.p;
-    const size_t had = b.bytes;
-    void* p;
-    SCCHK(grow_buffer(b, (size_t)nwg * sizeof(uint32_t), &p));
-    if (p != before || b.bytes != had) HIPCHK(hipMemsetAsync(p, 0, b.bytes, st));
-    *out = (uint32_t*)p;
-    return SC_OK;
-}
-
 template <int LOGE>
 int launch_pass(const NttPassDesc& pd, hipStream_t st) {
     int remap = (g.xcd_remap && pd.ntiles >= 16 && (pd.ntiles & 7u) == 0) ? 1 : 0;
@@ -715,19 +702,16 @@ int launch_pass(const NttPassDesc& pd, hipStream_t st) {
     if constexpr (LOGE == 3) {
         if (k.kind == PK_FIXED8) {
             const int lr = pd.p.logR, lc = pd.p.logC;
-            // fast kernel, then the exact one on the tiles it marked -- from the pass's input, so only where the pass is not in
-            // place (both passes of a two-pass plan: in -> work -> out); an in-place pass (the middle one of three), the first pass
-            // of an LDE (coset scaling, pruned stages: fast_pass_ok) and fast_fixups = 0 take the exact kernel on every tile;
-            // fast_fixups = 2 (tests) runs both on every tile
+            // one launch of the self-repairing kernel, in place or not; the first pass of an LDE (coset scaling, pruned stages:
+            // fast_pass_ok) and fast_fixups = 0 take the exact kernel instead; fast_fixups = 2 (tests) runs both, the exact one last
+            // and over the first one's output -- except in place, where the input is gone after the first
             const uint32_t nwg = pd.ntiles * pd.cols;
-            const bool fast = g.fast_fixups != 0 && fast_pass_ok(pd.p) && !pass_in_place(pd);
-            const int all = (!fast || g.fast_fixups == 2) ? 1 : 0;
-            uint32_t* flags;
-            SCCHK(pass_flags(st, nwg, &flags));
+            const bool fast = g.fast_fixups != 0 && fast_pass_ok(pd.p);
+            const bool exact = !fast || (g.fast_fixups == 2 && !pass_in_place(pd));
 #define SC_FIXED8(LR, LC)                                                                                                                                   \
             if (lr == LR && lc == LC) {                                                                                                                     \
-                if (fast) hipLaunchKernelGGL((ntt_pass_kernel_fixed8<LR, LC>), dim3(nwg), dim3(pd.threads), pd.lds_bytes, st, pd.p, pd.ntiles, remap, g.wave_local, flags); \
-                hipLaunchKernelGGL((ntt_pass_redo8_kernel<LR, LC>), dim3(nwg), dim3(pd.threads), pd.lds_bytes, st, pd.p, pd.ntiles, remap, g.wave_local, flags, all); \
+                if (fast) hipLaunchKernelGGL((ntt_pass_kernel_fixed8<LR, LC>), dim3(nwg), dim3(pd.threads), pd.lds_bytes, st, pd.p, pd.ntiles, remap, g.wave_local); \
+                if (exact) hipLaunchKernelGGL((ntt_pass_kernel_exact8<LR, LC>), dim3(nwg), dim3(pd.threads), pd.lds_bytes, st, pd.p, pd.ntiles, remap, g.wave_local); \
                 return SC_OK;                                                                                                                               \
             }
             SC_FIXED8_SHAPES(SC_FIXED8)
@@ -983,8 +967,6 @@ int sc_shutdown(void) {
     for (auto& b : g.scratch) { if (b.p) hipFree(b.p); b = DevBuf{}; }
     for (auto& kv : g.ntt_work) if (kv.second.p) hipFree(kv.second.p);
     g.ntt_work.clear();
-    for (auto& kv : g.ntt_flags) if (kv.second.p) hipFree(kv.second.p);
-    g.ntt_flags.clear();
     if (g.later_words) hipFree(g.later_words);     // (no check is in flight after the device-wide wait above; re-allocated on the next)
     g.later_words = nullptr;
     if (g.stream) hipStreamDestroy(g.stream);
@@ -1340,7 +1322,7 @@ int sc_field_selftest(int op, const void* a, const void* b, void* out, uint64_t 
 int sc_field_selftest2(int op, const void* a, const void* b, const void* c, const void* d, void* out, uint32_t* word, uint64_t n) {
     std::lock_guard<std::mutex> lk(g_mu);
     SCCHK(ensure_init());
-    if (op < 0 || op > 7) return fail(SC_ERR_BAD_ARG, "unknown field self-test op");
+    if (op < 0 || (op > 7 && op < 16) || op > 20) return fail(SC_ERR_BAD_ARG, "unknown field self-test op");
     if (!n) return SC_OK;
     if (!a || !b || !c || !d || !out || !word) return fail(SC_ERR_BAD_ARG, "null argument");
     void *din, *dout, *dword;

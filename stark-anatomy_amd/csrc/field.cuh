@@ -181,6 +181,71 @@ SC_HD Fe mont_mul_fast_c(Fe a, Fe b, rare_t& rare) {
     return fe_fixup_fast_c((uint64_t)r, (uint64_t)(r >> 64), neg, rare);
 }
 
+// ---- self-repairing top-limb forms (the eight-element pass kernel).  The same first steps as the fast forms; where
+// limb 0 wraps, the carry (borrow) it would have dropped is passed through limbs 1 to 3 on the spot, so the result is always the
+// canonical one and there is no flag.  Limb for limb what field_asm.cuh does (there the repair sits behind a wave-uniform branch).
+SC_HD Fe fe_fixup_fix_c(uint64_t lo, uint64_t hi, bool neg) {
+    const uint32_t d0 = (uint32_t)lo, d1 = (uint32_t)(lo >> 32), d2 = (uint32_t)hi, d3 = (uint32_t)(hi >> 32);
+    const uint32_t o0 = d0 + (neg ? 1u : 0u);
+    uint32_t o1 = d1, o2 = d2, o3 = neg ? d3 + P_TOP32 : d3;
+    if (neg && o0 == 0) {                                       // limb 0 wrapped: ripple its carry
+        o1 += 1u;
+        const uint32_t c1 = o1 == 0;
+        o2 += c1;
+        const uint32_t c2 = c1 && o2 == 0;
+        o3 += c2;
+    }
+    return Fe{((uint64_t)o1 << 32) | o0, ((uint64_t)o3 << 32) | o2};
+}
+SC_HD Fe fe_sub_fix_c(Fe a, Fe b) {
+    const uint64_t lo = a.lo - b.lo;
+    const uint64_t b0 = a.lo < b.lo;
+    const uint64_t hi = a.hi - b.hi;
+    const bool neg = (a.hi < b.hi) || (hi < b0);
+    return fe_fixup_fix_c(lo, hi - b0, neg);
+}
+SC_HD Fe fe_add_fix_c(Fe a, Fe b) {
+    const uint64_t lo = a.lo + b.lo;
+    const uint64_t c0 = lo < a.lo;
+    const uint64_t hi = a.hi + b.hi;
+    const uint64_t hi2 = hi + c0;
+    const bool ca = (hi < a.hi) || (hi2 < hi);
+    const uint32_t r0 = (uint32_t)lo, r1 = (uint32_t)(lo >> 32), r2 = (uint32_t)hi2, r3 = (uint32_t)(hi2 >> 32);
+    const bool sel = ca || r3 >= P_TOP32;
+    uint32_t o0 = r0 - (sel ? 1u : 0u), o1 = r1, o2 = r2, o3 = sel ? r3 - P_TOP32 : r3;
+    if (sel && r0 == 0) {                                       // limb 0 borrowed: ripple the borrow
+        const uint32_t b1 = o1 == 0;
+        o1 -= 1u;
+        const uint32_t b2 = b1 && o2 == 0;
+        o2 -= b1;
+        const uint32_t b3 = b2 && o3 == 0;
+        o3 -= b2;
+        // a borrow out of the top without a carry into bit 128: the top limb decided r >= p for r = p - 1; the result is r itself
+        if (b3 && !ca) { o0 = 0; o1 = 0; o2 = 0; o3 = P_TOP32; }
+    }
+    return Fe{((uint64_t)o1 << 32) | o0, ((uint64_t)o3 << 32) | o2};
+}
+SC_HD Fe mont_mul_fix_c(Fe a, Fe b) {
+    u128 p00 = (u128)a.lo * b.lo, p01 = (u128)a.lo * b.hi, p10 = (u128)a.hi * b.lo, p11 = (u128)a.hi * b.hi;
+    const uint64_t t0 = (uint64_t)p00;
+    u128 mid = (p00 >> 64) + (uint64_t)p01 + (uint64_t)p10;
+    const uint64_t t1 = (uint64_t)mid;
+    u128 top = (mid >> 64) + (p01 >> 64) + (p10 >> 64) + p11;
+    const uint32_t w0 = (uint32_t)t0, w1 = (uint32_t)(t0 >> 32), w2 = (uint32_t)t1, w3 = (uint32_t)(t1 >> 32);
+    const uint64_t PH = P_TOP32;
+    const uint64_t s0 = (uint64_t)w0 * PH;
+    const uint32_t m3 = w3 - (uint32_t)s0;
+    const uint64_t delta = w3 < (uint32_t)s0;
+    const uint64_t s1 = (uint64_t)w1 * PH + (s0 >> 32);
+    const uint64_t s2 = (uint64_t)w2 * PH + (s1 >> 32);
+    const uint64_t s3 = (uint64_t)m3 * PH + (s2 >> 32);
+    const u128 q = (u128)(uint32_t)s1 | ((u128)(uint32_t)s2 << 32) | ((u128)s3 << 64);
+    const u128 d = top - q;
+    const bool neg = top < q || d < delta;
+    const u128 r = d - delta;
+    return fe_fixup_fix_c((uint64_t)r, (uint64_t)(r >> 64), neg);
+}
+
 SC_HD Fe to_mont(Fe a) { return mont_mul(a, Fe{R2_LO, R2_HI}); }
 SC_HD Fe from_mont(Fe a) { return mont_mul(a, fe_one()); }
 // plain modular product of two canonical values (two Montgomery steps)
@@ -342,6 +407,44 @@ SC_HD void fe_addsub2_fast(Fe u0, Fe v0, Fe u1, Fe v1, Fe& s0, Fe& d0, Fe& s1, F
 #else
     s0 = fe_add_fast(u0, v0, rare); d0 = fe_sub_fast(u0, v0, rare);
     s1 = fe_add_fast(u1, v1, rare); d1 = fe_sub_fast(u1, v1, rare);
+#endif
+}
+// the self-repairing top-limb forms (see fe_fixup_fix_c): same dispatch, no flag, always the canonical result
+SC_HD Fe fe_add_fix(Fe a, Fe b) {
+#if defined(__HIP_DEVICE_COMPILE__) && SC_ASM_ADDSUB
+    return fe_add_fix_asm(a, b);
+#else
+    return fe_add_fix_c(a, b);
+#endif
+}
+SC_HD Fe fe_sub_fix(Fe a, Fe b) {
+#if defined(__HIP_DEVICE_COMPILE__) && SC_ASM_ADDSUB
+    return fe_sub_fix_asm(a, b);
+#else
+    return fe_sub_fix_c(a, b);
+#endif
+}
+SC_HD Fe mont_mul_fix(Fe a, Fe b) {
+#if defined(__HIP_DEVICE_COMPILE__) && SC_ASM_MUL
+    return mont_mul_fix_asm(a, b);
+#else
+    return mont_mul_fix_c(a, b);
+#endif
+}
+SC_HD void mont_mul2_fix(Fe a0, Fe b0, Fe a1, Fe b1, Fe& r0, Fe& r1) {
+#if defined(__HIP_DEVICE_COMPILE__) && SC_ASM_MUL && SC_MUL2
+    mont_mul2_fix_asm(a0, b0, a1, b1, r0, r1);
+#else
+    r0 = mont_mul_fix(a0, b0);
+    r1 = mont_mul_fix(a1, b1);
+#endif
+}
+SC_HD void fe_addsub2_fix(Fe u0, Fe v0, Fe u1, Fe v1, Fe& s0, Fe& d0, Fe& s1, Fe& d1) {
+#if defined(__HIP_DEVICE_COMPILE__) && SC_ASM_ADDSUB && SC_MUL2
+    fe_addsub2_fix_asm(u0, v0, u1, v1, s0, d0, s1, d1);
+#else
+    s0 = fe_add_fix(u0, v0); d0 = fe_sub_fix(u0, v0);
+    s1 = fe_add_fix(u1, v1); d1 = fe_sub_fix(u1, v1);
 #endif
 }
 

@@ -127,7 +127,50 @@ __device__ __forceinline__ Fe a_fixup_fast(uint32_t d0, uint32_t d1, uint32_t d2
     return Fe{((uint64_t)d1 << 32) | o0, ((uint64_t)o3 << 32) | d2};
 }
 
-template <bool FAST>
+// ---- self-repairing top-limb forms.  The same hot path as the fast forms, but where those OR the carry-out (borrow-out) mask of
+// limb 0 into a flag and leave a wrong value behind, these finish the job on the spot: the mask still sits in its SGPR pair and
+// limbs 1 to 3 are still in registers, so the dropped carry is rippled through them by three v_addc_co_u32 with a zero addend (all
+// lanes run them; an unflagged lane adds 0).  The repair sits behind a wave-uniform test of the mask on the SALU, inside the asm
+// statement: hipcc takes the SGPR outputs of asm for divergent values and would turn a C++ `if` into VALU compares and EXEC
+// juggling.  On transform data a wave takes the repair about once in 2^26 operations.  The compiler pads no hazards inside a
+// statement, so the block carries its own wait states (SC_HAZ_NOP) between a VALU that writes an SGPR pair and the one that reads it.
+// The labels are numeric local ones, so a statement inlines any number of times.
+//
+// carry ripple: o1 += c (mask operand `c`), o2 += carry, o3 += carry; t = scratch SGPR pair
+#define SC_FIX_CARRY(o1, o2, o3, c)                                                \
+    SC_HAZ_NOP "v_addc_co_u32_e64 %[" o1 "], %[t], %[" o1 "], 0, %[" c "]\n\t"      \
+    SC_HAZ_NOP "v_addc_co_u32_e64 %[" o2 "], %[t], %[" o2 "], 0, %[t]\n\t"          \
+    SC_HAZ_NOP "v_addc_co_u32_e64 %[" o3 "], %[t], %[" o3 "], 0, %[t]\n\t"
+// borrow ripple of a sum: o1 -= b, o2 -= borrow, o3 -= borrow; a borrow out of the top in a lane whose sum did not carry into bit
+// 128 (mask `ca`) means the top limb took r = p - 1 for r >= p: there the result is r itself, [0, 0, 0, PH3] (`r3` still holds PH3)
+#define SC_FIX_BORROW(o0, o1, o2, o3, r3, b, ca)                                   \
+    SC_HAZ_NOP "v_subb_co_u32_e64 %[" o1 "], %[t], %[" o1 "], 0, %[" b "]\n\t"      \
+    SC_HAZ_NOP "v_subb_co_u32_e64 %[" o2 "], %[t], %[" o2 "], 0, %[t]\n\t"          \
+    SC_HAZ_NOP "v_subb_co_u32_e64 %[" o3 "], %[t], %[" o3 "], 0, %[t]\n\t"          \
+    "s_andn2_b64 %[t], %[t], %[" ca "]\n\t"                                        \
+    SC_HAZ_NOP "v_cndmask_b32_e64 %[" o0 "], %[" o0 "], 0, %[t]\n\t"               \
+    "v_cndmask_b32_e64 %[" o1 "], %[" o1 "], 0, %[t]\n\t"                          \
+    "v_cndmask_b32_e64 %[" o2 "], %[" o2 "], 0, %[t]\n\t"                          \
+    "v_cndmask_b32_e64 %[" o3 "], %[" o3 "], %[" r3 "], %[t]\n\t"
+
+// the difference tail (a_fixup_fast), repaired in place
+__device__ __forceinline__ Fe a_fixup_fix(uint32_t d0, uint32_t d1, uint32_t d2, uint32_t d3, smask_t bw) {
+    smask_t c, t;
+    const uint32_t d3p = d3 + PH3;
+    uint32_t o0 = a_addc(d0, 0u, bw, c);
+    uint32_t o3 = a_cnd(d3, d3p, bw);
+    asm("s_cmp_eq_u64 %[c], 0\n\t"
+        "s_cbranch_scc1 1f\n\t"
+        SC_FIX_CARRY("o1", "o2", "o3", "c")
+        "1:"
+        : [o1] "+v"(d1), [o2] "+v"(d2), [o3] "+v"(o3), [t] "=&s"(t)
+        : [c] "s"(c)
+        : "scc");
+    return Fe{((uint64_t)d1 << 32) | o0, ((uint64_t)o3 << 32) | d2};
+}
+
+// MODE: 0 = exact four-limb correction, 1 = top-limb correction + flag (FAST), 2 = top-limb correction, repaired in place
+template <int MODE>
 __device__ __forceinline__ Fe mont_mul_core(Fe a, Fe b, smask_t& rare) {
     const uint32_t a0 = lo32(a.lo), a1 = hi32(a.lo), a2 = lo32(a.hi), a3 = hi32(a.hi);
     const uint32_t b0 = lo32(b.lo), b1 = hi32(b.lo), b2 = lo32(b.hi), b3 = hi32(b.hi);
@@ -182,7 +225,8 @@ __device__ __forceinline__ Fe mont_mul_core(Fe a, Fe b, smask_t& rare) {
     uint32_t r1 = a_subb(t5, lo32(s2), bw, bw);
     uint32_t r2 = a_subb(t6, lo32(s3), bw, bw);
     uint32_t r3 = a_subb(t7, hi32(s3), bw, bw);
-    if constexpr (FAST) return a_fixup_fast(r0, r1, r2, r3, bw, rare);
+    if constexpr (MODE == 1) return a_fixup_fast(r0, r1, r2, r3, bw, rare);
+    if constexpr (MODE == 2) return a_fixup_fix(r0, r1, r2, r3, bw);
     uint32_t ph = a_cnd(0u, PH3, bw);
     uint32_t o0 = a_addc(r0, 0u, bw, c);
     uint32_t o1 = a_addc(r1, 0u, c, c);
@@ -192,9 +236,13 @@ __device__ __forceinline__ Fe mont_mul_core(Fe a, Fe b, smask_t& rare) {
 }
 __device__ __forceinline__ Fe mont_mul_asm(Fe a, Fe b) {
     smask_t none = 0;
-    return mont_mul_core<false>(a, b, none);
+    return mont_mul_core<0>(a, b, none);
 }
-__device__ __forceinline__ Fe mont_mul_fast_asm(Fe a, Fe b, smask_t& rare) { return mont_mul_core<true>(a, b, rare); }
+__device__ __forceinline__ Fe mont_mul_fast_asm(Fe a, Fe b, smask_t& rare) { return mont_mul_core<1>(a, b, rare); }
+__device__ __forceinline__ Fe mont_mul_fix_asm(Fe a, Fe b) {
+    smask_t none = 0;
+    return mont_mul_core<2>(a, b, none);
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Two independent Montgomery products, hand-interleaved (A, B, A, B, ...) so that every carry / borrow consumer sits at least two
@@ -241,7 +289,9 @@ struct MulState {       // registers of one product in flight
 // FAST: the top-limb correction (field.cuh, fe_fixup_fast_c) instead of the four-limb one: limb 0 takes the borrow as its carry-in,
 // limb 3 gets PH3 by a plain add and a select, limbs 1 and 2 stay, and limb 0's carry-out -- the carry they would have passed on --
 // is ORed into `rare`.  46 four-cycle instructions and one plain add per product instead of 49.
-template <bool FAST>
+// MODE as in mont_mul_core.  2: the two carry-out masks are ORed on the SALU (which sets SCC) and tested once; the repair block
+// ripples each product's own mask.
+template <int MODE>
 __device__ __forceinline__ void mont_mul2_core(Fe xa, Fe wa, Fe xb, Fe wb, Fe& ra, Fe& rb, smask_t& rare) {
     MulState A, B;
     A.a0 = lo32(xa.lo); A.a1 = hi32(xa.lo); A.a2 = lo32(xa.hi); A.a3 = hi32(xa.hi);
@@ -303,7 +353,25 @@ __device__ __forceinline__ void mont_mul2_core(Fe xa, Fe wa, Fe xb, Fe wb, Fe& r
     SC_BOTH(SC_V_SUBB(M.r3, M.bw, M.t7, hi32(M.s3), M.bw);)
     SC_V_NOP0();
     // ---- negative -> add p back
-    if constexpr (FAST) {
+    if constexpr (MODE == 2) {
+        A.ph = A.r3 + PHc;
+        B.ph = B.r3 + PHc;
+        SC_BOTH(SC_V_ADDC(M.o0, M.cx, M.r0, zero32, M.bw);)
+        SC_BOTH(SC_V_CND(M.o3, M.r3, M.ph, M.bw);)
+        smask_t t;
+        asm volatile("s_or_b64 %[t], %[ca], %[cb]\n\t"
+                     "s_cbranch_scc0 1f\n\t"
+                     SC_FIX_CARRY("a1", "a2", "a3", "ca")
+                     SC_FIX_CARRY("b1", "b2", "b3", "cb")
+                     "1:"
+                     : [a1] "+v"(A.r1), [a2] "+v"(A.r2), [a3] "+v"(A.o3), [b1] "+v"(B.r1), [b2] "+v"(B.r2), [b3] "+v"(B.o3), [t] "=&s"(t)
+                     : [ca] "s"(A.cx), [cb] "s"(B.cx)
+                     : "scc");
+        ra = Fe{((uint64_t)A.r1 << 32) | A.o0, ((uint64_t)A.o3 << 32) | A.r2};
+        rb = Fe{((uint64_t)B.r1 << 32) | B.o0, ((uint64_t)B.o3 << 32) | B.r2};
+        return;
+    }
+    if constexpr (MODE == 1) {
         A.ph = A.r3 + PHc;
         B.ph = B.r3 + PHc;
         SC_BOTH(SC_V_ADDC(M.o0, M.cx, M.r0, zero32, M.bw);)
@@ -328,10 +396,14 @@ __device__ __forceinline__ void mont_mul2_core(Fe xa, Fe wa, Fe xb, Fe wb, Fe& r
 }
 __device__ __forceinline__ void mont_mul2_asm(Fe xa, Fe wa, Fe xb, Fe wb, Fe& ra, Fe& rb) {
     smask_t none = 0;
-    mont_mul2_core<false>(xa, wa, xb, wb, ra, rb, none);
+    mont_mul2_core<0>(xa, wa, xb, wb, ra, rb, none);
 }
 __device__ __forceinline__ void mont_mul2_fast_asm(Fe xa, Fe wa, Fe xb, Fe wb, Fe& ra, Fe& rb, smask_t& rare) {
-    mont_mul2_core<true>(xa, wa, xb, wb, ra, rb, rare);
+    mont_mul2_core<1>(xa, wa, xb, wb, ra, rb, rare);
+}
+__device__ __forceinline__ void mont_mul2_fix_asm(Fe xa, Fe wa, Fe xb, Fe wb, Fe& ra, Fe& rb) {
+    smask_t none = 0;
+    mont_mul2_core<2>(xa, wa, xb, wb, ra, rb, none);
 }
 
 // The sums and differences of TWO butterflies (u0 +- v0, u1 +- v1): four independent carry chains issued round-robin, so every
@@ -457,6 +529,82 @@ __device__ __forceinline__ void fe_addsub2_fast_asm(Fe ua, Fe va, Fe ub, Fe vb, 
     rare_or(rare, B.ce);
     rare_or(rare, A.cb);
     rare_or(rare, B.cb);
+    sa = Fe{((uint64_t)A.r1 << 32) | A.s0, ((uint64_t)A.s3 << 32) | A.r2};
+    da = Fe{((uint64_t)A.d1 << 32) | A.e0, ((uint64_t)A.e3 << 32) | A.d2};
+    sb = Fe{((uint64_t)B.r1 << 32) | B.s0, ((uint64_t)B.s3 << 32) | B.r2};
+    db = Fe{((uint64_t)B.d1 << 32) | B.e0, ((uint64_t)B.e3 << 32) | B.d2};
+}
+
+// ---- the self-repairing twins of fe_sub_fast_asm / fe_add_fast_asm / fe_addsub2_fast_asm (SC_FIX_CARRY / SC_FIX_BORROW above)
+__device__ __forceinline__ Fe fe_sub_fix_asm(Fe a, Fe b) {
+    smask_t bw;
+    uint32_t d0 = a_sub_co(lo32(a.lo), lo32(b.lo), bw);
+    uint32_t d1 = a_subb(hi32(a.lo), hi32(b.lo), bw, bw);
+    uint32_t d2 = a_subb(lo32(a.hi), lo32(b.hi), bw, bw);
+    uint32_t d3 = a_subb(hi32(a.hi), hi32(b.hi), bw, bw);
+    return a_fixup_fix(d0, d1, d2, d3, bw);
+}
+
+__device__ __forceinline__ Fe fe_add_fix_asm(Fe a, Fe b) {
+    smask_t ca, cb, bo, t;
+    uint32_t r0 = a_add_co(lo32(a.lo), lo32(b.lo), ca);
+    uint32_t r1 = a_addc(hi32(a.lo), hi32(b.lo), ca, ca);
+    uint32_t r2 = a_addc(lo32(a.hi), lo32(b.hi), ca, ca);
+    uint32_t r3 = a_addc(hi32(a.hi), hi32(b.hi), ca, ca);
+    uint32_t t3 = a_sub_co(r3, PH3, cb);
+    const smask_t sel = ca | ~cb;
+    uint32_t o0 = a_subb(r0, 0u, sel, bo);
+    uint32_t o3 = a_cnd(r3, t3, sel);
+    asm("s_cmp_eq_u64 %[bo], 0\n\t"
+        "s_cbranch_scc1 1f\n\t"
+        SC_FIX_BORROW("o0", "o1", "o2", "o3", "r3", "bo", "ca")
+        "1:"
+        : [o0] "+v"(o0), [o1] "+v"(r1), [o2] "+v"(r2), [o3] "+v"(o3), [t] "=&s"(t)
+        : [r3] "v"(r3), [bo] "s"(bo), [ca] "s"(ca)
+        : "scc");
+    return Fe{((uint64_t)r1 << 32) | o0, ((uint64_t)o3 << 32) | r2};
+}
+
+// four masks (two carry-outs of the differences, two borrow-outs of the sums) ORed on the SALU, one test; the repair block then
+// applies every member's own mask
+__device__ __forceinline__ void fe_addsub2_fix_asm(Fe ua, Fe va, Fe ub, Fe vb, Fe& sa, Fe& da, Fe& sb, Fe& db) {
+    AddSubState A, B;
+    A.u0 = lo32(ua.lo); A.u1 = hi32(ua.lo); A.u2 = lo32(ua.hi); A.u3 = hi32(ua.hi);
+    A.v0 = lo32(va.lo); A.v1 = hi32(va.lo); A.v2 = lo32(va.hi); A.v3 = hi32(va.hi);
+    B.u0 = lo32(ub.lo); B.u1 = hi32(ub.lo); B.u2 = lo32(ub.hi); B.u3 = hi32(ub.hi);
+    B.v0 = lo32(vb.lo); B.v1 = hi32(vb.lo); B.v2 = lo32(vb.hi); B.v3 = hi32(vb.hi);
+    const uint32_t zero32 = 0, PHc = PH3;
+#define SC_BOTH(STEP) { AddSubState& M = A; STEP } { AddSubState& M = B; STEP }
+    SC_BOTH(SC_V_ADDCO(M.r0, M.ca, M.u0, M.v0); SC_V_SUBCO(M.d0, M.bd, M.u0, M.v0);)
+    SC_BOTH(SC_V_ADDC(M.r1, M.ca, M.u1, M.v1, M.ca); SC_V_SUBB(M.d1, M.bd, M.u1, M.v1, M.bd);)
+    SC_BOTH(SC_V_ADDC(M.r2, M.ca, M.u2, M.v2, M.ca); SC_V_SUBB(M.d2, M.bd, M.u2, M.v2, M.bd);)
+    SC_BOTH(SC_V_ADDC(M.r3, M.ca, M.u3, M.v3, M.ca); SC_V_SUBB(M.d3, M.bd, M.u3, M.v3, M.bd);)
+    SC_BOTH(SC_V_SUBCO(M.t3, M.cb, M.r3, PHc);)
+    A.ph = A.d3 + PHc;
+    B.ph = B.d3 + PHc;
+    SC_BOTH(SC_V_ADDC(M.e0, M.ce, M.d0, zero32, M.bd);)
+    SC_BOTH(SC_V_CND(M.e3, M.d3, M.ph, M.bd);)
+    A.sel = A.ca | ~A.cb;
+    B.sel = B.ca | ~B.cb;
+    SC_BOTH(SC_V_SUBB(M.s0, M.cb, M.r0, zero32, M.sel);)
+    SC_BOTH(SC_V_CND(M.s3, M.r3, M.t3, M.sel);)
+#undef SC_BOTH
+    smask_t t;
+    asm volatile("s_or_b64 %[t], %[cea], %[ceb]\n\t"
+                 "s_or_b64 %[t], %[t], %[boa]\n\t"
+                 "s_or_b64 %[t], %[t], %[bob]\n\t"
+                 "s_cbranch_scc0 1f\n\t"
+                 SC_FIX_CARRY("da1", "da2", "da3", "cea")
+                 SC_FIX_CARRY("db1", "db2", "db3", "ceb")
+                 SC_FIX_BORROW("sa0", "sa1", "sa2", "sa3", "ra3", "boa", "caa")
+                 SC_FIX_BORROW("sb0", "sb1", "sb2", "sb3", "rb3", "bob", "cab")
+                 "1:"
+                 : [da1] "+v"(A.d1), [da2] "+v"(A.d2), [da3] "+v"(A.e3), [db1] "+v"(B.d1), [db2] "+v"(B.d2), [db3] "+v"(B.e3),
+                   [sa0] "+v"(A.s0), [sa1] "+v"(A.r1), [sa2] "+v"(A.r2), [sa3] "+v"(A.s3),
+                   [sb0] "+v"(B.s0), [sb1] "+v"(B.r1), [sb2] "+v"(B.r2), [sb3] "+v"(B.s3), [t] "=&s"(t)
+                 : [ra3] "v"(A.r3), [rb3] "v"(B.r3), [cea] "s"(A.ce), [ceb] "s"(B.ce), [boa] "s"(A.cb), [bob] "s"(B.cb),
+                   [caa] "s"(A.ca), [cab] "s"(B.ca)
+                 : "scc");
     sa = Fe{((uint64_t)A.r1 << 32) | A.s0, ((uint64_t)A.s3 << 32) | A.r2};
     da = Fe{((uint64_t)A.d1 << 32) | A.e0, ((uint64_t)A.e3 << 32) | A.d2};
     sb = Fe{((uint64_t)B.r1 << 32) | B.s0, ((uint64_t)B.s3 << 32) | B.r2};

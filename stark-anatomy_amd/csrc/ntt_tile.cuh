@@ -148,6 +148,11 @@ SC_HD Fe pow_table_entry(Fe base_m, uint64_t i, uint64_t step, Fe scale_m) {
     return mont_mul(mont_pow(base_m, i * step), scale_m);   // (x~ * s~) R^-1 = (x s)~
 }
 
+// arithmetic of a round's sums, differences and products (template parameter FAST of Round's members, ntt_round and FixedRounds;
+// an int, so that `false` / `true` still name the first two): exact four-limb corrections, top-limb corrections with a flag
+// accumulator, self-repairing top-limb corrections
+enum : int { ARITH_EXACT = 0, ARITH_FAST = 1, ARITH_FIX = 2 };
+
 // One round of one workgroup's tile, for thread `tid`: S radix-2 DIF stages on row bits [sh, sh+S), in three steps the
 // kernel can place separately (the geometry-specialised kernel issues the first round's global loads before it stages the
 // tile twiddles, so both latencies overlap): round_gather -> round_butterflies -> round_scatter.
@@ -238,13 +243,7 @@ struct Round {
     SC_HD static void store_at(Fe* base, uint32_t lane_bytes, Fe v) {
         *reinterpret_cast<gfe*>(reinterpret_cast<gchar*>(sgpr_pin(reinterpret_cast<uint64_t>(base))) + vgpr_pin(lane_bytes)) = v;
     }
-    // a 32-bit word in the same s[base] + v_offset form (the tile flag of the FAST kernels)
-    SC_HD static void store_word_at(uint32_t* base, uint32_t lane_bytes, uint32_t v) {
-        typedef __attribute__((address_space(1))) uint32_t gword;
-        *reinterpret_cast<gword*>(reinterpret_cast<gchar*>(sgpr_pin(reinterpret_cast<uint64_t>(base))) + vgpr_pin(lane_bytes)) = v;
-    }
 #else
-    static void store_word_at(uint32_t* base, uint32_t lane_bytes, uint32_t v) { *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(base) + lane_bytes) = v; }
     static Fe load_at(const Fe* base, uint32_t lane_bytes) { return *reinterpret_cast<const Fe*>(reinterpret_cast<const char*>(base) + lane_bytes); }
     static void store_at(Fe* base, uint32_t lane_bytes, Fe v) { *reinterpret_cast<Fe*>(reinterpret_cast<char*>(base) + lane_bytes) = v; }
 #endif
@@ -296,12 +295,13 @@ struct Round {
         }
     }
     // first round: the multiplications that belong to the load (coset scaling, twiddle-on-load)
-    // FAST (here, in butterflies and in scatter_global): the sums, differences and products of the data go through the top-limb
-    // correction forms of field.cuh and OR their flags into *rare; the caller redoes the tile with FAST = false where it is set.
-    template <bool FAST = false>
+    // FAST = ARITH_FAST (here, in butterflies and in scatter_global): the sums, differences and products of the data go through the
+    // top-limb correction forms of field.cuh and OR their flags into *rare; the caller redoes the tile with the exact forms where it
+    // is set.  ARITH_FIX: through the self-repairing top-limb forms -- always the canonical value, *rare is not touched.
+    template <int FAST = ARITH_EXACT>
     SC_HD void finish_global(const PassParams& P, int sh, Fe* x, const Fe* tin, rare_t* rare = nullptr) const {
         // (not with FAST, see fast_pass_ok: the zero-padding test is per lane)
-        if (!FAST && P.coset_enable) {
+        if (FAST == ARITH_EXACT && P.coset_enable) {
 #pragma unroll
             for (int i = 0; i < E; ++i) {
                 const uint64_t j = in_index(P, i, sh);
@@ -314,12 +314,14 @@ struct Round {
             if (E & 1) x[E - 1] = mul1<FAST>(x[E - 1], tin[E - 1], rare);
         }
     }
-    template <bool FAST> SC_HD static Fe mul1(Fe a, Fe b, rare_t* rare) {
-        if constexpr (FAST) return mont_mul_fast(a, b, *rare);
+    template <int FAST> SC_HD static Fe mul1(Fe a, Fe b, rare_t* rare) {
+        if constexpr (FAST == ARITH_FAST) return mont_mul_fast(a, b, *rare);
+        else if constexpr (FAST == ARITH_FIX) return mont_mul_fix(a, b);
         else return mont_mul(a, b);
     }
-    template <bool FAST> SC_HD static void mul2(Fe a0, Fe b0, Fe a1, Fe b1, Fe& r0, Fe& r1, rare_t* rare) {
-        if constexpr (FAST) mont_mul2_fast(a0, b0, a1, b1, r0, r1, *rare);
+    template <int FAST> SC_HD static void mul2(Fe a0, Fe b0, Fe a1, Fe b1, Fe& r0, Fe& r1, rare_t* rare) {
+        if constexpr (FAST == ARITH_FAST) mont_mul2_fast(a0, b0, a1, b1, r0, r1, *rare);
+        else if constexpr (FAST == ARITH_FIX) mont_mul2_fix(a0, b0, a1, b1, r0, r1);
         else mont_mul2(a0, b0, a1, b1, r0, r1);
     }
     SC_HD void gather_lds(int sh, Fe* x, const Fe* lds) const {
@@ -329,7 +331,7 @@ struct Round {
     // S radix-2 DIF stages on the field bits, highest bit first; tw[e << tw_shift] = w_R^e (LDS copy: shift 0).
     // prune_log > 0: stages whose index from the top (0-based) is below it are the degenerate ones of a zero-padded input.
     // last_hint: 1 / 0 when the caller knows whether this is the last round (sh == 0), -1 = look at sh.
-    template <bool FAST = false>
+    template <int FAST = ARITH_EXACT>
     SC_HD void butterflies(int sh, Fe* x, const Fe* tw, int tw_shift, int prune_log = 0, int last_hint = -1, int prio = 0, rare_t* rare = nullptr) const {
         const bool last = last_hint < 0 ? (sh == 0) : (last_hint != 0);
         set_prio(prio, 3);
@@ -338,7 +340,7 @@ struct Round {
             const int bit = S - 1 - q;          // field bit
             const int b = sh + bit;             // row bit
             const int tau = logR - 1 - b;       // twiddle exponent scale: w_R^(2^tau * (r mod 2^b)); also the stage index from the top
-            if (!FAST && tau < prune_log) {
+            if (FAST == ARITH_EXACT && tau < prune_log) {
                 // v = 0 everywhere: (u, 0) -> (u, u * w).  Before this stage row r is non-zero iff (r mod 2^(b+1)) < R >> prune_log.
                 const uint32_t nz = 1u << (logR - prune_log);
 #pragma unroll
@@ -375,13 +377,17 @@ struct Round {
                 if (bf + 1 < E / 2) {
                     const int j0 = (((bf + 1) >> bit) << (bit + 1)) | ((bf + 1) & ((1 << bit) - 1));
                     const int j1 = j0 | (1 << bit);
-                    if constexpr (FAST) fe_addsub2_fast(x[i0], x[i1], x[j0], x[j1], x[i0], dd[bf], x[j0], dd[bf + 1], *rare);
+                    if constexpr (FAST == ARITH_FAST) fe_addsub2_fast(x[i0], x[i1], x[j0], x[j1], x[i0], dd[bf], x[j0], dd[bf + 1], *rare);
+                    else if constexpr (FAST == ARITH_FIX) fe_addsub2_fix(x[i0], x[i1], x[j0], x[j1], x[i0], dd[bf], x[j0], dd[bf + 1]);
                     else fe_addsub2(x[i0], x[i1], x[j0], x[j1], x[i0], dd[bf], x[j0], dd[bf + 1]);
                 } else {
                     Fe u = x[i0], v = x[i1];
-                    if constexpr (FAST) {
+                    if constexpr (FAST == ARITH_FAST) {
                         x[i0] = fe_add_fast(u, v, *rare);
                         dd[bf] = fe_sub_fast(u, v, *rare);
+                    } else if constexpr (FAST == ARITH_FIX) {
+                        x[i0] = fe_add_fix(u, v);
+                        dd[bf] = fe_sub_fix(u, v);
                     } else {
                         x[i0] = fe_add(u, v);
                         dd[bf] = fe_sub(u, v);
@@ -470,7 +476,7 @@ struct Round {
     // ALT: the launch has a destination table (PassParams::out_blk).  A compile-time switch: with the test at run time (inside
     // the store loop, or two loops behind one branch) the plain transforms paid 1-2 % more VALU instructions for index math
     // the compiler hoisted above the branch; the geometry-specialised kernels are instantiated for both values.
-    template <bool ALT, bool FAST = false>
+    template <bool ALT, int FAST = ARITH_EXACT>
     SC_HD void scatter_global(const PassParams& P, const Fe* x, const Fe (&twd_prefetched)[E], bool have_prefetched, rare_t* rare = nullptr) const {
         Fe v[E];
 #pragma unroll
@@ -538,7 +544,7 @@ struct Round {
 };
 
 // the three steps in order (generic kernel and the CPU emulation)
-template <int LOGE, int S, int GLR = -1, int GLC = -1, bool FAST = false>
+template <int LOGE, int S, int GLR = -1, int GLC = -1, int FAST = ARITH_EXACT>
 SC_HD void ntt_round(const PassParams& P, int sh, bool first, uint32_t tile, uint32_t tid, Fe* lds, const Fe* tw, rare_t* rare = nullptr) {
     constexpr int E = 1 << LOGE;
     Round<LOGE, S, GLR, GLC> R;
@@ -594,10 +600,11 @@ SC_HD void tile_twiddles_to_lds(const PassParams& P, int logR, uint32_t tid, uin
 // (ntt_pass_kernel_fixed) and eight (ntt_pass_kernel_fixed8).  core.hip's launch_pass and the emulator dispatch over these lists.
 #define SC_FIXED4_SHAPES(X) X(8, 3) X(7, 4) X(10, 2) X(6, 5) X(9, 3) X(8, 4)
 #define SC_FIXED8_SHAPES(X) X(10, 2) X(9, 3) X(8, 4)
-// FAST: the rounds use the top-limb field corrections and accumulate their flags in `rare` (one accumulator through all rounds
+// FAST = ARITH_FIX: the rounds use the self-repairing top-limb forms; no accumulator, nothing to redo (ntt_pass_kernel_fixed8).
+// FAST = ARITH_FAST: the rounds use the top-limb field corrections and accumulate their flags in `rare` (one accumulator through all rounds
 // of the tile); where it ends up non-zero the tile's outputs may be wrong -- also those of other waves, which got this wave's
-// values through LDS -- and the caller has the whole tile transformed again with FAST = false.
-template <int LOGE, int GLR, int GLC, int ROUND = 0, bool ALT = false, bool FAST = false>
+// values through LDS -- and the caller has the whole tile transformed again with the exact forms.
+template <int LOGE, int GLR, int GLC, int ROUND = 0, bool ALT = false, int FAST = ARITH_EXACT>
 struct FixedRounds {
     static constexpr int E = 1 << LOGE;
     static constexpr int NR = (GLR + LOGE - 1) / LOGE;
@@ -668,8 +675,10 @@ inline bool fixed_offsets_fit(const PassParams& P) {
     return true;
 }
 
-// Launches the FAST rounds serve: no coset scaling and no pruned stages.  Both sit under per-lane tests (zero padding), and the flag
-// accumulator is a wave-uniform SGPR mask that must not merge behind a divergent branch; the FAST instantiations leave those paths out.
+// Launches the ARITH_FAST / ARITH_FIX rounds serve: no coset scaling and no pruned stages.  Both sit under per-lane tests (zero
+// padding).  The flag accumulator of ARITH_FAST is a wave-uniform SGPR mask that must not merge behind a divergent branch, and what a
+// carry-out mask holds for the lanes a branch left inactive -- the masks ARITH_FIX tests -- is not settled here; the non-exact
+// instantiations leave those paths out and the first pass of an LDE stays on the exact kernel.
 inline bool fast_pass_ok(const PassParams& P) { return !P.coset_enable && P.prune_log == 0; }
 
 // Round schedule shared by the kernel and the CPU emulation: the short round (if any) goes first.
