@@ -1,5 +1,6 @@
 """Proof-of-work grinding without a GPU: the host specification (grinding.py) against an independent Keccak-f[1600], the g++ build of
-the kernel's lane function (csrc/grind.cuh through tests/emu/grind_emu.cpp) against hashlib, the library's host search, the
+the kernel's lane function (csrc/grind.cuh through tests/emu/grind_emu.cpp) against hashlib, the library's host search, every recorded constant of
+tests/grind_cases.py (the deep values, the quiet range, the batch members) proved with hashlib, the member limit of a batch, the
 verifier's check of the nonce on transcripts built by hand, and the constructors."""
 import ctypes
 import os
@@ -87,6 +88,51 @@ def test_cases_are_what_hashlib_says():
             assert gc.smallest(seed, bits) == low
 
 
+def test_deep_cases_are_what_hashlib_says():
+    """the recorded (seed, nonce, value) triples of grind_cases.DEEP: the value is hashlib's, and over the 2^16 nonces in front of the
+    nonce nothing is accepted at the value's own count of leading zero bits -- for the 33-bit-and-up ones that stretch is ALL a CPU
+    check proves of their being minimal (the search that found them ran on a GPU)"""
+    for seed, nonce, value in gc.DEEP:
+        assert gc.pow_value(seed, nonce) == value == grinding.pow_value(seed, nonce)
+        z = gc.leading_zeros(value)
+        assert value >> (64 - z) == 0 and value >> (63 - z) == 1
+        assert gc.accepted(seed, nonce, z) and not gc.accepted(seed, nonce, z + 1)
+        assert nonce > gc.STRETCH
+        assert gc.smallest(seed, z, nonce - gc.STRETCH, gc.STRETCH + 1) == nonce
+    assert [gc.leading_zeros(value) for _, _, value in gc.DEEP_CPU] == [22, 23, 24]
+    assert len(gc.DEEP_GPU) >= 2 and all(gc.leading_zeros(value) >= 33 and nonce >= 2 ** 32 for _, nonce, value in gc.DEEP_GPU)
+    assert len(set(seed for seed, _, _ in gc.DEEP)) == len(gc.DEEP)
+
+
+def test_library_host_search_finds_the_cpu_found_deep_cases_from_zero():
+    """sc_grind_host (transcript.h's Keccak-f, not hashlib) walks the 1.6 to 6.6 million nonces from 0 and ends on the recorded one"""
+    for seed, nonce, value in gc.DEEP_CPU:
+        z = gc.leading_zeros(value)
+        assert grinding.grind_library_host(seed, z) == nonce
+        assert grinding.grind_library_host(seed, z, nonce - gc.STRETCH, gc.STRETCH) is None      # one short of it
+
+
+def test_quiet_range_holds_nothing_at_28_bits():
+    seed, count = gc.QUIET
+    values = [gc.pow_value(seed, nonce) for nonce in range(count)]
+    assert max(gc.leading_zeros(v) for v in values) < 28
+    assert [gc.smallest(seed, bits, 0, count) for bits in (1, 2, 3)] == [2, 7, 22]
+    for bits in (28, 31, 32, 33, 48, 63):
+        assert grinding.grind_library_host(seed, bits, 0, count) is None
+
+
+def test_batch_members_fall_in_many_windows():
+    """what tests/test_gpu_grind_scale.py needs of the members it takes (2 * 256 + 8 on a part of 256 compute units): minima in more
+    than 16 different windows of 256, and the library's host search agrees with hashlib on some of them"""
+    seeds, minima = gc.batch_members(520, 10, 30000)
+    assert len(seeds) == len(set(seeds)) == 520 and None not in minima
+    assert len(set(low // 256 for low in minima)) > 16
+    for k in (0, 1, 519, minima.index(max(minima))):
+        assert grinding.grind_library_host(seeds[k], 10) == minima[k]
+    seeds, minima = gc.batch_members(65535, 3, 100000)
+    assert len(set(seeds)) == 65535 and None not in minima and max(minima) < 256
+
+
 # ---- the lane function, compiled by g++ ---------------------------------------------------------------------------------------------
 def build(target, extra):
     srcs = [os.path.join(EMU_DIR, "grind_emu.cpp")] + CSRC
@@ -118,8 +164,9 @@ def test_lane_function_against_hashlib(emu):
         got = (ctypes.c_uint64 * len(nonces))()
         emu.emu_grind_values(b"".join(seeds), (ctypes.c_uint64 * len(nonces))(*nonces), len(nonces), unrolled, got)
         assert list(got) == expect
-    for bits in (1, 12, 63):
+    for bits in range(1, 64):                                  # every shift, those across the 32-bit half included
         assert emu.emu_grind_accepts(2 ** (64 - bits) - 1, bits) == 1 and emu.emu_grind_accepts(2 ** (64 - bits), bits) == 0
+        assert emu.emu_grind_accepts(0, bits) == 1 and emu.emu_grind_accepts(2 ** 64 - 1, bits) == 0 and emu.emu_grind_accepts(2 ** 63, bits) == 0
 
 
 def test_window_walk_of_the_lane_function(emu):
@@ -170,6 +217,17 @@ def test_library_refuses_bad_ranges():
     with pytest.raises(AssertionError):
         grinding.grind(seed, 0)
     assert grinding.grind_batch([], 8) == []
+
+
+def test_library_refuses_more_than_65535_members_before_any_device_work():
+    """no device is needed (or looked for) to refuse the batch: the answer is SC_ERR_BAD_ARG, not a HIP error, and nothing is written"""
+    import starkcore
+    lib = starkcore.lib()
+    count = 65536
+    nonces, found = (ctypes.c_uint64 * count)(*[7] * count), (ctypes.c_uint8 * count)(*[7] * count)
+    assert lib.sc_grind_batch(b"\x07" * (32 * count), count, 3, 0, 100, nonces, found, None) == -6          # SC_ERR_BAD_ARG (include/starkcore.h)
+    assert "at most 65535" in lib.sc_last_error().decode()
+    assert set(nonces) == {7} and set(found) == {7}
 
 
 # ---- the verifier's check, on transcripts built by hand ------------------------------------------------------------------------------
