@@ -803,6 +803,34 @@ int sc_fri_fold_slab_build_dev(const void* d_in, uint64_t rows, uint64_t cols, u
 uint64_t sc_merkle_leaves(const sc_merkle_t* tree);
 int sc_merkle_free(sc_merkle_t* tree);
 
+/* ---- Row commitments: ONE tree over the rows of a matrix of codewords (not in the reference) ------------------- */
+/* leaf i = BLAKE2b-512(col[0][i] || ... || col[w-1][i], person = "sc-merkle-row"), 16 little-endian bytes per value, digest 64, no
+ * key; node = H(left || right) as above.  The personalisation keeps leaves and nodes apart (a row of 8 values is 128 bytes, a node's
+ * message).  The values are hashed as they lie in memory: nothing is reduced.  d_cols: a HOST array of w device pointers, each to N
+ * elements (N a power of two; the columns need not be neighbours); the result is an ordinary sc_merkle_t: sc_merkle_root,
+ * sc_merkle_open_batch, sc_merkle_level_copy_dev and sc_merkle_free work on it unchanged.  N == 1: the root is the leaf digest and
+ * paths are empty.  One lane per row, ceil(16 w / 128) compressions per leaf (csrc/merkle_rows.cuh); from 256 leaves up the leaf stage
+ * is the entry of the fused subtree launch of the decimal trees.
+ * build_dev:       synchronous, the root to root_out (may be NULL when `tree` is given; `tree` may be NULL when root_out is given).
+ * build_async_dev: only enqueues; sc_merkle_root waits.  Fetch the root (or free the tree) before destroying a caller-owned stream.
+ *                  Both builds take the caller's stream; the pointer table travels as a kernel argument and the tree is the call's
+ *                  own allocation: no shared scratch, no one-stream rule -- the columns must be complete on `stream`, and builds on
+ *                  different streams do not disturb one another.
+ * query_dev:       for k positions, the w values of each row (rows_out: [k][w], 16 bytes each) and its path (paths_out: 64 * log2 N
+ *                  bytes per position) in ONE launch on the library stream; synchronous.  d_cols, w: the columns the tree was built
+ *                  from, whose build must be complete or ordered before the library stream (sc_merkle_root has returned).  Outputs
+ *                  inside a buffer of sc_host_alloc are written by the kernel itself; other host memory is served through the shared
+ *                  staging scratch, so queries keep the one-stream rule like sc_merkle_query_dev.  k == 0: SC_OK.
+ * row_leaf:        host only, no GPU: the leaf digest of one row of w values (16 bytes each) -- the specification, for tests and callers
+ *                  without Python.
+ * SC_ERR_BAD_ARG, with nothing enqueued and nothing written: w == 0, w > SC_MERKLE_ROWS_MAX_COLUMNS, a NULL column or table, an index
+ * >= N, a NULL output that is needed; SC_ERR_NOT_POW2: N no power of two. */
+#define SC_MERKLE_ROWS_MAX_COLUMNS 256
+int sc_merkle_rows_build_dev(const void* const* d_cols, uint64_t w, uint64_t N, uint8_t root_out[64], sc_merkle_t** tree, void* stream);
+int sc_merkle_rows_build_async_dev(const void* const* d_cols, uint64_t w, uint64_t N, sc_merkle_t** tree, void* stream);
+int sc_merkle_rows_query_dev(const sc_merkle_t* tree, const void* const* d_cols, uint64_t w, const uint64_t* indices, uint64_t k, void* rows_out, uint8_t* paths_out);
+int sc_merkle_row_leaf(const void* row, uint64_t w, uint8_t out[64]);   /* host only */
+
 /* ---- Merkle forests: Merkle.commit (merkle.py:13-14) of `count` arrays of N leaves each in one set of launches ------------------ */
 /* d_elems: a device matrix [count][N] of residues, row t = the leaves of tree t; N a power of two >= 2, count >= 1.  All levels of all
  * trees are kept (tree-major, csrc/merkle_forest.cuh).  The largest forest an entry takes has SC_FOREST_MAX_LEAVES leaves in total

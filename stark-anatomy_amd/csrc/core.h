@@ -4,6 +4,7 @@
 //
 //   core.hip          state, pool, streams, tables, planner + pass launches, vectors / randomness / transforms / pointwise entries
 //   merkle_fri.hip    Merkle trees and forests of them, the FRI fold and commit loop, the Fiat-Shamir transcript, openings
+//   merkle_rows.hip   row commitments: one Merkle tree over the rows of a matrix of codewords (csrc/merkle_rows.cuh); the climb is merkle_fri.hip's
 //   polytree_geo.hip  subproduct trees and geometric progressions (fast_zerofier / fast_evaluate / fast_interpolate)
 //   fourstep.hip      batched transforms, the sharded four-step plan, the RCCL communicator, the direct-store corner turn
 //   rescue.hip        the Rescue-Prime permutation (hash and trace; permutation, sponge and states at any width 2 .. 8) over many inputs
@@ -255,7 +256,12 @@ bool upload_small(void* d_dst, const void* host, size_t bytes, hipStream_t st);
 int merkle_climb(uint64_t* levels, uint64_t N, int lvl, hipStream_t st, volatile uint64_t* host = nullptr, uint64_t seq = 0, bool* published = nullptr);
 int merkle_finish(uint64_t* levels, uint64_t width, hipStream_t st);
 int root_slot_get();
-int merkle_build_device(const Fe* d_elems, uint64_t N, uint8_t root_out[64], sc_merkle** tree, hipStream_t st, BuildMode mode = BUILD_SYNC, const FoldIn* fold = nullptr);
+// A leaf stage other than the decimal one of merkle.cuh (merkle_rows.hip: rows of several columns): called once by merkle_build_device to
+// enqueue level 0 of `levels` on `st` -- nlev < 0: that level alone (fewer than 256 leaves); otherwise the leaves and the first nlev
+// levels of every 256-leaf subtree in one launch of merkle_subtree_kernel<true, four_lane, ...>.
+using LeafStage = std::function<void(uint64_t* levels, uint64_t N, int nlev, bool four_lane, hipStream_t st)>;
+int merkle_build_device(const Fe* d_elems, uint64_t N, uint8_t root_out[64], sc_merkle** tree, hipStream_t st, BuildMode mode = BUILD_SYNC, const FoldIn* fold = nullptr,
+                        const LeafStage* leaves = nullptr);
 int merkle_root_wait(sc_merkle* t, bool from_free = false);
 void root_poll_unlocked(std::unique_lock<std::mutex>& lk, const sc_merkle* t);
 int fold_prepare(const Fe* d_in, uint64_t N, Fe alpha, Fe offset, Fe omega, Fe* d_out, hipStream_t st, FoldIn* f);

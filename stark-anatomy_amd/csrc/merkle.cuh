@@ -56,16 +56,20 @@ template <int R> __device__ __forceinline__ uint64_t rotr64c(uint64_t x) {
     B2_G(0, 5, 10, 15, m[s8], m[s9]);  B2_G(1, 6, 11, 12, m[s10], m[s11]);              \
     B2_G(2, 7, 8, 13, m[s12], m[s13]); B2_G(3, 4, 9, 14, m[s14], m[s15]);
 
-// Single-block unkeyed BLAKE2b-512 of a message of `len` <= 128 bytes held zero-padded in m[16].
-__device__ __forceinline__ void blake2b_single_block(const uint64_t m[16], uint32_t len, uint64_t h[8]) {
-    uint64_t v[16];
+// The state an unkeyed BLAKE2b-512 starts from.
+__device__ __forceinline__ void blake2b_initial_state(uint64_t h[8]) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) { h[i] = B2_IV[i]; }
     h[0] ^= 0x01010040ull;       // digest 64, key 0, fanout 1, depth 1
+}
+
+// One compression: the block m[16] into h, `t` = bytes of the message up to and including this block, `last`: the final block.
+__device__ __forceinline__ void blake2b_compress_block(const uint64_t m[16], uint64_t t, bool last, uint64_t h[8]) {
+    uint64_t v[16];
 #pragma unroll
     for (int i = 0; i < 8; ++i) { v[i] = h[i]; v[i + 8] = B2_IV[i]; }
-    v[12] ^= (uint64_t)len;
-    v[14] = ~v[14];              // final block
+    v[12] ^= t;
+    if (last) v[14] = ~v[14];
     B2_ROUND(0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15)
     B2_ROUND(14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3)
     B2_ROUND(11, 8, 12, 0, 5, 2, 15, 13, 10, 14, 3, 6, 7, 1, 9, 4)
@@ -80,6 +84,12 @@ __device__ __forceinline__ void blake2b_single_block(const uint64_t m[16], uint3
     B2_ROUND(14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3)
 #pragma unroll
     for (int i = 0; i < 8; ++i) h[i] ^= v[i] ^ v[i + 8];
+}
+
+// Single-block unkeyed BLAKE2b-512 of a message of `len` <= 128 bytes held zero-padded in m[16].
+__device__ __forceinline__ void blake2b_single_block(const uint64_t m[16], uint32_t len, uint64_t h[8]) {
+    blake2b_initial_state(h);
+    blake2b_compress_block(m, (uint64_t)len, true, h);
 }
 
 // ---- four lanes per hash ---------------------------------------------------------------------------------------------
@@ -423,6 +433,9 @@ __device__ __forceinline__ void entry_prio(bool on) {
 #endif
 }
 
+// SC_MERKLE_NO_KERNELS: a translation unit that wants the device functions and the kernel TEMPLATES of this header only
+// (merkle_rows.hip) defines it; the plain kernels have one home, merkle_fri.hip.
+#ifndef SC_MERKLE_NO_KERNELS
 __global__ void __launch_bounds__(256) merkle_leaf_kernel(const Fe* __restrict__ elems, uint64_t* __restrict__ digests, uint64_t N) {
     __shared__ uint4 sm[256 * 4];
     const uint64_t base = (uint64_t)blockIdx.x * 256u;
@@ -438,6 +451,7 @@ __global__ void __launch_bounds__(256) merkle_leaf_kernel(const Fe* __restrict__
     }
     store_digests_coalesced(sm, h, active, digests, base, n_here);
 }
+#endif  // SC_MERKLE_NO_KERNELS
 
 __device__ __forceinline__ void merkle_node(const uint64_t* __restrict__ in, uint64_t* __restrict__ out, uint64_t i) {
     uint64_t m[16], h[8];
@@ -450,6 +464,7 @@ __device__ __forceinline__ void merkle_node(const uint64_t* __restrict__ in, uin
     for (int k = 0; k < 4; ++k) o[k] = make_ulonglong2(h[2 * k], h[2 * k + 1]);
 }
 
+#ifndef SC_MERKLE_NO_KERNELS
 // one level: count parents from 2*count children; a workgroup handles 256 consecutive parents
 __global__ void __launch_bounds__(256) merkle_level_kernel(const uint64_t* __restrict__ in, uint64_t* __restrict__ out, uint64_t count) {
     __shared__ uint4 sm[256 * 8];                     // 32 KiB: the workgroup's 256 messages of 128 bytes
@@ -479,6 +494,7 @@ __global__ void __launch_bounds__(256) merkle_level_kernel(const uint64_t* __res
     __syncthreads();                                   // all messages consumed before the buffer is reused for digests
     store_digests_coalesced(sm, h, active, out, base, n_here);
 }
+#endif  // SC_MERKLE_NO_KERNELS
 
 // Fused subtree kernel: a workgroup owns 256 consecutive nodes of level `lvl0` and climbs up to `nlev` further levels of
 // THEIR subtree through LDS (256 -> 128 -> ... ), writing every level to its place in the tree (all levels are kept for
@@ -511,9 +527,13 @@ __device__ __forceinline__ Fe fold_element(const FoldIn& f, uint64_t i, uint64_t
     return fe_add(fe_half(fe_add(a, b)), mont_mul(fe_sub(a, b), t));
 }
 
-template <bool LEAVES, bool FOUR_LANE, bool FOLD = false>
-__global__ void __launch_bounds__(256) merkle_subtree_kernel(const Fe* __restrict__ elems, uint64_t* __restrict__ levels, uint64_t N, int lvl0, int nlev, const FoldIn fold = FoldIn()) {
-    __shared__ uint4 cur[LEAVES ? 256 * 5 : 256 * 4];  // this level's digests of the subtree (16 KiB); before that, the leaf stage's 80 bytes per thread
+// Rows (with LEAVES): another leaf stage altogether -- rows.leaf(i, h) hashes leaf i of the tree into h (csrc/merkle_rows.cuh: a row
+// of several columns); the default, NoRows, is the decimal leaf of one column above and leaves every instantiation as it was.
+struct NoRows { static constexpr bool on = false; };
+template <bool LEAVES, bool FOUR_LANE, bool FOLD = false, class Rows = NoRows>
+__global__ void __launch_bounds__(256) merkle_subtree_kernel(const Fe* __restrict__ elems, uint64_t* __restrict__ levels, uint64_t N, int lvl0, int nlev, const FoldIn fold = FoldIn(),
+                                                             const Rows rows = Rows()) {
+    __shared__ uint4 cur[(LEAVES && !Rows::on) ? 256 * 5 : 256 * 4];  // this level's digests of the subtree (16 KiB); before that, the decimal leaf stage's 80 bytes per thread
     constexpr bool four_lane = FOUR_LANE && (SC_MERKLE_4LANE != 0);
     constexpr uint32_t FOUR_LANE_FROM = SC_FOUR_LANE_FROM;      // the width (digests) at which a latency-bound launch hands over to the four-lane form
     __shared__ uint64_t linA[four_lane ? (SC_FOUR_LANE_FROM / 2) * 17 : 1], linB[four_lane ? (SC_FOUR_LANE_FROM / 4) * 17 : 1];   // 4-lane path: FOUR_LANE_FROM resp. half as many digests in the lin layout
@@ -522,7 +542,9 @@ __global__ void __launch_bounds__(256) merkle_subtree_kernel(const Fe* __restric
     auto level_off = [N](int l) -> uint64_t { return l == 0 ? 0 : 2 * N - (N >> (l - 1)); };
     uint64_t h[8];
     entry_prio(true);
-    if (LEAVES) {
+    if constexpr (LEAVES && Rows::on) {
+        rows.leaf(wg * 256u + t, h);                   // (lowers the entry priority behind its own loads)
+    } else if (LEAVES) {
         uint64_t m[16];
         Fe e;
         if constexpr (FOLD) {
@@ -611,6 +633,7 @@ __device__ __forceinline__ void publish_root(const uint64_t* root, volatile uint
     if (threadIdx.x == 0) host[8] = seq;
 }
 
+#ifndef SC_MERKLE_NO_KERNELS
 __global__ void __launch_bounds__(1024) merkle_tail_kernel(uint64_t* level, uint64_t width, volatile uint64_t* host = nullptr, uint64_t seq = 0) {
     uint64_t* cur = level;
     uint64_t w = width;
@@ -746,6 +769,7 @@ __global__ void __launch_bounds__(256) merkle_query_multi_kernel(QueryTrees Q, c
         }
     }
 }
+#endif  // SC_MERKLE_NO_KERNELS
 
 #endif  // __HIPCC__
 

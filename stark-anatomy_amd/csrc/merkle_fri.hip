@@ -90,7 +90,9 @@ int root_slot_get() {
 // trees can be alive at once without degrading the asynchronous builds of Fri.commit to the synchronous path.
 // fold != nullptr (with N >= 256): the leaves are the split-and-fold of the previous round's codeword, computed, stored to
 // d_elems (= fold->out) and hashed by the leaf stage itself (merkle_subtree_kernel<true, *, true>)
-int merkle_build_device(const Fe* d_elems, uint64_t N, uint8_t root_out[64], sc_merkle** tree, hipStream_t st, BuildMode mode, const FoldIn* fold) {
+// leaves != nullptr (d_elems and fold are then not looked at): the caller's leaf stage instead of the decimal one, fused from 256
+// leaves up in the same way
+int merkle_build_device(const Fe* d_elems, uint64_t N, uint8_t root_out[64], sc_merkle** tree, hipStream_t st, BuildMode mode, const FoldIn* fold, const LeafStage* leaves) {
     if (!is_pow2(N)) return fail(SC_ERR_NOT_POW2, "length must be power of two");
     if (fold && N < 256) return fail(SC_ERR_BAD_ARG, "the fused fold needs at least 256 leaves");
     const int slot = (mode == BUILD_ASYNC && tree) ? root_slot_get() : -1;
@@ -102,7 +104,11 @@ int merkle_build_device(const Fe* d_elems, uint64_t N, uint8_t root_out[64], sc_
     uint64_t* levels = nullptr;
     const size_t tree_bytes = (2 * N - 1) * 64;
     HIPCHK(pool_alloc((void**)&levels, tree_bytes));
-    if (N >= 256 && N <= FUSE_MAX_W) {
+    if (leaves) {
+        const int nlev = N < 256 ? -1 : (N <= FUSE_MAX_W ? 8 : (g.merkle_big_nlev > 0 ? g.merkle_big_nlev : 1));
+        (*leaves)(levels, N, nlev, N <= FUSE_MAX_W, st);
+        (void)merkle_climb(levels, N, nlev < 0 ? 0 : nlev, st, host, seq, &published);
+    } else if (N >= 256 && N <= FUSE_MAX_W) {
         int nlev = ilog2(N) < 8 ? ilog2(N) : 8;                  // leaves + up to 8 levels of every 256-leaf subtree in one launch
         if (fold) hipLaunchKernelGGL((merkle_subtree_kernel<true, true, true>), dim3((unsigned)(N / 256)), dim3(256), 0, st, d_elems, levels, N, 0, nlev, *fold);
         else hipLaunchKernelGGL((merkle_subtree_kernel<true, true>), dim3((unsigned)(N / 256)), dim3(256), 0, st, d_elems, levels, N, 0, nlev, FoldIn());

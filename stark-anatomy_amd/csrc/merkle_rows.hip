@@ -1,0 +1,107 @@
+// merkle_rows.hip -- row commitments (csrc/merkle_rows.cuh): one Merkle tree over the rows of a matrix of codewords
+// whose columns are separate device vectors.  The tree is an ordinary sc_merkle_t: the climb above the leaf stage, the root's way to
+// the host and everything that reads a tree are merkle_fri.hip's.
+#define SC_MERKLE_NO_KERNELS
+#include "core.h"
+#include "merkle_rows.cuh"
+#include "transcript.h"
+
+namespace {
+
+int rows_check(const char* what, const void* const* d_cols, uint64_t w, uint64_t N) {
+    if (!d_cols) return fail(SC_ERR_BAD_ARG, std::string(what) + ": null argument");
+    if (w == 0 || w > SC_MERKLE_ROWS_MAX_COLUMNS) return fail(SC_ERR_BAD_ARG, std::string(what) + ": 1 .. 256 columns");
+    for (uint64_t c = 0; c < w; ++c) if (!d_cols[c]) return fail(SC_ERR_BAD_ARG, std::string(what) + ": null column");
+    if (!is_pow2(N)) return fail(SC_ERR_NOT_POW2, "length must be power of two");
+    return SC_OK;
+}
+
+void rows_table(const void* const* d_cols, uint64_t w, RowColumns& C) {
+    for (uint64_t c = 0; c < ROWS_MAX_COLUMNS; ++c) C.col[c] = c < w ? (const Fe*)d_cols[c] : nullptr;
+    C.w = (uint32_t)w;
+}
+
+int rows_build(const void* const* d_cols, uint64_t w, uint64_t N, uint8_t root_out[64], sc_merkle_t** tree, hipStream_t st, BuildMode mode) {
+    RowColumns C;
+    rows_table(d_cols, w, C);
+    // the leaf stage of merkle_build_device: below 256 leaves a plain launch (nlev < 0), from there up the entry of the fused subtree
+    // launch -- leaves plus nlev levels through LDS, the level_off layout of the decimal trees
+    const LeafStage leaves = [&C](uint64_t* levels, uint64_t n, int nlev, bool four_lane, hipStream_t s) {
+        if (nlev < 0) hipLaunchKernelGGL(merkle_rows_leaf_kernel, dim3(1), dim3(256), 0, s, C, levels, n);
+        else if (four_lane) hipLaunchKernelGGL((merkle_subtree_kernel<true, true, false, RowColumns>), dim3((unsigned)(n / 256)), dim3(256), 0, s, (const Fe*)nullptr, levels, n, 0, nlev, FoldIn(), C);
+        else hipLaunchKernelGGL((merkle_subtree_kernel<true, false, false, RowColumns>), dim3((unsigned)(n / 256)), dim3(256), 0, s, (const Fe*)nullptr, levels, n, 0, nlev, FoldIn(), C);
+    };
+    return merkle_build_device(nullptr, N, root_out, tree, st, mode, nullptr, &leaves);
+}
+
+}  // namespace
+
+extern "C" {
+
+int sc_merkle_rows_build_dev(const void* const* d_cols, uint64_t w, uint64_t N, uint8_t root_out[64], sc_merkle_t** tree, void* stream) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    if (!root_out && !tree) return fail(SC_ERR_BAD_ARG, "sc_merkle_rows_build_dev: null argument");
+    SCCHK(rows_check("sc_merkle_rows_build_dev", d_cols, w, N));
+    return rows_build(d_cols, w, N, root_out, tree, pick_stream(stream), BUILD_SYNC);
+}
+
+int sc_merkle_rows_build_async_dev(const void* const* d_cols, uint64_t w, uint64_t N, sc_merkle_t** tree, void* stream) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    if (!tree) return fail(SC_ERR_BAD_ARG, "sc_merkle_rows_build_async_dev: null argument");
+    SCCHK(rows_check("sc_merkle_rows_build_async_dev", d_cols, w, N));
+    return rows_build(d_cols, w, N, nullptr, tree, pick_stream(stream), BUILD_ASYNC);
+}
+
+int sc_merkle_rows_query_dev(const sc_merkle_t* tree, const void* const* d_cols, uint64_t w, const uint64_t* indices, uint64_t k, void* rows_out, uint8_t* paths_out) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    if (!tree) return fail(SC_ERR_BAD_ARG, "sc_merkle_rows_query_dev: null argument");
+    SCCHK(rows_check("sc_merkle_rows_query_dev", d_cols, w, tree->N));
+    if (k && (!indices || !rows_out || (tree->logN > 0 && !paths_out))) return fail(SC_ERR_BAD_ARG, "sc_merkle_rows_query_dev: null argument");
+    for (uint64_t i = 0; i < k; ++i) if (indices[i] >= tree->N) return fail(SC_ERR_BAD_ARG, "cannot open invalid index");
+    if (k == 0) return SC_OK;
+    const size_t idx_bytes = (k * 8 + 255) & ~255ull;
+    const size_t row_bytes = k * w * sizeof(Fe), path_bytes = k * 64 * (size_t)tree->logN;
+    // a buffer of sc_host_alloc is written by the kernel itself (the stores cross the bus as they are made); any other host pointer
+    // is served through device scratch and a copy
+    const bool rows_direct = host_pool_holds(rows_out, row_bytes), paths_direct = !path_bytes || host_pool_holds(paths_out, path_bytes);
+    const size_t row_stage = rows_direct ? 0 : (row_bytes + 255) & ~255ull, path_stage = paths_direct ? 0 : path_bytes;
+    void* buf;
+    SCCHK(scratch(5, idx_bytes + row_stage + path_stage + 256, &buf));
+    uint64_t* d_idx = (uint64_t*)buf;
+    Fe* d_rows = rows_direct ? (Fe*)rows_out : (Fe*)((char*)buf + idx_bytes);
+    uint64_t* d_paths = paths_direct ? (uint64_t*)paths_out : (uint64_t*)((char*)buf + idx_bytes + row_stage);
+    SCCHK(upload(d_idx, indices, k * 8, g.stream));
+    RowColumns C;
+    rows_table(d_cols, w, C);
+    const uint64_t total = k * (w + 4ull * (uint64_t)tree->logN);
+    hipLaunchKernelGGL(merkle_rows_query_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, g.stream, C, (const uint64_t*)tree->d_levels, tree->N, tree->logN,
+                       (const uint64_t*)d_idx, k, d_rows, d_paths);
+    HIPCHK(hipGetLastError());
+    if (!rows_direct) HIPCHK(hipMemcpyAsync(rows_out, d_rows, row_bytes, hipMemcpyDeviceToHost, g.stream));
+    if (!paths_direct) HIPCHK(hipMemcpyAsync(paths_out, d_paths, path_bytes, hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+    return SC_OK;
+}
+
+// host only: the walk of merkle_rows.cuh over transcript.h's compression
+int sc_merkle_row_leaf(const void* row, uint64_t w, uint8_t out[64]) {
+    if (!row || !out || w == 0 || w > SC_MERKLE_ROWS_MAX_COLUMNS) {
+        std::lock_guard<std::mutex> lk(g_mu);
+        return fail(SC_ERR_BAD_ARG, "sc_merkle_row_leaf: a row of 1 .. 256 values");
+    }
+    struct Source {
+        const uint8_t* row;
+        void gate(bool) const {}
+        Fe at(uint32_t c) const { Fe e; memcpy(&e, row + 16 * (size_t)c, 16); return e; }
+    };
+    uint64_t h[8];
+    row_leaf_walk((uint32_t)w, Source{(const uint8_t*)row},
+                  [](uint64_t* hh, const uint64_t* m, uint64_t t, bool last) { blake2b_compress(hh, (const uint8_t*)m, t, last); }, h);
+    memcpy(out, h, 64);
+    return SC_OK;
+}
+
+}  // extern "C"

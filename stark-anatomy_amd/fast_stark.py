@@ -124,9 +124,14 @@ def device_powers(base, count):
 
 
 class FastStark:
-    def __init__(self, field, expansion_factor, num_colinearity_checks, security_level, num_registers, num_cycles, transition_constraints_degree=2, grinding_bits=0):
+    def __init__(self, field, expansion_factor, num_colinearity_checks, security_level, num_registers, num_cycles, transition_constraints_degree=2, grinding_bits=0,
+                 row_commitments=False):
         """grinding_bits (not in the reference; 0 = the reference's protocol): bits of proof of work on the transcript before FRI's
-        query indices (grinding.py, Fri(grinding_bits)); each bit stands in for half a colinearity check in the security level"""
+        query indices (grinding.py, Fri(grinding_bits)); each bit stands in for half a colinearity check in the security level.
+        row_commitments (not in the reference; False = the reference's protocol, byte for byte): the boundary-quotient codewords and the
+        randomizer codeword are committed in ONE Merkle tree over their rows (Merkle.commit_rows) -- one root in front of
+        FRI's objects, and per opened position one row of num_registers + 1 values and ONE authentication path -- instead of a tree, a
+        root and a path each.  No challenge lies between those commitments, so nothing else of the protocol moves."""
         assert(field.p.bit_length() >= security_level), "p must have at least as many bits as security level"
         assert(expansion_factor & (expansion_factor - 1) == 0), "expansion factor must be a power of 2"
         assert(expansion_factor >= 4), "expansion factor must be 4 or greater"
@@ -137,6 +142,7 @@ class FastStark:
         self.field, self.security_level = field, security_level
         self.expansion_factor, self.num_colinearity_checks = expansion_factor, num_colinearity_checks
         self.grinding_bits = grinding_bits
+        self.row_commitments = bool(row_commitments)
         self.num_registers, self.original_trace_length = num_registers, num_cycles
         self.num_randomizers = 4 * num_colinearity_checks
         self.randomized_trace_length = num_cycles + self.num_randomizers
@@ -370,6 +376,8 @@ class FastStark:
         later = _po.lazy_objects(proof_stream) if on_device and not FastStark.EAGER_COMMITS else None
 
         def commit(codeword):
+            if self.row_commitments:
+                return                                   # (committed together, in the row tree below the randomizer's LDE)
             if later is not None and isinstance(codeword, DeviceCodeword):
                 later.add(_po.RootLater(codeword.start_tree()))
             else:
@@ -408,6 +416,18 @@ class FastStark:
         self._mark("randomizer polynomial: os.urandom / getrandom draws and Field.sample")
         randomizer_codeword = lde(randomizer_polynomial)
         commit(randomizer_codeword)
+        row_tree = None
+        if self.row_commitments:
+            # ONE tree over the rows of [boundary quotients ..., randomizer]: one root, pushed where the randomizer's would be
+            row_columns = boundary_quotient_codewords + [randomizer_codeword]
+            if later is not None and all(isinstance(c, DeviceCodeword) for c in row_columns):
+                row_tree = _sc.RowTree.start(row_columns)
+                later.add(_po.RootLater(row_tree))
+            elif Merkle._on_device(row_columns, len(randomizer_codeword)):
+                row_tree = _sc.RowTree.build(row_columns)
+                proof_stream.push(row_tree.root)
+            else:
+                proof_stream.push(Merkle.commit_rows(row_columns))
         self._mark("randomizer polynomial: LDE, commitment")
 
         _collect_verdicts(pending or ())                 # the collected checks: the device has long decided them
@@ -437,6 +457,8 @@ class FastStark:
         # are fetched in the query phase's own device round trip (AlsoOpen) when every codeword lives on the device
         N = self.fri.domain_length
         committed = boundary_quotient_codewords + [randomizer_codeword, transition_zerofier_codeword]
+        if self.row_commitments:
+            committed = [transition_zerofier_codeword]   # (the others open as rows of the row tree, in front of these)
 
         def opened_positions(indices):
             # the queried positions and their expansion_factor / half-domain companions (fast_stark.py:154-158)
@@ -451,6 +473,8 @@ class FastStark:
         self._mark("FRI: commit + query phases, openings fetched with them")
 
         quadrupled_indices = opened_positions(indices)
+        if self.row_commitments:
+            self._open_rows(row_tree, row_columns, quadrupled_indices, proof_stream)
         lazy = _po.lazy_objects(proof_stream) if all(_po.eligible(codeword) for codeword in committed) else None
         if lazy is not None:
             # the device's answers as they are (proof_objects.Openings): same transcript bytes, no object per digest
@@ -476,8 +500,8 @@ class FastStark:
         """does prove_batch serve this batch with the members' work done together?  Decided from shapes alone, before any draw:
         the main field, traces of one length (long enough for the device data flow) and of one column per register, boundaries that
         name the same (cycle, register) pairs, an FRI shape the forest path serves, and a member's codewords within one forest"""
-        if self.field.p != Field.P_MAIN:
-            return False
+        if self.field.p != Field.P_MAIN or self.row_commitments:
+            return False                                 # (row commitments: no batched row forests yet, members go one by one)
         rows = len(traces[0])
         if any(len(trace) != rows for trace in traces) or rows < 1 or rows + self.num_randomizers < FastStark.DEVICE_MIN:
             return False
@@ -1029,6 +1053,26 @@ class FastStark:
             entries, paths = [codeword[i] for i in indices], Merkle._tree(codeword).open_batch(indices)
         self._push_openings(entries, paths, proof_stream)
 
+    def _open_rows(self, row_tree, columns, indices, proof_stream):
+        """row, path, row, path, ... of the row commitment: per position the list of every column's value there and ONE path.  A
+        resident tree answers in one launch (RowTree.query), described to the stream without objects where the stream takes
+        descriptions; the host-list data flow opens position by position (Merkle.open_rows)."""
+        lazy = _po.lazy_objects(proof_stream) if row_tree is not None and all(_po.eligible(c) for c in columns) else None
+        if lazy is not None:
+            # the device's answers as they are (proof_objects.RowOpenings): no object per value or digest
+            values, paths = row_tree.query_raw(indices)
+            lazy.add(_po.RowOpenings(columns, indices, values, paths))
+            return
+        if row_tree is not None:
+            rows, paths = row_tree.query(indices)
+            field = self.field
+            rows = [[FieldElement(v, field) for v in row] for row in rows]
+        else:
+            rows, paths = zip(*[Merkle.open_rows(i, columns) for i in indices]) if indices else ((), ())
+        for row, path in zip(rows, paths):
+            proof_stream.push(row)
+            proof_stream.push(path)
+
     @staticmethod
     def _push_openings(entries, paths, proof_stream):
         if type(proof_stream) is ProofStream:            # push == objects.append: one list extension for the whole codeword
@@ -1045,8 +1089,11 @@ class FastStark:
         trace_rows = 1 + max(cycle for cycle, _, _ in boundary) + self.num_randomizers
 
         # the commitments, and the combination weights they determine
-        quotient_roots = [stream.pull() for _ in registers]
-        randomizer_root = stream.pull()
+        if self.row_commitments:
+            row_root = stream.pull()                     # one tree over the rows of [boundary quotients ..., randomizer]
+        else:
+            quotient_roots = [stream.pull() for _ in registers]
+            randomizer_root = stream.pull()
         weights = self.sample_weights(1 + 2 * len(transition_constraints) + 2 * self.num_registers, stream.verifier_fiat_shamir())
 
         # low-degree test of the combination; it reports the combination's values at the points it opened
@@ -1059,14 +1106,21 @@ class FastStark:
         # every committed codeword opened at those points and at their successors on the trace domain
         N, step = self.fri.domain_length, self.expansion_factor
         positions = sorted([i for i, _ in opened] + [(i + step) % N for i, _ in opened])
-        quotient_leaves = []
-        for root in quotient_roots:
-            quotient_leaves.append(self._pull_openings(stream, root, positions))
-            if quotient_leaves[-1] is None:
+        if self.row_commitments:
+            opened_rows = self._pull_row_openings(stream, row_root, positions)
+            if opened_rows is None:
                 return False
-        randomizer = self._pull_openings(stream, randomizer_root, positions)
-        if randomizer is None:
-            return False
+            quotient_leaves = [{position: row[s] for position, row in opened_rows.items()} for s in registers]
+            randomizer = {position: row[-1] for position, row in opened_rows.items()}
+        else:
+            quotient_leaves = []
+            for root in quotient_roots:
+                quotient_leaves.append(self._pull_openings(stream, root, positions))
+                if quotient_leaves[-1] is None:
+                    return False
+            randomizer = self._pull_openings(stream, randomizer_root, positions)
+            if randomizer is None:
+                return False
         zerofier_values = self._pull_openings(stream, transition_zerofier_root, positions)
         if zerofier_values is None:
             return False
@@ -1121,8 +1175,11 @@ class FastStark:
         trace_rows = 1 + max(cycle for cycle, _, _ in boundary) + self.num_randomizers
 
         # the commitments, and the combination weights they determine
-        quotient_roots = [stream.pull() for _ in registers]
-        randomizer_root = stream.pull()
+        if self.row_commitments:
+            row_root = stream.pull()                     # one tree over the rows of [boundary quotients ..., randomizer]
+        else:
+            quotient_roots = [stream.pull() for _ in registers]
+            randomizer_root = stream.pull()
         weights = self.sample_weights(1 + 2 * len(transition_constraints) + 2 * self.num_registers, stream.verifier_fiat_shamir())
 
         # low-degree test of the combination; it reports the combination's values at the points it opened
@@ -1135,10 +1192,17 @@ class FastStark:
         # every committed codeword opened at those points and at their successors on the trace domain
         N, step = self.fri.domain_length, self.expansion_factor
         positions = sorted([i for i, _ in opened] + [(i + step) % N for i, _ in opened])
-        quotient_leaves = []
-        for root in quotient_roots:
-            quotient_leaves.append(self._collect_openings(stream, root, positions, checks, owner))
-        randomizer = self._collect_openings(stream, randomizer_root, positions, checks, owner)
+        if self.row_commitments:
+            opened_rows = self._pull_row_openings(stream, row_root, positions, checks, owner)
+            if opened_rows is None:
+                return False
+            quotient_leaves = [{position: row[s] for position, row in opened_rows.items()} for s in registers]
+            randomizer = {position: row[-1] for position, row in opened_rows.items()}
+        else:
+            quotient_leaves = []
+            for root in quotient_roots:
+                quotient_leaves.append(self._collect_openings(stream, root, positions, checks, owner))
+            randomizer = self._collect_openings(stream, randomizer_root, positions, checks, owner)
         zerofier_values = self._collect_openings(stream, transition_zerofier_root, positions, checks, owner)
 
         # the combination recomputed from the openings must agree with FRI's view of it at every queried point
@@ -1237,6 +1301,27 @@ class FastStark:
             checks.merkle(owner, root, position, path, leaf)
             leaves[position] = leaf
         return leaves
+
+    def _pull_row_openings(self, stream, root, positions, checks=None, owner=None):
+        """{position: row} from the (row, authentication path) pairs of a row commitment, in the order of `positions`; None as soon as
+        a row is not a list of num_registers + 1 elements of this field with values below p, a path is not log2 N digests of 64
+        bytes, or the path does not lead from the row's leaf to `root`.  checks: the path is recorded there (a row whose leaf digest
+        the host computed) instead of verified here."""
+        p, width, depth = self.field.p, self.num_registers + 1, self.fri.domain_length.bit_length() - 1
+        rows = {}
+        for position in positions:
+            row, path = stream.pull(), stream.pull()
+            if type(row) is not list or len(row) != width or not all(
+                    type(v) is FieldElement and type(v.value) is int and 0 <= v.value < p and getattr(v.field, "p", None) == p for v in row):
+                return None
+            if type(path) is not list or len(path) != depth or not all(type(d) is bytes and len(d) == 64 for d in path):
+                return None
+            if checks is not None:
+                checks.merkle(owner, root, position, path, None, leaf_digest=Merkle.row_leaf(row))
+            elif not (type(root) is bytes and Merkle.verify_rows(root, position, path, row)):
+                return None
+            rows[position] = row
+        return rows
 
     @staticmethod
     def _pull_openings(stream, root, positions):

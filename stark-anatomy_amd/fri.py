@@ -193,8 +193,9 @@ class BatchChecks:
             self.roots.append(root)
         return index
 
-    def merkle(self, owner, root, index, path, data_element):
-        """Merkle.verify(root, index, path, data_element) as a row"""
+    def merkle(self, owner, root, index, path, data_element, leaf_digest=None):
+        """Merkle.verify(root, index, path, data_element) as a row; leaf_digest (64 bytes, computed by the caller: a row commitment's
+        leaf, Merkle.row_leaf) stands in for the element's hash: Merkle.verify_(root, index, path, leaf_digest)"""
         r = self.root(root)
         try:
             joined = b"".join(path)
@@ -204,7 +205,11 @@ class BatchChecks:
         except Exception:
             device = False
         if device:
-            if type(data_element) is FieldElement and type(data_element.value) is int and 0 <= data_element.value < (1 << 128):
+            if leaf_digest is not None:
+                kind, leaf = _sc.LEAF_DIGEST, self.n_digests.to_bytes(16, "little")
+                self.digests.append(leaf_digest)
+                self.n_digests += 1
+            elif type(data_element) is FieldElement and type(data_element.value) is int and 0 <= data_element.value < (1 << 128):
                 kind, leaf = _sc.LEAF_RESIDUE, data_element.value.to_bytes(16, "little")
             else:
                 try:
@@ -226,7 +231,7 @@ class BatchChecks:
             self.n_digests += depth
             return
         try:
-            accepted = Merkle.verify(root, index, path, data_element)
+            accepted = Merkle.verify(root, index, path, data_element) if leaf_digest is None else Merkle.verify_(root, index, path, leaf_digest)
         except Exception:
             accepted = False
         if not accepted:

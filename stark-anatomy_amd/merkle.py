@@ -78,3 +78,45 @@ class Merkle:
 
     def verify(root, index, path, data_element):
         return Merkle.verify_(root, index, path, Merkle.H(bytes(data_element)).digest())
+
+    # ---- row commitments (not in the reference): ONE tree over the rows of a matrix of codewords.  Leaf i is the
+    # hash of every column's value at index i, personalised so that a leaf (a row of 8 values is 128 bytes) is never a node's hash;
+    # nodes are H(left || right) as above.  `columns`: w >= 1 equal-length sequences, lists of FieldElements or DeviceCodewords.
+    ROW_PERSON = b"sc-merkle-row"
+    ROWS_DEVICE_MIN = 256            # rows from which commit_rows / open_rows build the tree on the GPU (csrc/merkle_rows.cuh)
+
+    def row_leaf(row):
+        return blake2b(b"".join(v.value.to_bytes(16, "little") for v in row), person=Merkle.ROW_PERSON).digest()
+
+    def _rows(columns):
+        columns = list(columns)
+        assert(len(columns) >= 1), "a row tree needs at least one column"
+        n = len(columns[0])
+        assert(all(len(c) == n for c in columns)), "columns of one length"
+        assert(n >= 1 and n & (n - 1) == 0), "length must be power of two"
+        return columns, n
+
+    def _on_device(columns, n):
+        return any(isinstance(c, DeviceCodeword) for c in columns) or (n >= Merkle.ROWS_DEVICE_MIN and _sc.device_count() > 0)
+
+    def _row_leafs(columns):
+        return [Merkle.row_leaf(row) for row in zip(*columns)]
+
+    def commit_rows(columns):
+        columns, n = Merkle._rows(columns)
+        if Merkle._on_device(columns, n):
+            return _sc.RowTree.build(columns).root
+        return Merkle.commit_(Merkle._row_leafs(columns))
+
+    def open_rows(index, columns):
+        """(row, path): the columns' values at `index` and the authentication path of that row's leaf"""
+        columns, n = Merkle._rows(columns)
+        assert(0 <= index and index < n), "cannot open invalid index"
+        if Merkle._on_device(columns, n):
+            field = next(c.field for c in columns if isinstance(c, DeviceCodeword)) if any(isinstance(c, DeviceCodeword) for c in columns) else columns[0][0].field
+            rows, paths = _sc.RowTree.build(columns).query([index])
+            return [_sc._field_element()(v, field) for v in rows[0]], paths[0]
+        return [c[index] for c in columns], Merkle.open_(index, Merkle._row_leafs(columns))
+
+    def verify_rows(root, index, path, row):
+        return Merkle.verify_(root, index, path, Merkle.row_leaf(row))

@@ -293,6 +293,43 @@ class Openings:
         return [x for pair in zip(entries, paths) for x in pair]
 
 
+class RowOpenings:
+    """row, path, row, path, ... of a row commitment (fast_stark.FastStark(row_commitments=True)): per opened position
+    the list of every committed column's value there and ONE authentication path, as starkcore.RowTree.query_raw answered them.
+    codewords: the w committed DeviceCodewords, in column order; values: uint8 array of [k][w] residues (16 bytes each); paths: uint8
+    array [k][64 * depth].  An element is named by (its column's codeword, its index) like every other opened entry."""
+
+    def __init__(self, codewords, indices, values, paths):
+        self.holders, self.indices, self.values, self.paths = [entries_of(c) for c in codewords], list(indices), values, paths
+        self.count = 2 * len(self.indices)
+
+    def ops(self, ctx):
+        """per position: 'L' w, w 'E' records, one 'D' record (csrc/proof_pickle.h)"""
+        k, w = len(self.indices), len(self.holders)
+        if k == 0:
+            return b""
+        depth = self.paths.shape[1] // 64
+        rec = np.empty(k, dtype=np.dtype([("l", "u1"), ("n", "<u4"), ("e", _E, (w,)), ("p", _path_dtype(depth))]))
+        rec["l"], rec["n"] = ord("L"), w
+        elements = rec["e"]
+        elements["op"] = ord("E")
+        elements["f"] = np.asarray([ctx.field_index(h.field) for h in self.holders], dtype=np.uint32)
+        uids = np.asarray([ctx.uid(h) for h in self.holders], dtype=np.uint64)
+        elements["key"] = (uids[None, :] << np.uint64(32)) | np.asarray(self.indices, dtype=np.uint64)[:, None]
+        elements["v"] = np.frombuffer(self.values, dtype=np.uint8).reshape(k, w, 16)
+        rec["p"]["op"], rec["p"]["depth"] = ord("D"), depth
+        if depth:
+            rec["p"]["raw"] = self.paths
+        return rec.tobytes()
+
+    def materialize(self):
+        k, w = len(self.indices), len(self.holders)
+        ints = _sc.unpack(bytes(self.values), k * w)
+        columns = [h._entries(self.indices, ints[c::w]) for c, h in enumerate(self.holders)]
+        paths = _sc._path_lists(memoryview(np.ascontiguousarray(self.paths)).cast("B"), 0, self.paths.shape[1] // 64, k)
+        return [x for row, path in zip(zip(*columns), paths) for x in (list(row), path)]
+
+
 class _Real:
     """objects the caller pushed as objects"""
 

@@ -162,6 +162,10 @@ SIGNATURES = {
     "sc_fri_fold_slab_build_dev": (_int, [_vp, _u64, _u64, _u64, _u64, _vp, _vp, _vp, _vp, ctypes.POINTER(_vp), _vp]),
     "sc_merkle_leaves": (_u64, [_vp]),
     "sc_merkle_free": (_int, [_vp]),
+    "sc_merkle_rows_build_dev": (_int, [_vp, _u64, _u64, _vp, ctypes.POINTER(_vp), _vp]),
+    "sc_merkle_rows_build_async_dev": (_int, [_vp, _u64, _u64, ctypes.POINTER(_vp), _vp]),
+    "sc_merkle_rows_query_dev": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp]),
+    "sc_merkle_row_leaf": (_int, [_vp, _u64, _vp]),
     "sc_merkle_forest_build_dev": (_int, [_vp, _u64, _u64, ctypes.POINTER(_vp), _vp]),
     "sc_fri_fold_forest_dev": (_int, [_vp, _u64, _u64, _vp, _vp, _vp, _vp, ctypes.POINTER(_vp), _vp]),
     "sc_merkle_forest_roots": (_int, [_vp, _vp]),
@@ -967,6 +971,83 @@ class MerkleTree:
             self.free()
         except Exception:
             pass
+
+
+ROWS_MAX_COLUMNS = 256             # SC_MERKLE_ROWS_MAX_COLUMNS of include/starkcore.h
+
+
+class RowTree(MerkleTree):
+    """ONE Merkle tree over the rows of a matrix of codewords (csrc/merkle_rows.cuh): leaf i is the personalised hash
+    of every column's value at index i, so a position opens with one path whatever the width.  `columns`: w >= 1 DeviceCodewords,
+    DeviceVectors or host sequences (of FieldElements or ints; uploaded) of one power-of-two length.  The tree keeps its columns alive;
+    `root`, `open_batch`, `copy_level` and `free` are MerkleTree's."""
+
+    def __init__(self, handle, root, n, vectors):
+        super().__init__(handle, root, n)
+        self.vectors = vectors
+        self.width = len(vectors)
+        self._table = (_vp * self.width)(*[v.ptr for v in vectors])
+
+    @staticmethod
+    def _vectors(columns):
+        vectors = []
+        for column in columns:
+            if isinstance(column, DeviceCodeword):
+                vectors.append(column.vec)
+            elif isinstance(column, DeviceVector):
+                vectors.append(column)
+            else:
+                vectors.append(DeviceVector.from_ints([int(getattr(x, "value", x)) for x in column]))
+        assert 1 <= len(vectors) <= ROWS_MAX_COLUMNS, "a row tree takes 1 .. %d columns" % ROWS_MAX_COLUMNS
+        n = vectors[0].n
+        assert all(v.n == n for v in vectors), "columns of one length"
+        assert n >= 1 and n & (n - 1) == 0, "length must be power of two"
+        return vectors
+
+    @classmethod
+    def build(cls, columns):
+        vectors = cls._vectors(columns)
+        tree = cls(_vp(), None, vectors[0].n, vectors)
+        root = ctypes.create_string_buffer(64)
+        _check(lib().sc_merkle_rows_build_dev(tree._table, tree.width, tree.n, root, ctypes.byref(tree._h), None))
+        tree._root = root.raw
+        return tree
+
+    @classmethod
+    def start(cls, columns):
+        """the build is enqueued, not waited for: `.root` waits (proof_objects.RootLater)"""
+        vectors = cls._vectors(columns)
+        tree = cls(_vp(), None, vectors[0].n, vectors)
+        _check(lib().sc_merkle_rows_build_async_dev(tree._table, tree.width, tree.n, ctypes.byref(tree._h), None))
+        return tree
+
+    def query_raw(self, indices):
+        """the answers of `query` as the kernel wrote them, into pinned memory of the library's pool: (values, paths) -- uint8 arrays
+        of the [k][w] residues (16 bytes each) and of [k][64 * depth] path bytes; the arrays keep the memory alive"""
+        k, w, d = len(indices), self.width, self.depth
+        for i in indices:
+            assert 0 <= i < self.n, "cannot open invalid index"
+        self.root                                           # (an asynchronous build has finished once its root is here)
+        idx = (ctypes.c_uint64 * max(k, 1))(*[int(i) for i in indices])
+        row_bytes = (16 * k * w + 255) & ~255
+        out = HostBuffer(row_bytes + max(64 * d * k, 64))
+        if k:
+            _check(lib().sc_merkle_rows_query_dev(self._h, self._table, w, idx, k, out.ptr, _vp(out.ptr.value + row_bytes)))
+        return out.array[:16 * k * w], out.array[row_bytes:row_bytes + 64 * d * k].reshape(k, 64 * d)
+
+    def query(self, indices):
+        """(rows, paths) for `indices` in one launch: rows[i] = the w residues (ints) at indices[i], paths[i] its authentication path"""
+        k, w = len(indices), self.width
+        if k == 0:
+            return [], []
+        raw, paths = self.query_raw(indices)
+        values = unpack(raw.tobytes(), k * w)
+        return [values[i * w:(i + 1) * w] for i in range(k)], _path_lists(memoryview(paths).cast("B"), 0, self.depth, k)
+
+    def free(self):
+        if self._h is not None and not self._h.value:
+            self._h = None                                  # (a build that was refused left no tree)
+        super().free()
 
 
 class CodewordMatrix:
