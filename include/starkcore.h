@@ -861,6 +861,36 @@ int sc_merkle_forest_query_dev(uint64_t n_pairs, const sc_merkle_forest_t* const
                                const uint64_t* counts, void* elems_out, uint8_t* paths_out);
 int sc_merkle_forest_stats(uint64_t out[2]);   /* forests built and trees in them since sc_init */
 
+/* ---- Row forests: `count` row commitments (above) of N rows and w columns each in one set of launches ---------- */
+/* Tree t is the row tree of its own w columns: leaf i = the personalised row hash of sc_merkle_rows_build_dev over tree t's values at
+ * row i, nodes as everywhere; root t = the root sc_merkle_rows_build_dev gives for those columns.  In a batch the columns are not
+ * count * w allocations but the columns of a few matrices, so they are described by n_segs (1 .. SC_ROW_FOREST_MAX_SEGMENTS)
+ * SEGMENTS, a HOST array that travels as a kernel argument: segment s is a device matrix of count * per_tree columns, consecutive
+ * columns `pitch` elements (>= N) apart, and tree t's columns are, segment after segment, columns t * per_tree .. t * per_tree +
+ * per_tree - 1 of that segment.  Column c of tree t at row i lies at base_s + 16 * ((t * per_tree_s + (c - first_s)) * pitch_s + i),
+ * first_s = the columns of the segments in front; w = the sum of per_tree, 1 .. SC_MERKLE_ROWS_MAX_COLUMNS.  (The batched prover:
+ * the boundary-quotient codewords [K R][N] with per_tree R, then the randomizer codewords [K][N] with per_tree 1.)  The values are
+ * hashed as they lie in memory.
+ * build_dev:  only enqueues, on the caller's stream.  The result is an ordinary sc_merkle_forest_t (tree-major, all levels kept):
+ *             sc_merkle_forest_roots / _trees / _leaves / _free / _stats work on it unchanged, and "forest_four_lane_wgs" applies as to
+ *             every forest.  No shared scratch, the table is a kernel argument and the forest the call's own allocation: the build
+ *             is free of the one-stream rule -- the segments must be complete on `stream`, and builds on different streams do not
+ *             disturb one another.  One lane per row; level 0 is the entry of the forest's first launch (csrc/merkle_forest.cuh).
+ * query_dev:  for k positions (trees[q], indices[q]), the w values of each row (rows_out: [k][w], 16 bytes each) and its path
+ *             (paths_out: 64 * log2 N bytes per position) in ONE launch on the library stream; synchronous.  segs, n_segs: what the
+ *             forest was built from; a build on another stream is ordered in front of the launch on the device.  Outputs inside a
+ *             buffer of sc_host_alloc are written by the kernel itself; other host memory is served through the shared staging
+ *             scratch, so queries keep the one-stream rule like sc_merkle_rows_query_dev.  k == 0: SC_OK.
+ * A refused call enqueues nothing, writes nothing and leaves sc_merkle_forest_stats unchanged.  SC_ERR_BAD_ARG: a NULL table, handle
+ * or needed output, n_segs 0 or > SC_ROW_FOREST_MAX_SEGMENTS, a NULL base, per_tree 0, w > SC_MERKLE_ROWS_MAX_COLUMNS, pitch < N,
+ * N < 2, count 0, a tree >= count, an index >= N; SC_ERR_NOT_POW2: N no power of two (as the row tree); SC_ERR_UNSUPPORTED:
+ * count * N > SC_FOREST_MAX_LEAVES (split the batch). */
+#define SC_ROW_FOREST_MAX_SEGMENTS 8
+typedef struct { const void* base; uint64_t per_tree; uint64_t pitch; } sc_row_segment_t;   /* pitch: elements between consecutive columns, >= N */
+int sc_merkle_row_forest_build_dev(const sc_row_segment_t* segs, uint64_t n_segs, uint64_t N, uint64_t count, sc_merkle_forest_t** forest, void* stream);
+int sc_merkle_row_forest_query_dev(const sc_merkle_forest_t* forest, const sc_row_segment_t* segs, uint64_t n_segs, const uint64_t* trees, const uint64_t* indices,
+                                   uint64_t k, void* rows_out, uint8_t* paths_out);
+
 #ifdef __cplusplus
 }
 #endif

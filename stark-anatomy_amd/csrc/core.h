@@ -38,7 +38,7 @@
 #pragma GCC visibility pop
 #include "ntt_plan.h"
 
-namespace sc { struct FoldIn; }          // merkle.cuh (its kernels belong to merkle_fri.hip alone)
+namespace sc { struct FoldIn; struct ForestFold; }          // merkle.cuh, merkle_forest.cuh (their kernels belong to merkle_fri.hip alone)
 using namespace sc;
 
 struct sc_vec {
@@ -262,6 +262,15 @@ int root_slot_get();
 using LeafStage = std::function<void(uint64_t* levels, uint64_t N, int nlev, bool four_lane, hipStream_t st)>;
 int merkle_build_device(const Fe* d_elems, uint64_t N, uint8_t root_out[64], sc_merkle** tree, hipStream_t st, BuildMode mode = BUILD_SYNC, const FoldIn* fold = nullptr,
                         const LeafStage* leaves = nullptr);
+// The same for a forest (merkle_rows.hip: a forest whose leaves are rows): called once by forest_build to enqueue the launch that starts
+// at level 0 -- `wgs` workgroups of forest_climb_kernel<true, four_lane, false, Rows>, which climb nlev levels and, when that reaches
+// the roots, write them to `roots` (else NULL).  forest_args: the shape rules every forest entry shares (N a power of two >= min_n,
+// count >= 1, count * N <= SC_FOREST_MAX_LEAVES).  Callers hold g_mu.
+using ForestLeafStage = std::function<void(uint64_t* levels, uint64_t N, uint64_t count, int nlev, bool four_lane, unsigned wgs, uint64_t* roots, hipStream_t st)>;
+int forest_build(const Fe* d_elems, uint64_t N, uint64_t count, const ForestFold* fold, const std::vector<Fe>* cm, sc_merkle_forest** out, hipStream_t st,
+                 const ForestLeafStage* leaves = nullptr);
+int forest_args(uint64_t N, uint64_t count, uint64_t min_n);
+int wait_polled(std::unique_lock<std::mutex>* lk, hipEvent_t ev);
 int merkle_root_wait(sc_merkle* t, bool from_free = false);
 void root_poll_unlocked(std::unique_lock<std::mutex>& lk, const sc_merkle* t);
 int fold_prepare(const Fe* d_in, uint64_t N, Fe alpha, Fe offset, Fe omega, Fe* d_out, hipStream_t st, FoldIn* f);

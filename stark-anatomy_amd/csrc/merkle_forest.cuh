@@ -16,6 +16,10 @@
 //   fold     the leaf stage may compute its leaves as the split-and-fold of fri.py:85 of the previous round's matrix [count][2N], as
 //            merkle_subtree_kernel's FoldIn does, with ONE challenge per tree: c_m = alpha_t / (2 offset) is read from a device array
 //            [count]; the power table of omega^-1 is the forest's.  The element is fold_element's, bit for bit.
+//   rows     the leaf stage may instead hash ROWS (csrc/merkle_rows.cuh: a row forest, tree t = the row commitment of its own w columns,
+//            which lie in a few matrices described by segments): the Rows template parameter, as merkle_subtree_kernel has one.  Only
+//            level 0 differs -- h comes from row_leaf_walk over the one-lane compression, no LDS is used before the climb -- and the
+//            tree is the LANE's (trees of fewer than 256 rows share a workgroup); everything above is the same code.
 //
 // The indexing is written as SC_HD functions so that tests/emu/merkle_forest_emu.cpp runs the same numbering on the host.
 #pragma once
@@ -113,10 +117,12 @@ __device__ __forceinline__ void forest_level_4lane(const uint64_t* src, uint64_t
 // LEAVES: the launch starts at level 0 and hashes the residues (FOLD: computes them first); else it reads its 256 nodes from the forest.
 // FOUR_LANE: a launch of few workgroups (latency-bound): from 128 nodes per workgroup down, four lanes per compression.
 // roots_out (optional, may be pinned host memory): the launch that reaches the roots also writes them there, 64 bytes per tree.
-template <bool LEAVES, bool FOUR_LANE, bool FOLD>
+// Rows (with LEAVES): another leaf stage altogether -- rows.leaf(tree, i, h) hashes row i of tree `tree` into h (csrc/merkle_rows.cuh:
+// RowForestColumns, a ROW forest); the default, NoRows, is the decimal leaf of one residue and leaves every instantiation as it was.
+template <bool LEAVES, bool FOUR_LANE, bool FOLD, class Rows = NoRows>
 __global__ void __launch_bounds__(256) forest_climb_kernel(const Fe* __restrict__ elems, uint64_t* __restrict__ levels, const ForestShape s, int lvl0, int nlev,
-                                                           const ForestFold fold, uint64_t* roots_out) {
-    __shared__ uint4 cur[LEAVES ? 256 * 5 : 256 * 4];   // this level's digests (16 KiB); before that, the leaf stage's 80 bytes per thread
+                                                           const ForestFold fold, uint64_t* roots_out, const Rows rows = Rows()) {
+    __shared__ uint4 cur[(LEAVES && !Rows::on) ? 256 * 5 : 256 * 4];   // this level's digests (16 KiB); before that, the decimal leaf stage's 80 bytes per thread
     constexpr bool four_lane = FOUR_LANE && (SC_MERKLE_4LANE != 0);
     constexpr uint32_t FOUR_LANE_FROM = SC_FOUR_LANE_FROM;
     __shared__ uint64_t linA[four_lane ? (SC_FOUR_LANE_FROM / 2) * 17 : 1], linB[four_lane ? (SC_FOUR_LANE_FROM / 4) * 17 : 1];
@@ -128,7 +134,13 @@ __global__ void __launch_bounds__(256) forest_climb_kernel(const Fe* __restrict_
         const uint64_t flat = forest_wg_flat(wg, 0, t);
         const bool there = forest_place(s, lvl0, flat, &dig, &tree);
         entry_prio(true);
-        if (LEAVES) {
+        if constexpr (LEAVES && Rows::on) {
+            // the tree is the lane's own (trees of fewer than 256 rows share a workgroup); a lane past the last tree loads nothing
+#pragma unroll
+            for (int k = 0; k < 8; ++k) h[k] = 0;
+            if (there) rows.leaf(tree, flat & (s.N - 1), h);      // (lowers the entry priority behind each block's loads)
+            entry_prio(false);
+        } else if (LEAVES) {
             uint64_t m[16];
             Fe e = Fe{0, 0};
             if (there) {
@@ -214,6 +226,7 @@ __global__ void __launch_bounds__(256) forest_climb_kernel(const Fe* __restrict_
     }
 }
 
+#ifndef SC_MERKLE_NO_KERNELS      // (merkle.cuh: a translation unit that wants the kernel templates only -- merkle_rows.hip's row forests)
 // the forest form of merkle_query_multi_kernel: opening q of the launch is (trees[q], indices[q]) in the pair its number falls into
 __global__ void __launch_bounds__(256) forest_query_kernel(const ForestQuery Q, const uint64_t* __restrict__ trees, const uint64_t* __restrict__ indices,
                                                            Fe* __restrict__ elems_out, uint64_t* __restrict__ paths_out) {
@@ -234,6 +247,7 @@ __global__ void __launch_bounds__(256) forest_query_kernel(const ForestQuery Q, 
         o[quarter] = src[quarter];
     }
 }
+#endif  // SC_MERKLE_NO_KERNELS
 
 #endif  // __HIPCC__
 

@@ -1432,7 +1432,9 @@ int sc_merkle_free(sc_merkle_t* tree) {
 // caller (Fri.prove_batch: every member has its own proof stream).
 namespace {
 uint64_t g_forests = 0, g_forest_trees = 0;      // sc_merkle_forest_stats
+}  // namespace
 
+namespace sci {
 // wait for an event by polling (a blocking wait that has gone to sleep costs tens of microseconds to wake up); lk: the library lock
 // to release meanwhile (not while a kernel in flight reads the shared scratch buffers)
 int wait_polled(std::unique_lock<std::mutex>* lk, hipEvent_t ev) {
@@ -1444,7 +1446,9 @@ int wait_polled(std::unique_lock<std::mutex>* lk, hipEvent_t ev) {
     if (e != hipSuccess) { (void)hipGetLastError(); return fail(SC_ERR_HIP, hipGetErrorString(e)); }
     return SC_OK;
 }
+}  // namespace sci
 
+namespace {
 template <bool LEAVES, bool FOLD>
 void launch_climb(bool four_lane, unsigned wgs, hipStream_t st, const Fe* elems, uint64_t* levels, const ForestShape& s, int lvl0, int nlev, const ForestFold& fold,
                   uint64_t* roots) {
@@ -1460,10 +1464,14 @@ void forest_release(sc_merkle_forest* f) {
     if (f->done) g_event_pool.push_back(f->done);
     delete f;
 }
+}  // namespace
 
+namespace sci {
 // the launches of a forest over d_elems [count][N] (fold: the leaves are computed into d_elems = fold->out first); N >= 1 here
 // (a fold of two-element codewords leaves trees of one leaf).  alphas_cm: the fold's per-tree constants, staged behind the roots.
-int forest_build(const Fe* d_elems, uint64_t N, uint64_t count, const ForestFold* fold, const std::vector<Fe>* cm, sc_merkle_forest** out, hipStream_t st) {
+// leaves: another leaf stage (core.h ForestLeafStage: a row forest's), which enqueues the launch that starts at level 0.
+int forest_build(const Fe* d_elems, uint64_t N, uint64_t count, const ForestFold* fold, const std::vector<Fe>* cm, sc_merkle_forest** out, hipStream_t st,
+                 const ForestLeafStage* leaves) {
     sc_merkle_forest* f = new sc_merkle_forest{nullptr, N, count, ilog2(N)};
     f->st = st;
     const size_t tree_bytes = count * 2 * N * 64;
@@ -1493,7 +1501,8 @@ int forest_build(const Fe* d_elems, uint64_t N, uint64_t count, const ForestFold
         // chain at ~1.6 x the instructions, which pays only while the launch leaves the machine's SIMDs idle
         const bool four = nlev >= 2 && wgs <= (uint64_t)g.forest_four_lane_wgs;
         uint64_t* roots = lvl + nlev == s.logN ? f->h_roots : nullptr;
-        if (lvl == 0 && fold) launch_climb<true, true>(four, (unsigned)wgs, st, d_elems, f->d_levels, s, lvl, nlev, ff, roots);
+        if (lvl == 0 && leaves) (*leaves)(f->d_levels, N, count, nlev, four, (unsigned)wgs, roots, st);
+        else if (lvl == 0 && fold) launch_climb<true, true>(four, (unsigned)wgs, st, d_elems, f->d_levels, s, lvl, nlev, ff, roots);
         else if (lvl == 0) launch_climb<true, false>(four, (unsigned)wgs, st, d_elems, f->d_levels, s, lvl, nlev, ff, roots);
         else launch_climb<false, false>(four, (unsigned)wgs, st, d_elems, f->d_levels, s, lvl, nlev, ff, roots);
         lvl += nlev;
@@ -1513,7 +1522,7 @@ int forest_args(uint64_t N, uint64_t count, uint64_t min_n) {
     if (count > SC_FOREST_MAX_LEAVES / N) return fail(SC_ERR_UNSUPPORTED, "forest larger than SC_FOREST_MAX_LEAVES leaves: split the batch");
     return SC_OK;
 }
-}  // namespace
+}  // namespace sci
 
 extern "C" {
 

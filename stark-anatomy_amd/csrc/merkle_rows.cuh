@@ -12,6 +12,7 @@
 // one-lane rounds of merkle.cuh, sc_merkle_row_leaf and tests/emu/merkle_rows_emu.cpp with transcript.h's blake2b_compress.
 #pragma once
 #include "merkle.cuh"
+#include "merkle_forest.cuh"
 
 namespace sc {
 
@@ -52,6 +53,40 @@ SC_HD void row_leaf_walk(uint32_t w, Source source, Compress compress, uint64_t 
         compress(h, m, last ? 16ull * w : 128ull * (b + 1), last);
     }
 }
+
+// ---- row FORESTS: `count` row trees of N rows and w columns each, built by forest_climb_kernel (csrc/merkle_forest.cuh) with the row
+// leaf stage above.  In a batch the columns are not count * w allocations: they are the columns of a few matrices (the prover's: the
+// boundary-quotient LDE matrix [K R][N] and the randomizer LDE matrix [K][N]), so they are described by up to ROW_FOREST_MAX_SEGMENTS
+// SEGMENTS instead of a pointer each.  Segment s is a matrix of count * per_tree[s] columns, `pitch` >= N elements apart; tree t's
+// columns are, segment after segment, columns t * per_tree .. t * per_tree + per_tree - 1 of that segment:
+//     column c of tree t at row i  =  base_s[(t * per_tree_s + (c - first_s)) * pitch_s + i],     first_s = per_tree_0 + .. + per_tree_{s-1}
+// w = sum of per_tree, 1 <= w <= 256.  The lookup is written once, for the kernels and tests/emu/row_forest_emu.cpp.
+constexpr uint32_t ROW_FOREST_MAX_SEGMENTS = 8;     // SC_ROW_FOREST_MAX_SEGMENTS of include/starkcore.h
+struct RowSegment {                                  // sc_row_segment_t
+    const Fe* base;
+    uint64_t per_tree;
+    uint64_t pitch;
+};
+struct RowSegments {
+    RowSegment seg[ROW_FOREST_MAX_SEGMENTS];
+    uint32_t n, w;
+};
+// the segment that holds column c, reached from the segment of an earlier column (a row is walked in column order)
+struct RowSegmentCursor { uint32_t s = 0, first = 0; };
+SC_HD void row_segment_seek(const RowSegments& S, uint32_t c, RowSegmentCursor& k) {
+    while (c >= k.first + (uint32_t)S.seg[k.s].per_tree) {          // (c < w: ends inside the table)
+        k.first += (uint32_t)S.seg[k.s].per_tree;
+        ++k.s;
+    }
+}
+SC_HD uint64_t row_segment_element(const RowSegment& g, uint64_t tree, uint32_t column, uint64_t i) { return (tree * g.per_tree + column) * g.pitch + i; }
+SC_HD const Fe* row_segment_address(const RowSegments& S, uint64_t tree, uint32_t c, uint64_t i, RowSegmentCursor& k) {
+    row_segment_seek(S, c, k);
+    const RowSegment& g = S.seg[k.s];
+    return g.base + row_segment_element(g, tree, c - k.first, i);
+}
+// threads per opened position of row_forest_query_kernel: one per value, one per 16-byte quarter of a path digest
+SC_HD uint64_t row_forest_query_threads(uint32_t w, uint32_t logN) { return (uint64_t)w + 4ull * logN; }
 
 #if defined(__HIPCC__)
 
@@ -104,6 +139,49 @@ __global__ void __launch_bounds__(256) merkle_rows_query_kernel(const RowColumns
         const uint64_t off = (l == 0) ? 0 : (2 * N - (N >> (l - 1)));
         const uint64_t node = (idx >> l) ^ 1ull;
         const ulonglong2* s = reinterpret_cast<const ulonglong2*>(levels + 8 * (off + node));
+        ulonglong2* o = reinterpret_cast<ulonglong2*>(paths_out + 8 * (q * (uint64_t)logN + l));
+        o[quarter] = s[quarter];
+    }
+}
+
+// The segments of a row forest as a kernel argument (forest_climb_kernel's Rows parameter): the table is wave-uniform and read by
+// scalar loads from the kernel-argument segment, the SEGMENT of a column is wave-uniform (columns are walked in step), the TREE is the
+// lane's own -- trees of fewer than 256 rows share a workgroup -- so the address is computed per lane.  Lane (tree, row) reads 16
+// contiguous bytes per column; the lanes of one tree are coalesced.
+struct RowForestColumns {
+    static constexpr bool on = true;
+    RowSegments S;
+
+    struct Source {
+        const RowSegments& S;
+        uint64_t tree, row;
+        RowSegmentCursor k;
+        __device__ __forceinline__ void gate(bool on) const { entry_prio(on); }
+        __device__ __forceinline__ Fe at(uint32_t c) { return *row_segment_address(S, tree, c, row, k); }
+    };
+    __device__ __forceinline__ void leaf(uint64_t tree, uint64_t row, uint64_t h[8]) const {
+        row_leaf_walk(S.w, Source{S, tree, row, RowSegmentCursor{}}, RowColumns::Compress{}, h);
+    }
+};
+
+// k opened rows of a row forest in one launch: per position (trees[q], indices[q]) its w values (rows_out [k][w], 16 bytes each) and its
+// authentication path (paths_out, 64 * logN bytes per position, digest l at forest_path_digest).  One thread per value and per 16-byte
+// quarter of a digest.
+__global__ void __launch_bounds__(256) row_forest_query_kernel(const RowSegments S, const uint64_t* __restrict__ levels, uint64_t N, int logN,
+                                                               const uint64_t* __restrict__ trees, const uint64_t* __restrict__ indices, uint64_t k,
+                                                               Fe* __restrict__ rows_out, uint64_t* __restrict__ paths_out) {
+    const uint64_t per = row_forest_query_threads(S.w, (uint32_t)logN);
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= k * per) return;
+    const uint64_t q = t / per;
+    const uint32_t r = (uint32_t)(t % per);
+    const uint64_t tree = trees[q], idx = indices[q];
+    if (r < S.w) {
+        RowSegmentCursor cur;
+        rows_out[q * S.w + r] = *row_segment_address(S, tree, r, idx, cur);
+    } else {
+        const uint32_t quarter = (r - S.w) & 3u, l = (r - S.w) >> 2;
+        const ulonglong2* s = reinterpret_cast<const ulonglong2*>(levels + 8 * forest_path_digest(N, tree, idx, l));
         ulonglong2* o = reinterpret_cast<ulonglong2*>(paths_out + 8 * (q * (uint64_t)logN + l));
         o[quarter] = s[quarter];
     }

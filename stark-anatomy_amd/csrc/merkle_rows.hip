@@ -1,6 +1,8 @@
 // merkle_rows.hip -- row commitments (csrc/merkle_rows.cuh): one Merkle tree over the rows of a matrix of codewords
 // whose columns are separate device vectors.  The tree is an ordinary sc_merkle_t: the climb above the leaf stage, the root's way to
-// the host and everything that reads a tree are merkle_fri.hip's.
+// the host and everything that reads a tree are merkle_fri.hip's.  Row FORESTS (count such trees in one set of launches, the columns
+// described by segments): the leaf stage of merkle_fri.hip's forest_build and a query kernel of their own; the result is an ordinary
+// sc_merkle_forest_t.
 #define SC_MERKLE_NO_KERNELS
 #include "core.h"
 #include "merkle_rows.cuh"
@@ -34,9 +36,91 @@ int rows_build(const void* const* d_cols, uint64_t w, uint64_t N, uint8_t root_o
     return merkle_build_device(nullptr, N, root_out, tree, st, mode, nullptr, &leaves);
 }
 
+// ---- row forests: the checks of both entries, and the segment table as the kernels take it
+int row_forest_table(const char* what, const sc_row_segment_t* segs, uint64_t n_segs, uint64_t N, RowSegments& S) {
+    if (!segs) return fail(SC_ERR_BAD_ARG, std::string(what) + ": null argument");
+    if (n_segs == 0 || n_segs > SC_ROW_FOREST_MAX_SEGMENTS) return fail(SC_ERR_BAD_ARG, std::string(what) + ": 1 .. 8 segments");
+    uint64_t w = 0;
+    for (uint64_t s = 0; s < ROW_FOREST_MAX_SEGMENTS; ++s) {
+        if (s >= n_segs) { S.seg[s] = RowSegment{nullptr, 0, 0}; continue; }
+        if (!segs[s].base) return fail(SC_ERR_BAD_ARG, std::string(what) + ": null segment");
+        if (segs[s].per_tree == 0 || segs[s].per_tree > SC_MERKLE_ROWS_MAX_COLUMNS || (w += segs[s].per_tree) > SC_MERKLE_ROWS_MAX_COLUMNS)
+            return fail(SC_ERR_BAD_ARG, std::string(what) + ": 1 .. 256 columns per tree");
+        if (segs[s].pitch < N) return fail(SC_ERR_BAD_ARG, std::string(what) + ": a segment's pitch is at least N");
+        S.seg[s] = RowSegment{(const Fe*)segs[s].base, segs[s].per_tree, segs[s].pitch};
+    }
+    S.n = (uint32_t)n_segs;
+    S.w = (uint32_t)w;
+    return SC_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int sc_merkle_row_forest_build_dev(const sc_row_segment_t* segs, uint64_t n_segs, uint64_t N, uint64_t count, sc_merkle_forest_t** forest, void* stream) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    if (!forest) return fail(SC_ERR_BAD_ARG, "sc_merkle_row_forest_build_dev: null argument");
+    if (N >= 2 && !is_pow2(N)) return fail(SC_ERR_NOT_POW2, "length must be power of two");
+    RowForestColumns C;
+    SCCHK(row_forest_table("sc_merkle_row_forest_build_dev", segs, n_segs, N, C.S));
+    SCCHK(forest_args(N, count, 2));
+    // the leaf stage of forest_build: the launch that starts at level 0 hashes rows; the launches above it are the decimal forests'
+    const ForestLeafStage leaves = [&C](uint64_t* levels, uint64_t n, uint64_t trees, int nlev, bool four_lane, unsigned wgs, uint64_t* roots, hipStream_t s) {
+        const ForestShape shape{n, trees, ilog2(n)};
+        if (four_lane) hipLaunchKernelGGL((forest_climb_kernel<true, true, false, RowForestColumns>), dim3(wgs), dim3(256), 0, s, (const Fe*)nullptr, levels, shape, 0, nlev, ForestFold{}, roots, C);
+        else hipLaunchKernelGGL((forest_climb_kernel<true, false, false, RowForestColumns>), dim3(wgs), dim3(256), 0, s, (const Fe*)nullptr, levels, shape, 0, nlev, ForestFold{}, roots, C);
+    };
+    return forest_build(nullptr, N, count, nullptr, nullptr, forest, pick_stream(stream), &leaves);
+}
+
+int sc_merkle_row_forest_query_dev(const sc_merkle_forest_t* forest, const sc_row_segment_t* segs, uint64_t n_segs, const uint64_t* trees, const uint64_t* indices, uint64_t k,
+                                   void* rows_out, uint8_t* paths_out) {
+    std::unique_lock<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    if (!forest) return fail(SC_ERR_BAD_ARG, "sc_merkle_row_forest_query_dev: null argument");
+    RowSegments S;
+    SCCHK(row_forest_table("sc_merkle_row_forest_query_dev", segs, n_segs, forest->N, S));
+    if (k && (!trees || !indices || !rows_out || !paths_out)) return fail(SC_ERR_BAD_ARG, "sc_merkle_row_forest_query_dev: null argument");
+    for (uint64_t i = 0; i < k; ++i)
+        if (trees[i] >= forest->count || indices[i] >= forest->N) return fail(SC_ERR_BAD_ARG, "cannot open invalid index");
+    if (k == 0) return SC_OK;
+    hipStream_t st = g.stream;
+    if (!forest->have_roots && forest->st != st) HIPCHK(hipStreamWaitEvent(st, forest->done, 0));     // built on another stream: ordered in front of the gather
+    const uint64_t w = S.w;
+    const size_t idx_bytes = (k * 8 + 255) & ~255ull;
+    const size_t row_bytes = k * w * sizeof(Fe), path_bytes = k * 64 * (size_t)forest->logN;
+    // a buffer of sc_host_alloc is written by the kernel itself (the stores cross the bus as they are made); any other host pointer
+    // is served through device scratch and a copy
+    const bool rows_direct = host_pool_holds(rows_out, row_bytes), paths_direct = host_pool_holds(paths_out, path_bytes);
+    const size_t row_stage = rows_direct ? 0 : (row_bytes + 255) & ~255ull, path_stage = paths_direct ? 0 : path_bytes;
+    void* buf;
+    SCCHK(scratch(5, 2 * idx_bytes + row_stage + path_stage + 256, &buf));
+    uint64_t* d_trees = (uint64_t*)buf;
+    uint64_t* d_idx = (uint64_t*)((char*)buf + idx_bytes);
+    Fe* d_rows = rows_direct ? (Fe*)rows_out : (Fe*)((char*)buf + 2 * idx_bytes);
+    uint64_t* d_paths = paths_direct ? (uint64_t*)paths_out : (uint64_t*)((char*)buf + 2 * idx_bytes + row_stage);
+    SCCHK(upload(d_trees, trees, k * 8, st));
+    SCCHK(upload(d_idx, indices, k * 8, st));
+    const uint64_t total = k * row_forest_query_threads((uint32_t)w, (uint32_t)forest->logN);
+    hipLaunchKernelGGL(row_forest_query_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, S, (const uint64_t*)forest->d_levels, forest->N, forest->logN,
+                       (const uint64_t*)d_trees, (const uint64_t*)d_idx, k, d_rows, d_paths);
+    HIPCHK(hipGetLastError());
+    if (!rows_direct) HIPCHK(hipMemcpyAsync(rows_out, d_rows, row_bytes, hipMemcpyDeviceToHost, st));
+    if (!paths_direct) HIPCHK(hipMemcpyAsync(paths_out, d_paths, path_bytes, hipMemcpyDeviceToHost, st));
+    if (rows_direct && paths_direct) {                     // nothing but the kernel's own stores to wait for: poll, as sc_merkle_forest_query_dev does
+        hipEvent_t ev = event_get();
+        if (ev) {
+            hipError_t e = hipEventRecord(ev, st);
+            int rc = e == hipSuccess ? wait_polled(nullptr, ev) : fail(SC_ERR_HIP, hipGetErrorString(e));
+            g_event_pool.push_back(ev);
+            return rc;
+        }
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    return SC_OK;
+}
 
 int sc_merkle_rows_build_dev(const void* const* d_cols, uint64_t w, uint64_t N, uint8_t root_out[64], sc_merkle_t** tree, void* stream) {
     std::lock_guard<std::mutex> lk(g_mu);

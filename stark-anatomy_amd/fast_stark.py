@@ -131,7 +131,8 @@ class FastStark:
         row_commitments (not in the reference; False = the reference's protocol, byte for byte): the boundary-quotient codewords and the
         randomizer codeword are committed in ONE Merkle tree over their rows (Merkle.commit_rows) -- one root in front of
         FRI's objects, and per opened position one row of num_registers + 1 values and ONE authentication path -- instead of a tree, a
-        root and a path each.  No challenge lies between those commitments, so nothing else of the protocol moves."""
+        root and a path each.  No challenge lies between those commitments, so nothing else of the protocol moves.  prove_batch serves
+        the option too: the members' row trees are one row forest (starkcore.RowForest, _rows_batch_served)."""
         assert(field.p.bit_length() >= security_level), "p must have at least as many bits as security level"
         assert(expansion_factor & (expansion_factor - 1) == 0), "expansion factor must be a power of 2"
         assert(expansion_factor >= 4), "expansion factor must be 4 or greater"
@@ -500,8 +501,20 @@ class FastStark:
         """does prove_batch serve this batch with the members' work done together?  Decided from shapes alone, before any draw:
         the main field, traces of one length (long enough for the device data flow) and of one column per register, boundaries that
         name the same (cycle, register) pairs, an FRI shape the forest path serves, and a member's codewords within one forest"""
-        if self.field.p != Field.P_MAIN or self.row_commitments:
-            return False                                 # (row commitments: no batched row forests yet, members go one by one)
+        if self.row_commitments:
+            return False                                 # (served by the per-codeword forests; a row-committed batch: _rows_batch_served)
+        return self._batch_shapes_served(traces, boundaries)
+
+    def _rows_batch_served(self, traces, boundaries):
+        """_batch_served for a prover with row_commitments: the same shape rules, and a row of R boundary quotients and the randomizer
+        within a row tree's width.  Such a batch commits every member's codewords in ONE row forest (starkcore.RowForest)."""
+        if not self.row_commitments or self.num_registers + 1 > _sc.ROWS_MAX_COLUMNS:
+            return False
+        return self._batch_shapes_served(traces, boundaries)
+
+    def _batch_shapes_served(self, traces, boundaries):
+        if self.field.p != Field.P_MAIN:
+            return False
         rows = len(traces[0])
         if any(len(trace) != rows for trace in traces) or rows < 1 or rows + self.num_randomizers < FastStark.DEVICE_MIN:
             return False
@@ -525,10 +538,13 @@ class FastStark:
         K R columns of one matrix (sc_randomized_columns_dev: one launch copies the traces and samples the randomizer rows), and
         interpolation, the boundary quotients, the LDEs, the AIR, the nonlinear combination and FRI are one call each for all members
         (fast_interpolate_columns_device, combine_columns_device, coset_divide_columns_device, transition_quotients_batch,
-        Fri.prove_batch with AlsoOpenForests); every commitment is a Merkle forest.  traces[m]: a DeviceTrace or the reference's list of
+        Fri.prove_batch with AlsoOpenForests); every commitment is a Merkle forest -- with row_commitments ONE row forest of K trees
+        over the boundary-quotient and randomizer matrices (starkcore.RowForest) in place of the forests of those codewords, its rows
+        opened by one launch behind FRI's.  traces[m]: a DeviceTrace or the reference's list of
         rows; proof_streams None: fresh ProofStreams.  The draws are made first, in the order of K sequential `prove` calls (per member
         num_randomizers * num_registers draws for the randomizer rows, then max_degree + 1 for the randomizer polynomial); with the
-        operating system's os.urandom they are ONE os.urandom call.  A batch whose shape is not served (_batch_served) goes member by
+        operating system's os.urandom they are ONE os.urandom call.  A batch whose shape is not served (_batch_served, or
+        _rows_batch_served with row_commitments) goes member by
         member through `prove`, before any draw.  A false witness raises what `prove` raises for the lowest-numbered failing member; no
         proofs are returned, and every stream then holds a prefix of what `prove` would have pushed.  COLUMN_BATCH_MIN is not consulted:
         K R columns always form a matrix."""
@@ -538,7 +554,7 @@ class FastStark:
         if not traces:
             return []
         proof_streams = [ProofStream() if stream is None else stream for stream in proof_streams]
-        if not self._batch_served(traces, boundaries):
+        if not (self._batch_served(traces, boundaries) or self._rows_batch_served(traces, boundaries)):
             return [self.prove(trace, transition_constraints, boundary, transition_zerofier, transition_zerofier_codeword, stream)
                     for trace, boundary, stream in zip(traces, boundaries, proof_streams)]
         K, R = len(traces), self.num_registers
@@ -618,26 +634,40 @@ class FastStark:
                                                           self.omicron_domain_length, exact=True, later=pending) for c in range(cols)]
             self._mark("boundary quotients (division)")
 
-            # commitments: one forest over the K R boundary-quotient codewords, one over the K randomizer codewords, the zerofier's own
-            bq_forest = _sc.MerkleForest.build(self._lde_matrix(boundary_quotients))
+            # commitments: one forest over the K R boundary-quotient codewords, one over the K randomizer codewords, the zerofier's own;
+            # with row_commitments ONE row forest of K trees over both matrices, built behind the randomizer's LDE
+            rows_on = self.row_commitments
+            bq_matrix = self._lde_matrix(boundary_quotients)
+            bq_forest = None if rows_on else _sc.MerkleForest.build(bq_matrix)
             self._mark("boundary quotient LDEs + commitments")
             x = DevicePolynomial.from_polynomial(Polynomial([field.zero(), field.one()]), field)
             points = [[x] + trace_polynomials[m * R:(m + 1) * R] + [tp.scaled_later(self.omicron) for tp in trace_polynomials[m * R:(m + 1) * R]] for m in range(K)]
             transition_quotients = self.transition_quotients_batch(transition_constraints, points, transition_zerofier, pending)
             self._mark("AIR substitution + transition quotients (value domain)")
-            randomizer_forest = _sc.MerkleForest.build(self._lde_matrix(randomizer_polynomials))
+            randomizer_matrix = self._lde_matrix(randomizer_polynomials)
+            if rows_on:
+                # tree m: the rows of [member m's R boundary-quotient codewords, its randomizer codeword] -- prove's row tree
+                row_forest = _sc.RowForest.build([(bq_matrix, R), (randomizer_matrix, 1)], N, K)
+            else:
+                randomizer_forest = _sc.MerkleForest.build(randomizer_matrix)
             zerofier_forest = self._zerofier_forest(transition_zerofier_codeword)
             self._mark("randomizer polynomial: LDE, commitment")
 
             # per member: the commitments, the collected checks (once: they speak for the whole chunk), the weights, the degree check
             tq_bounds = self.transition_quotient_degree_bounds(transition_constraints)
             bq_bounds = self.boundary_quotient_degree_bounds(trace_rows, boundaries[0])
-            bq_roots, randomizer_roots = bq_forest.roots, randomizer_forest.roots
+            if rows_on:
+                row_roots = row_forest.roots
+            else:
+                bq_roots, randomizer_roots = bq_forest.roots, randomizer_forest.roots
             weights = []
             for m, stream in enumerate(streams):
-                for s in range(R):
-                    stream.push(bq_roots[m * R + s])
-                stream.push(randomizer_roots[m])
+                if rows_on:
+                    stream.push(row_roots[m])            # (one root, where prove pushes its row tree's)
+                else:
+                    for s in range(R):
+                        stream.push(bq_roots[m * R + s])
+                    stream.push(randomizer_roots[m])
                 checks, pending = pending, []
                 _collect_verdicts(checks)
                 weights.append(self.sample_weights(1 + 2 * len(transition_quotients[m]) + 2 * R, stream.prover_fiat_shamir()))
@@ -658,16 +688,29 @@ class FastStark:
         self._mark("weights, degree checks, nonlinear combination + its LDE")
 
         # FRI on all members; the committed codewords' openings travel in the launch that fetches the FRI openings
-        owners = [[list(range(m * R, (m + 1) * R)) for m in range(K)], [[m] for m in range(K)], [[0] for _ in range(K)]]
-        also = AlsoOpenForests([bq_forest, randomizer_forest, zerofier_forest], owners, shift=self.expansion_factor)
+        if rows_on:
+            # (the rows open from the row forest, in a launch of their own behind FRI's: below)
+            also = AlsoOpenForests([zerofier_forest], [[[0]] * K], shift=self.expansion_factor)
+        else:
+            owners = [[list(range(m * R, (m + 1) * R)) for m in range(K)], [[m] for m in range(K)], [[0] for _ in range(K)]]
+            also = AlsoOpenForests([bq_forest, randomizer_forest, zerofier_forest], owners, shift=self.expansion_factor)
         self.fri.prove_batch(combined_codewords, streams, also_open=also)
         self._mark("FRI: commit + query phases, openings fetched with them")
+
+        if rows_on:
+            # every member's rows at its positions in ONE launch; per member row, path, row, path, ... in front of the zerofier's openings
+            w, at = R + 1, 0
+            row_values, row_paths = row_forest.query_raw([(m, position) for m in range(K) for position in also.positions[m]])
+            for m, stream in enumerate(streams):
+                k = len(also.positions[m])
+                self._push_rows(stream, also.positions[m], row_values[16 * w * at:16 * w * (at + k)], row_paths[at:at + k], w)
+                at += k
 
         # openings in `committed` order; entries are made once per (member, codeword, index): the transcript is pickled by object identity
         proofs = []
         shared_elements = None if isinstance(transition_zerofier_codeword, DeviceCodeword) else list(transition_zerofier_codeword)
         for m, stream in enumerate(streams):
-            holders = [DeviceCodeword(None, field) for _ in range(R + 1)] + [DeviceCodeword(None, field, elements=shared_elements)]
+            holders = [DeviceCodeword(None, field) for _ in range(0 if rows_on else R + 1)] + [DeviceCodeword(None, field, elements=shared_elements)]
             for holder, (values, paths) in zip(holders, also.answers[m]):
                 self._push_openings(holder._entries(also.positions[m], values), paths, stream)
         self._mark("openings of the committed codewords")
@@ -1072,6 +1115,23 @@ class FastStark:
         for row, path in zip(rows, paths):
             proof_stream.push(row)
             proof_stream.push(path)
+
+    def _push_rows(self, proof_stream, indices, values, paths, width):
+        """_open_rows for one member of a row-committed batch, over its slice of RowForest.query_raw's answer (values: uint8 array of
+        [k][width] residues, paths: uint8 array [k][64 * depth]): the same pushes -- a description where the stream takes
+        descriptions (the columns were never Python objects: detached holders name them), else a list of FieldElements and a list of
+        digests per position"""
+        field = self.field
+        lazy = _po.lazy_objects(proof_stream)
+        if lazy is not None:
+            lazy.add(_po.RowOpenings([_po.DetachedEntries(field) for _ in range(width)], indices, values, paths))
+            return
+        k = len(indices)
+        ints = _sc.unpack(values.tobytes(), k * width)
+        digests = _sc._path_lists(memoryview(paths.tobytes()), 0, paths.shape[1] // 64, k)
+        for j in range(k):
+            proof_stream.push([FieldElement(v, field) for v in ints[j * width:(j + 1) * width]])
+            proof_stream.push(digests[j])
 
     @staticmethod
     def _push_openings(entries, paths, proof_stream):

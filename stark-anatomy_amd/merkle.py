@@ -108,6 +108,26 @@ class Merkle:
             return _sc.RowTree.build(columns).root
         return Merkle.commit_(Merkle._row_leafs(columns))
 
+    def commit_rows_batch(members):
+        """[Merkle.commit_rows(columns) for columns in members] -- as ONE row forest (starkcore.RowForest: one set of launches and one
+        wait for all the roots) when every member has the same number of columns and the same power-of-two length (at least two rows)
+        and the whole batch has at least ROWS_DEVICE_MIN rows: the members' columns become the columns of one device matrix (columns
+        that are not on the device are uploaded into it), tree t over columns t w ... t w + w - 1.  A batch above the library's forest
+        limit is split; any other batch goes member by member."""
+        members = [Merkle._rows(columns) for columns in members]
+        if not members:
+            return []
+        w, n = len(members[0][0]), members[0][1]
+        alike = all(len(columns) == w and length == n for columns, length in members)
+        if not alike or n < 2 or w > _sc.ROWS_MAX_COLUMNS or len(members) * n < Merkle.ROWS_DEVICE_MIN or _sc.device_count() == 0:
+            return [Merkle.commit_rows(columns) for columns, _ in members]
+        roots, step = [], max(1, _sc.FOREST_MAX_LEAVES // n)
+        for lo in range(0, len(members), step):
+            part = members[lo:lo + step]
+            matrix = CodewordMatrix.from_members([column for columns, _ in part for column in columns])
+            roots += _sc.RowForest.build([(matrix, w)], n, len(part)).roots
+        return roots
+
     def open_rows(index, columns):
         """(row, path): the columns' values at `index` and the authentication path of that row's leaf"""
         columns, n = Merkle._rows(columns)

@@ -174,6 +174,8 @@ SIGNATURES = {
     "sc_merkle_forest_free": (_int, [_vp]),
     "sc_merkle_forest_query_dev": (_int, [_u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sc_merkle_forest_stats": (_int, [_vp]),
+    "sc_merkle_row_forest_build_dev": (_int, [_vp, _u64, _u64, _u64, ctypes.POINTER(_vp), _vp]),
+    "sc_merkle_row_forest_query_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp]),
     "sc_mpoly_eval_dev": (_int, [_vp, _u64, _u64, _vp, _vp, _u64, _vp, _vp]),
     "sc_mpoly_eval_ex_dev": (_int, [_vp, _u64, _u64, _vp, _vp, _u64, _vp, _int, _vp]),
     "sc_mpoly_eval_rot_dev": (_int, [_vp, _u64, _u64, _vp, _vp, _u64, _vp, _int, _vp, _vp, _vp]),
@@ -1130,6 +1132,88 @@ class MerkleForest:
 
     def free(self):
         if self._h is not None and _lib is not None:
+            _lib.sc_merkle_forest_free(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+ROW_FOREST_MAX_SEGMENTS = 8        # SC_ROW_FOREST_MAX_SEGMENTS of include/starkcore.h
+
+
+class RowSegment(ctypes.Structure):
+    """sc_row_segment_t"""
+    _fields_ = [("base", _vp), ("per_tree", _u64), ("pitch", _u64)]
+
+
+class RowForest:
+    """Owner of an sc_merkle_forest_t whose leaves are ROWS (csrc/merkle_rows.cuh): `count` row trees of n rows each,
+    built by one set of launches.  segments: [(matrix, per_tree) or (matrix, per_tree, pitch)] -- `matrix` a DeviceVector or
+    CodewordMatrix of count * per_tree columns, consecutive columns `pitch` (default n) elements apart; tree t's columns are, segment
+    after segment, columns t * per_tree ... of that segment.  The forest keeps its matrices alive.  `roots` waits for the build (once)."""
+
+    def __init__(self, handle, matrices, table, n, count):
+        self._h, self.matrices, self._table = handle, matrices, table
+        self.n, self.count = int(n), int(count)
+        self.width = sum(int(segment.per_tree) for segment in table)
+        self.depth = self.n.bit_length() - 1
+        self._roots = None
+
+    @classmethod
+    def build(cls, segments, n, count):
+        segments = [tuple(segment) for segment in segments]
+        assert 1 <= len(segments) <= ROW_FOREST_MAX_SEGMENTS, "a row forest takes 1 .. %d segments" % ROW_FOREST_MAX_SEGMENTS
+        table = (RowSegment * len(segments))()
+        matrices = []
+        for entry, (matrix, per_tree, *pitch) in zip(table, segments):
+            vec = matrix.vec if isinstance(matrix, CodewordMatrix) else matrix
+            pitch = n if not pitch or pitch[0] is None else int(pitch[0])
+            assert per_tree >= 1 and pitch >= n and vec.n >= (count * per_tree - 1) * pitch + n, "a segment holds count * per_tree columns of n rows"
+            entry.base, entry.per_tree, entry.pitch = vec.ptr, int(per_tree), pitch
+            matrices.append(matrix)
+        forest = cls(_vp(), matrices, table, n, count)
+        assert forest.width <= ROWS_MAX_COLUMNS, "a row tree takes 1 .. %d columns" % ROWS_MAX_COLUMNS
+        _check(lib().sc_merkle_row_forest_build_dev(table, len(table), n, count, ctypes.byref(forest._h), None))
+        return forest
+
+    @property
+    def roots(self):
+        if self._roots is None:
+            out = ctypes.create_string_buffer(64 * self.count)
+            _check(lib().sc_merkle_forest_roots(self._h, out))
+            raw = out.raw
+            self._roots = [raw[64 * t:64 * t + 64] for t in range(self.count)]
+        return self._roots
+
+    def query_raw(self, positions):
+        """the answers of `query` as the kernel wrote them, into pinned memory of the library's pool: (values, paths) -- uint8 arrays
+        of the [k][w] residues (16 bytes each) and of [k][64 * depth] path bytes; the arrays keep the memory alive"""
+        k, w, d = len(positions), self.width, self.depth
+        for tree, index in positions:
+            assert 0 <= tree < self.count and 0 <= index < self.n, "cannot open invalid index"
+        trees = (ctypes.c_uint64 * max(k, 1))(*[int(t) for t, _ in positions])
+        idx = (ctypes.c_uint64 * max(k, 1))(*[int(i) for _, i in positions])
+        row_bytes = (16 * k * w + 255) & ~255
+        out = HostBuffer(row_bytes + max(64 * d * k, 64))
+        if k:
+            _check(lib().sc_merkle_row_forest_query_dev(self._h, self._table, len(self._table), trees, idx, k, out.ptr, _vp(out.ptr.value + row_bytes)))
+        return out.array[:16 * k * w], out.array[row_bytes:row_bytes + 64 * d * k].reshape(k, 64 * d)
+
+    def query(self, positions):
+        """(rows, paths) for positions [(tree, index)] in one launch: rows[i] = the w residues (ints) of that row, paths[i] its path"""
+        k, w = len(positions), self.width
+        if k == 0:
+            return [], []
+        raw, paths = self.query_raw(positions)
+        values = unpack(raw.tobytes(), k * w)
+        return [values[i * w:(i + 1) * w] for i in range(k)], _path_lists(memoryview(paths).cast("B"), 0, self.depth, k)
+
+    def free(self):
+        if self._h is not None and self._h.value and _lib is not None:
             _lib.sc_merkle_forest_free(self._h)
         self._h = None
 
