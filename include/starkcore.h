@@ -831,6 +831,27 @@ int sc_merkle_rows_build_async_dev(const void* const* d_cols, uint64_t w, uint64
 int sc_merkle_rows_query_dev(const sc_merkle_t* tree, const void* const* d_cols, uint64_t w, const uint64_t* indices, uint64_t k, void* rows_out, uint8_t* paths_out);
 int sc_merkle_row_leaf(const void* row, uint64_t w, uint8_t out[64]);   /* host only */
 
+/* ---- pair leaves for FRI (not in the reference; Fri(pair_leaves=True)) ------------------------------------------------ */
+/* A round's codeword cw of n >= 2 elements is committed as the row tree of its two halves: n/2 leaves, leaf i = the row leaf of
+ * (cw[i], cw[i + n/2]) -- sc_merkle_rows_build*_dev on the two pointers {cw, cw + n/2} builds it, and the tree is an ordinary sc_merkle_t.
+ * fold_pairs_commit_dev: the pair twin of sc_fri_fold_commit_dev, one round of the commit phase in one call, enqueue only: the fold of
+ *             fri.py:85 of d_in (N elements, N a power of two >= 4) into d_out (N/2 elements, bit for bit what sc_fri_fold_dev writes)
+ *             and the asynchronous build of the pair tree over d_out (N/4 leaves).  From 256 leaves up the leaf stage of the tree
+ *             computes the fold itself: a lane folds both members of its pair, stores them and hashes them out of registers.  No shared
+ *             scratch: free of the one-stream rule, like sc_fri_fold_commit_dev.  sc_merkle_root waits for the root.
+ * pairs_query_dev: every opening of a proof's query phase in ONE launch on the library stream; synchronous.  Codeword j: 2 L_j elements
+ *             at d_codewords[j] under the pair tree trees[j] of L_j leaves; counts[j] of the concatenated `indices` belong to it.  Opening
+ *             i of codeword j writes the pair {cw[a], cw[a + L_j]} (32 bytes) to pairs_out and the 64 * log2 L_j bytes of leaf a's path to
+ *             paths_out, both packed codeword after codeword in the order of `indices`.  A tree that was only enqueued is waited for.
+ *             Outputs inside a buffer of sc_host_alloc are written by the kernel itself; other host memory is served through the shared
+ *             staging scratch (the one-stream rule of sc_merkle_query_multi_dev).  n == 0 or all counts 0: SC_OK.
+ * SC_ERR_BAD_ARG, with nothing enqueued and nothing written: a NULL handle, codeword, table or needed output, an index >= L_j;
+ * SC_ERR_NOT_POW2: N no power of two, or below 4. */
+int sc_fri_fold_pairs_commit_dev(const void* d_in, uint64_t N, const uint64_t alpha[2], const uint64_t offset[2], const uint64_t omega[2], void* d_out,
+                                 sc_merkle_t** tree, void* stream);
+int sc_fri_pairs_query_dev(uint64_t n, const sc_merkle_t* const* trees, const void* const* d_codewords, const uint64_t* indices, const uint64_t* counts,
+                           void* pairs_out, uint8_t* paths_out);
+
 /* ---- Merkle forests: Merkle.commit (merkle.py:13-14) of `count` arrays of N leaves each in one set of launches ------------------ */
 /* d_elems: a device matrix [count][N] of residues, row t = the leaves of tree t; N a power of two >= 2, count >= 1.  All levels of all
  * trees are kept (tree-major, csrc/merkle_forest.cuh).  The largest forest an entry takes has SC_FOREST_MAX_LEAVES leaves in total

@@ -2,10 +2,12 @@
 // whose columns are separate device vectors.  The tree is an ordinary sc_merkle_t: the climb above the leaf stage, the root's way to
 // the host and everything that reads a tree are merkle_fri.hip's.  Row FORESTS (count such trees in one set of launches, the columns
 // described by segments): the leaf stage of merkle_fri.hip's forest_build and a query kernel of their own; the result is an ordinary
-// sc_merkle_forest_t.
+// sc_merkle_forest_t.  Pair leaves for FRI (csrc/fri_pairs.cuh) live here too: a round's codeword under the row tree of
+// its two halves, built by the row stage above or, behind a fold, by a leaf stage that computes the fold itself.
 #define SC_MERKLE_NO_KERNELS
 #include "core.h"
 #include "merkle_rows.cuh"
+#include "fri_pairs.cuh"
 #include "transcript.h"
 
 namespace {
@@ -165,6 +167,101 @@ int sc_merkle_rows_query_dev(const sc_merkle_t* tree, const void* const* d_cols,
                        (const uint64_t*)d_idx, k, d_rows, d_paths);
     HIPCHK(hipGetLastError());
     if (!rows_direct) HIPCHK(hipMemcpyAsync(rows_out, d_rows, row_bytes, hipMemcpyDeviceToHost, g.stream));
+    if (!paths_direct) HIPCHK(hipMemcpyAsync(paths_out, d_paths, path_bytes, hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+    return SC_OK;
+}
+
+// ---- pair leaves for FRI (csrc/fri_pairs.cuh): a round's codeword under the row tree of its two halves
+// one round of the commit phase with pair leaves: the fold of d_in (N elements) into d_out (N/2) and the pair tree over d_out (N/4
+// leaves), enqueued.  From 256 leaves up the leaf stage of the tree computes the fold (PairFold); below, the fold kernel and the plain
+// row leaf launch over {d_out, d_out + N/4}.
+int sc_fri_fold_pairs_commit_dev(const void* d_in, uint64_t N, const uint64_t alpha[2], const uint64_t offset[2], const uint64_t omega[2], void* d_out,
+                                 sc_merkle_t** tree, void* stream) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    if (!tree || !d_in || !d_out || !alpha || !offset || !omega) return fail(SC_ERR_BAD_ARG, "sc_fri_fold_pairs_commit_dev: null argument");
+    if (N < 4 || !is_pow2(N)) return fail(SC_ERR_NOT_POW2, "sc_fri_fold_pairs_commit_dev: codeword length must be a power of two >= 4");
+    hipStream_t st = pick_stream(stream);
+    const uint64_t q = N / 4;
+    if (q < 256) {
+        SCCHK(fold_device((const Fe*)d_in, N, fe_from(alpha), fe_from(offset), fe_from(omega), (Fe*)d_out, st));
+        const void* halves[2] = {d_out, (const Fe*)d_out + q};
+        return rows_build(halves, 2, q, nullptr, tree, st, BUILD_ASYNC);
+    }
+    PairFold P;
+    SCCHK(fold_prepare((const Fe*)d_in, N, fe_from(alpha), fe_from(offset), fe_from(omega), (Fe*)d_out, st, &P.f));
+    P.q = q;
+    // the launch plan of the row stage (rows_build): nlev levels of every 256-leaf subtree behind the leaves, four lanes per hash on
+    // the narrow levels of a latency-bound launch
+    const LeafStage leaves = [&P](uint64_t* levels, uint64_t n, int nlev, bool four_lane, hipStream_t s) {
+        if (four_lane) hipLaunchKernelGGL((merkle_subtree_kernel<true, true, false, PairFold>), dim3((unsigned)(n / 256)), dim3(256), 0, s, (const Fe*)nullptr, levels, n, 0, nlev, FoldIn(), P);
+        else hipLaunchKernelGGL((merkle_subtree_kernel<true, false, false, PairFold>), dim3((unsigned)(n / 256)), dim3(256), 0, s, (const Fe*)nullptr, levels, n, 0, nlev, FoldIn(), P);
+    };
+    return merkle_build_device(nullptr, q, nullptr, tree, st, BUILD_ASYNC, nullptr, &leaves);
+}
+
+// every opening of a proof's query phase in one launch: codeword j = 2 L_j elements at d_codewords[j] under the pair tree trees[j] of
+// L_j leaves; counts[j] of the concatenated `indices` belong to it; per opening the pair (32 bytes) and the path (64 * log2 L_j bytes),
+// packed codeword after codeword
+int sc_fri_pairs_query_dev(uint64_t n, const sc_merkle_t* const* trees, const void* const* d_codewords, const uint64_t* indices, const uint64_t* counts,
+                           void* pairs_out, uint8_t* paths_out) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    SCCHK(ensure_init());
+    if (n == 0) return SC_OK;
+    if (!trees || !d_codewords || !counts) return fail(SC_ERR_BAD_ARG, "sc_fri_pairs_query_dev: null argument");
+    uint64_t total = 0;
+    size_t path_bytes = 0;
+    for (uint64_t t = 0; t < n; ++t) {
+        if (!trees[t] || !d_codewords[t]) return fail(SC_ERR_BAD_ARG, "sc_fri_pairs_query_dev: null tree or codeword");
+        if (counts[t] && !indices) return fail(SC_ERR_BAD_ARG, "sc_fri_pairs_query_dev: null argument");
+        for (uint64_t i = 0; i < counts[t]; ++i) if (indices[total + i] >= trees[t]->N) return fail(SC_ERR_BAD_ARG, "cannot open invalid index");
+        total += counts[t];
+        path_bytes += counts[t] * 64 * (size_t)trees[t]->logN;
+    }
+    if (total == 0) return SC_OK;
+    if (!pairs_out || (path_bytes && !paths_out)) return fail(SC_ERR_BAD_ARG, "sc_fri_pairs_query_dev: null argument");
+    // a tree that was only enqueued (on whatever stream) is complete once its root has landed
+    for (uint64_t t = 0; t < n; ++t)
+        if (counts[t] && !trees[t]->have_root) SCCHK(merkle_root_wait(const_cast<sc_merkle_t*>(trees[t])));
+    const size_t idx_bytes = (total * 8 + 255) & ~255ull;
+    const size_t pair_bytes = total * 2 * sizeof(Fe);
+    // a buffer of sc_host_alloc is written by the kernel itself; any other host pointer is served through device scratch and a copy
+    const bool pairs_direct = host_pool_holds(pairs_out, pair_bytes), paths_direct = !path_bytes || host_pool_holds(paths_out, path_bytes);
+    const size_t pair_stage = pairs_direct ? 0 : (pair_bytes + 255) & ~255ull, path_stage = paths_direct ? 0 : path_bytes;
+    void* buf;
+    SCCHK(scratch(5, idx_bytes + pair_stage + path_stage + 256, &buf));
+    uint64_t* d_idx = (uint64_t*)buf;
+    Fe* d_pairs = pairs_direct ? (Fe*)pairs_out : (Fe*)((char*)buf + idx_bytes);
+    uint64_t* d_paths = paths_direct ? (uint64_t*)paths_out : (uint64_t*)((char*)buf + idx_bytes + pair_stage);
+    SCCHK(upload(d_idx, indices, total * 8, g.stream));
+    // one launch per PAIRS_MAX_TREES codewords (a proof: one launch)
+    uint64_t off = 0, poff = 0;
+    for (uint64_t t0 = 0; t0 < n; t0 += PAIRS_MAX_TREES) {
+        PairTrees Q;
+        Q.count = 0;
+        Q.total_threads = 0;
+        for (uint64_t t = t0; t < n && t < t0 + PAIRS_MAX_TREES; ++t) {
+            const uint64_t k = counts[t];
+            if (!k) continue;
+            PairTree& T = Q.t[Q.count++];
+            T.levels = trees[t]->d_levels;
+            T.elems = (const Fe*)d_codewords[t];
+            T.L = trees[t]->N;
+            T.logL = (uint32_t)trees[t]->logN;
+            T.per_query = (uint32_t)pair_query_threads(T.logL);
+            T.thread_off = Q.total_threads;
+            T.idx_off = off;
+            T.path_off = poff;
+            Q.total_threads += k * T.per_query;
+            off += k;
+            poff += k * (uint64_t)trees[t]->logN;
+        }
+        if (!Q.count) continue;
+        hipLaunchKernelGGL(fri_pairs_query_kernel, dim3((unsigned)((Q.total_threads + 255) / 256)), dim3(256), 0, g.stream, Q, (const uint64_t*)d_idx, d_pairs, d_paths);
+    }
+    HIPCHK(hipGetLastError());
+    if (!pairs_direct) HIPCHK(hipMemcpyAsync(pairs_out, d_pairs, pair_bytes, hipMemcpyDeviceToHost, g.stream));
     if (!paths_direct) HIPCHK(hipMemcpyAsync(paths_out, d_paths, path_bytes, hipMemcpyDeviceToHost, g.stream));
     HIPCHK(hipStreamSynchronize(g.stream));
     return SC_OK;

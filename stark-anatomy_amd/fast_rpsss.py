@@ -41,10 +41,11 @@ class FastRPSSS:
     # sign: the trace from the Rescue-Prime kernel (True) or the host mirror (False); both give the same signature
     SIGN_ON_DEVICE = True
 
-    def __init__(self, num_colinearity_checks=64, grinding_bits=0, row_commitments=False):
+    def __init__(self, num_colinearity_checks=64, grinding_bits=0, row_commitments=False, pair_leaves=False):
         """the defaults are the reference's parameters; fewer colinearity checks with as many grinding bits as keep 2 * checks + bits
         at the security level of 128 (FastStark(grinding_bits), grinding.py) give shorter signatures for a proof of work per signature.
-        row_commitments: FastStark's option of the same name (one Merkle tree over the rows of the committed codewords), passed through"""
+        row_commitments: FastStark's option of the same name (one Merkle tree over the rows of the committed codewords), passed through
+        pair_leaves: FastStark's option of the same name (FRI opens one pair and one path per colinearity test), passed through"""
         self.field = Field.main()
         expansion_factor = 4
         security_level = 128
@@ -52,7 +53,7 @@ class FastRPSSS:
         num_cycles = self.rp.N + 1
         state_width = self.rp.m
         self.stark = FastStark(self.field, expansion_factor, num_colinearity_checks, security_level, state_width, num_cycles,
-                               transition_constraints_degree=3, grinding_bits=grinding_bits, row_commitments=row_commitments)
+                               transition_constraints_degree=3, grinding_bits=grinding_bits, row_commitments=row_commitments, pair_leaves=pair_leaves)
         self.transition_zerofier, self.transition_zerofier_codeword, self.transition_zerofier_root = self.stark.preprocess()
 
     def stark_prove(self, input_element, proof_stream):

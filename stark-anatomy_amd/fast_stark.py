@@ -125,14 +125,17 @@ def device_powers(base, count):
 
 class FastStark:
     def __init__(self, field, expansion_factor, num_colinearity_checks, security_level, num_registers, num_cycles, transition_constraints_degree=2, grinding_bits=0,
-                 row_commitments=False):
+                 row_commitments=False, pair_leaves=False):
         """grinding_bits (not in the reference; 0 = the reference's protocol): bits of proof of work on the transcript before FRI's
         query indices (grinding.py, Fri(grinding_bits)); each bit stands in for half a colinearity check in the security level.
         row_commitments (not in the reference; False = the reference's protocol, byte for byte): the boundary-quotient codewords and the
         randomizer codeword are committed in ONE Merkle tree over their rows (Merkle.commit_rows) -- one root in front of
         FRI's objects, and per opened position one row of num_registers + 1 values and ONE authentication path -- instead of a tree, a
         root and a path each.  No challenge lies between those commitments, so nothing else of the protocol moves.  prove_batch serves
-        the option too: the members' row trees are one row forest (starkcore.RowForest, _rows_batch_served)."""
+        the option too: the members' row trees are one row forest (starkcore.RowForest, _rows_batch_served).
+        pair_leaves (not in the reference; False = the reference's protocol, byte for byte): Fri's option of the same name (DESIGN.md
+        3.4e), passed through -- FRI's query phase carries one pair and one path per colinearity test.  It combines freely with the two
+        above and does not enter the security-level test; prove_batch then goes member by member (Fri._batchable)."""
         assert(field.p.bit_length() >= security_level), "p must have at least as many bits as security level"
         assert(expansion_factor & (expansion_factor - 1) == 0), "expansion factor must be a power of 2"
         assert(expansion_factor >= 4), "expansion factor must be 4 or greater"
@@ -144,6 +147,7 @@ class FastStark:
         self.expansion_factor, self.num_colinearity_checks = expansion_factor, num_colinearity_checks
         self.grinding_bits = grinding_bits
         self.row_commitments = bool(row_commitments)
+        self.pair_leaves = bool(pair_leaves)
         self.num_registers, self.original_trace_length = num_registers, num_cycles
         self.num_randomizers = 4 * num_colinearity_checks
         self.randomized_trace_length = num_cycles + self.num_randomizers
@@ -160,7 +164,7 @@ class FastStark:
         self._lifted = {}                 # id(host Polynomial) -> (the Polynomial, its DevicePolynomial): lifted once, not per proof
         self._zerofier_values = {}        # transform order -> (the transition zerofier, its values on that order's coset)
 
-        self.fri = Fri(self.generator, self.omega, self.fri_domain_length, expansion_factor, num_colinearity_checks, grinding_bits)
+        self.fri = Fri(self.generator, self.omega, self.fri_domain_length, expansion_factor, num_colinearity_checks, grinding_bits, pair_leaves=self.pair_leaves)
 
     @property
     def omicron_domain(self):

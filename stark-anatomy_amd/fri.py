@@ -341,15 +341,20 @@ class BatchChecks:
 
 
 class Fri:
-    def __init__(self, offset, omega, initial_domain_length, expansion_factor, num_colinearity_tests, grinding_bits=0):
+    def __init__(self, offset, omega, initial_domain_length, expansion_factor, num_colinearity_tests, grinding_bits=0, pair_leaves=False):
         """grinding_bits (not in the reference; 0 = the reference's protocol, byte for byte): a proof of work of that many bits on
         the transcript between the last codeword and the query indices (grinding.py) -- the prover pushes the smallest accepted
-        nonce, the verifier checks it, and the indices are sampled from the transcript with it"""
+        nonce, the verifier checks it, and the indices are sampled from the transcript with it
+        pair_leaves (not in the reference; False = the reference's protocol, byte for byte): every round's codeword
+        is committed under the tree of its pairs (Merkle.commit_pairs: leaf i holds cw[i] and cw[i + n/2]), so a colinearity test
+        carries the pair (y_a, y_b) and ONE path; y_c is never opened -- the verifier reads it from the next round's pair or from the
+        last codeword.  Same colinearity relation, same indices, same seeds."""
         self.offset, self.omega, self.field = offset, omega, omega.field
         self.domain_length = initial_domain_length
         self.expansion_factor, self.num_colinearity_tests = expansion_factor, num_colinearity_tests
         assert(type(grinding_bits) is int and 0 <= grinding_bits <= _grinding.MAX_BITS), "grinding_bits must be an integer of 0 .. %d" % _grinding.MAX_BITS
         self.grinding_bits = grinding_bits
+        self.pair_leaves = bool(pair_leaves)
         assert(self.num_rounds() >= 1), "cannot do FRI with less than one round"
 
     def num_rounds(self):
@@ -499,6 +504,8 @@ class Fri:
         """also_open (optional, an AlsoOpen): further device codewords to open at positions that depend on the sampled indices --
         FastStark's committed codewords (fast_stark.py:154-175) -- fetched in the SAME device round trip as the query phase"""
         assert(self.domain_length == len(codeword)), "initial codeword length does not match length of initial codeword"
+        if self.pair_leaves:
+            return self._prove_pairs(codeword, proof_stream, also_open)
         top_level_indices = self._prove_in_library(codeword, proof_stream, also_open)
         if top_level_indices is not None:
             return top_level_indices
@@ -527,6 +534,8 @@ class Fri:
         """what the forest path serves: the main field, at least two rounds (fri.py:122 reads codewords[1]), a power-of-two length,
         and members that are device codewords or sequences of residues below 2^128"""
         N, rounds, s = self.domain_length, self.num_rounds(), self.num_colinearity_tests
+        if self.pair_leaves:                                     # (pair forests are not built: member by member through `prove`)
+            return False
         if self.field.p != Field.P_MAIN or rounds < 2 or N < 2 or N & (N - 1) != 0 or s < 1 or s > (N >> (rounds - 1)):
             return False
         for cw in codewords:
@@ -792,6 +801,129 @@ class Fri:
                 for obj in triples + openings:
                     proof_stream.push(obj)
 
+    # -- pair leaves --------------------------------------------------------------------
+    def _prove_pairs(self, codeword, proof_stream, also_open=None):
+        """`prove` with pair_leaves: the round-by-round route of _commit_rounds over pair trees (round 0's tree is started first, then
+        per round one sc_fri_fold_pairs_commit_dev with the Fiat-Shamir step in Python, so any ProofStream subclass is served), the
+        last codeword in the clear, the proof of work, and a query phase of ONE device round trip (sc_fri_pairs_query_dev): per round
+        r < rounds - 1 the s pairs (cw_r[a], cw_r[a + half]), then the s paths of leaf a in cw_r's pair tree.  Nothing of cw_{r+1} is
+        pushed for round r.  also_open's openings travel in a call of their own."""
+        codeword = self._on_device(codeword)
+        rounds, s = self.num_rounds(), self.num_colinearity_tests
+        N = len(codeword)
+        assert(N & (N - 1) == 0 and (N >> (rounds - 1)) >= 2), "pair leaves need power-of-two codewords of at least two elements in every round"
+        self._check_omega_order(N)                             # (before anything is enqueued)
+        omega, offset = self.omega, self.offset
+        codewords = []
+        codeword.start_pair_tree()
+        for r in range(rounds):
+            folded = DeviceVector(len(codeword) // 2) if r < rounds - 1 else None
+            proof_stream.push(codeword.pair_tree().root)       # (waits for the device; the tree stays in HBM for the query phase)
+            if r == rounds - 1:
+                break
+            alpha = self.field.sample(proof_stream.prover_fiat_shamir())
+            codewords.append(codeword)
+            codeword = codeword.fold_pairs_commit(alpha, offset, omega, folded)
+            omega, offset = omega ^ 2, offset ^ 2
+        codewords.append(codeword)
+        proof_stream.push(codewords[-1].tolist())              # the last codeword in the clear
+        self.grind(proof_stream)
+        top_level_indices = self.sample_indices(proof_stream.prover_fiat_shamir(), N // 2, len(codewords[-1]), s)
+        requests = [[index % (N >> (r + 1)) for index in top_level_indices] for r in range(rounds - 1)]
+        for pairs, paths in _sc.query_pairs(codewords[:-1], requests):
+            for pair in pairs:
+                proof_stream.push(pair)
+            for path in paths:
+                proof_stream.push(path)
+        if also_open is not None:
+            more_codewords, more_requests = also_open.requests(top_level_indices)
+            also_open.answers = _sc.query_codewords_raw(list(more_codewords), list(more_requests))
+        return top_level_indices
+
+    def _pair_shape(self, pair):
+        """a pulled pair as two elements of the field below p, else None"""
+        if type(pair) not in (tuple, list) or len(pair) != 2:
+            return None
+        p = self.field.p
+        for y in pair:
+            if not (type(y) is FieldElement and type(y.value) is int and 0 <= y.value < p and getattr(y.field, "p", None) == p):
+                return None
+        return (pair[0], pair[1])
+
+    @staticmethod
+    def _path_shape(path, depth):
+        return type(path) in (list, tuple) and len(path) == depth and all(type(d) is bytes and len(d) == 64 for d in path)
+
+    def _verify_pairs(self, proof_stream, polynomial_values, checks=None, owner=None):
+        """`verify` with pair_leaves; with `checks` (a BatchChecks) the same walk with every path and colinearity test recorded as a row
+        for the batch's device calls instead of evaluated (a pair's path: a LEAF_DIGEST row over Merkle.row_leaf computed here; a
+        test: the existing 80-byte row with the y_c looked up here).  y_c of round r is never in the proof: it is the member of the
+        next round's pair at a % (half / 2) that lies at position a, or last_codeword[a] in the last queried round -- so all pairs
+        are pulled before the first test.  A pair that is not two field elements below p, or a path that is not log2(half) digests of
+        64 bytes, returns False before anything is appended to polynomial_values."""
+        rounds, s = self.num_rounds(), self.num_colinearity_tests
+        roots, alphas = [], []
+        for _ in range(rounds):
+            roots.append(proof_stream.pull())
+            alphas.append(self.field.sample(proof_stream.verifier_fiat_shamir()))
+        last_codeword = proof_stream.pull()
+        try:
+            well_formed = Merkle.commit_pairs(last_codeword) == roots[-1]
+        except Exception:
+            well_formed = False
+        if not well_formed:
+            return Fri._reject("last codeword is not well formed") if checks is None else False
+        squarings = 1 << (rounds - 1)
+        last_omega, last_offset = self.omega ^ squarings, self.offset ^ squarings
+        assert(last_omega.inverse() == last_omega ^ (len(last_codeword) - 1)), "omega does not have right order"
+        allowed = len(last_codeword) // self.expansion_factor - 1
+        observed = self._last_codeword_degree(last_codeword, last_omega, last_offset)
+        if observed > allowed:
+            return Fri._reject("last codeword does not correspond to polynomial of low enough degree", "observed degree: %s" % observed,
+                               "but should be: %s" % allowed) if checks is None else False
+        if not self._check_grinding(proof_stream):
+            return Fri._reject("proof of work fails") if checks is None else False
+        top_level_indices = self.sample_indices(proof_stream.verifier_fiat_shamir(), self.domain_length >> 1, self.domain_length >> (rounds - 1), s)
+        # everything the query phase holds, and its shape
+        pairs, paths = [], []
+        for r in range(rounds - 1):
+            depth = (self.domain_length >> (r + 1)).bit_length() - 1
+            pairs.append([self._pair_shape(proof_stream.pull()) for _ in range(s)])
+            paths.append([proof_stream.pull() for _ in range(s)])
+            if None in pairs[r]:
+                return Fri._reject("a pair is not two field elements") if checks is None else False
+            if not all(Fri._path_shape(path, depth) for path in paths[r]):
+                return Fri._reject("an authentication path has the wrong shape") if checks is None else False
+        omega, offset = self.omega, self.offset
+        for r in range(rounds - 1):
+            half = self.domain_length >> (r + 1)
+            lower = [index % half for index in top_level_indices]
+            if r + 2 < rounds:
+                y_c = [pairs[r + 1][t][0 if a < half // 2 else 1] for t, a in enumerate(lower)]
+            else:
+                y_c = [last_codeword[a] for a in lower]
+            if checks is not None:
+                round_index = checks.round(offset, omega, alphas[r])
+                refs = []
+                if r == 0:
+                    checks.truncate(polynomial_values, len(polynomial_values), refs)
+            for a, (ya, yb), yc in zip(lower, pairs[r], y_c):
+                b = a + half
+                if r == 0:
+                    polynomial_values += [(a, ya), (b, yb)]
+                # (x_a, y_a), (x_b, y_b) and (alpha, y_c) lie on one line: that is the fold of fri.py:85 read backwards
+                if checks is not None:
+                    refs.append(checks.colinearity(owner, round_index, offset, omega, a, b, alphas[r], ya, yb, yc))
+                elif not test_colinearity([(offset * (omega ^ a), ya), (offset * (omega ^ b), yb), (alphas[r], yc)]):
+                    return Fri._reject("colinearity check failure")
+            for a, pair, path in zip(lower, pairs[r], paths[r]):
+                if checks is not None:
+                    checks.merkle(owner, roots[r], a, path, None, leaf_digest=Merkle.row_leaf(pair))
+                elif not Merkle.verify_pair(roots[r], a, path, pair):
+                    return Fri._reject("merkle authentication path verification fails for a pair")
+            omega, offset = omega ^ 2, offset ^ 2
+        return True
+
     def _last_codeword_degree(self, last_codeword, last_omega, last_offset):
         """Degree of the interpolant of the last codeword on its coset: intt + unscale (the route the
         reference's fri.py:165-166 / docs describe) -- same unique polynomial as Lagrange at fri.py:164."""
@@ -807,6 +939,8 @@ class Fri:
         return False
 
     def verify(self, proof_stream, polynomial_values):
+        if self.pair_leaves:
+            return self._verify_pairs(proof_stream, polynomial_values)
         rounds, s = self.num_rounds(), self.num_colinearity_tests
         # the commit phase replayed: per round a root and the challenge it determines, then the last codeword in the clear
         roots, alphas = [], []
@@ -865,6 +999,8 @@ class Fri:
             checks.reject(owner)
 
     def _collect_checks(self, proof_stream, polynomial_values, checks, owner):
+        if self.pair_leaves:
+            return self._verify_pairs(proof_stream, polynomial_values, checks, owner)
         rounds, s = self.num_rounds(), self.num_colinearity_tests
         # the commit phase replayed: per round a root and the challenge it determines, then the last codeword in the clear
         roots, alphas = [], []

@@ -140,3 +140,28 @@ class Merkle:
 
     def verify_rows(root, index, path, row):
         return Merkle.verify_(root, index, path, Merkle.row_leaf(row))
+
+    # ---- pair leaves (not in the reference): a codeword of n >= 2 values under the row tree of its two halves -- n/2
+    # leaves, leaf i = row_leaf((cw[i], cw[i + n/2])) -- so the two points of a colinearity test of FRI open with one path.  Thin
+    # definitions over the row trees above; a DeviceCodeword is served without a copy (two pointers into the one vector).
+    def _pair_columns(codeword):
+        n = len(codeword)
+        assert(n >= 2 and n & (n - 1) == 0), "length must be a power of two of at least 2"
+        return [codeword[:n // 2], codeword[n // 2:]]
+
+    def commit_pairs(codeword):
+        if isinstance(codeword, DeviceCodeword):
+            return codeword.pair_tree().root
+        return Merkle.commit_rows(Merkle._pair_columns(codeword))
+
+    def open_pair(index, codeword):
+        """((y_a, y_b), path): the values at `index` and `index + n/2` and the authentication path of their leaf"""
+        if isinstance(codeword, DeviceCodeword):
+            assert(0 <= index and index < len(codeword) // 2), "cannot open invalid index"
+            (pairs, paths), = _sc.query_pairs([codeword], [[index]])
+            return pairs[0], paths[0]
+        row, path = Merkle.open_rows(index, Merkle._pair_columns(codeword))
+        return (row[0], row[1]), path
+
+    def verify_pair(root, index, path, pair):
+        return Merkle.verify_rows(root, index, path, list(pair))

@@ -255,6 +255,7 @@ class ShardedFri:
         adds to it, and on the HIP engine the rest of the commit phase is then ONE library call (0: only when one row is left)."""
         self.fri, self.R, self.rank, self.world, self.device, self.group = fri, int(R), rank, world, device, group
         assert(getattr(fri, "grinding_bits", 0) == 0), "the sharded provers do not grind: a Fri with grinding_bits > 0 proves on one GPU (Fri.prove / Fri.prove_batch)"
+        assert(not getattr(fri, "pair_leaves", False)), "the sharded provers commit every codeword element by element: a Fri with pair_leaves proves on one GPU (Fri.prove)"
         assert R % world == 0 and fri.domain_length % R == 0
         self.Rw = self.R // world
         self.engine = engine if engine is not None else HipFriEngine(device)

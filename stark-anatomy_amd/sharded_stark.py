@@ -140,8 +140,9 @@ class ShardedFastStark(FastStark):
     MIN_SHARDED_LOG2 = 10
 
     def __init__(self, field, expansion_factor, num_colinearity_checks, security_level, num_registers, num_cycles, rank, world, device, group=None,
-                 transition_constraints_degree=2, replicated_steps=None, row_commitments=False):
+                 transition_constraints_degree=2, replicated_steps=None, row_commitments=False, pair_leaves=False):
         assert not row_commitments, "the sharded prover commits every codeword in a tree of its own: row_commitments is not supported"
+        assert not pair_leaves, "the sharded prover commits every codeword element by element: pair_leaves is not supported"
         super().__init__(field, expansion_factor, num_colinearity_checks, security_level, num_registers, num_cycles, transition_constraints_degree)
         assert field.p == Field.P_MAIN, "the sharded prover works in the main field"
         self.rank, self.world, self.device, self.group = rank, world, device, group

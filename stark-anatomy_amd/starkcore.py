@@ -166,6 +166,8 @@ SIGNATURES = {
     "sc_merkle_rows_build_async_dev": (_int, [_vp, _u64, _u64, ctypes.POINTER(_vp), _vp]),
     "sc_merkle_rows_query_dev": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp]),
     "sc_merkle_row_leaf": (_int, [_vp, _u64, _vp]),
+    "sc_fri_fold_pairs_commit_dev": (_int, [_vp, _u64, _vp, _vp, _vp, _vp, ctypes.POINTER(_vp), _vp]),
+    "sc_fri_pairs_query_dev": (_int, [_u64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sc_merkle_forest_build_dev": (_int, [_vp, _u64, _u64, ctypes.POINTER(_vp), _vp]),
     "sc_fri_fold_forest_dev": (_int, [_vp, _u64, _u64, _vp, _vp, _vp, _vp, ctypes.POINTER(_vp), _vp]),
     "sc_merkle_forest_roots": (_int, [_vp, _vp]),
@@ -643,6 +645,40 @@ def combination_batch(shared, rows):
     if len(rows):
         _check(lib().sc_stark_combination_batch(ctypes.byref(shared.struct), rows.ctypes.data, len(rows), out.ctypes.data))
     return out
+
+
+def query_pairs(codewords, requests):
+    """The query phase of a proof with pair leaves (Fri(pair_leaves=True), csrc/fri_pairs.cuh) in ONE device round trip: requests[t] =
+    leaf numbers a < len(codewords[t]) / 2 of codewords[t]'s pair tree; returns [(pairs, paths)] in the same order -- pairs[i] =
+    (cw[a], cw[a + half]) as identity-preserving entries, paths[i] the fresh digests of leaf a's path.  The kernel writes into pinned
+    memory of the library's pool."""
+    n = len(codewords)
+    trees = [cw.pair_tree() for cw in codewords]
+    try:
+        flat = array.array("Q", itertools.chain.from_iterable(requests))  # (the upper bound is checked by the library)
+    except OverflowError:
+        raise AssertionError("cannot open invalid index")
+    total = len(flat)
+    if total == 0:
+        return [([], []) for _ in codewords]
+    depths = [t.depth for t in trees]
+    pair_bytes = (32 * total + 255) & ~255
+    path_bytes = sum(64 * d * len(req) for d, req in zip(depths, requests))
+    out = HostBuffer(pair_bytes + max(path_bytes, 64))
+    _check(lib().sc_fri_pairs_query_dev(n, (_vp * n)(*[t._h for t in trees]), (_vp * n)(*[cw.vec.ptr for cw in codewords]),
+                                        (ctypes.c_uint64 * total).from_buffer(flat), (ctypes.c_uint64 * n)(*[len(req) for req in requests]),
+                                        out.ptr, _vp(out.ptr.value + pair_bytes)))
+    values = unpack(out.array[:32 * total].tobytes(), 2 * total)
+    view = memoryview(out.array[pair_bytes:pair_bytes + path_bytes].tobytes())
+    answers, vo, po = [], 0, 0
+    for cw, req, d in zip(codewords, requests, depths):
+        k, half = len(req), cw.vec.n // 2
+        mine = values[2 * vo:2 * (vo + k)]
+        entries = cw._entries(list(req) + [a + half for a in req], mine[0::2] + mine[1::2])
+        answers.append((list(zip(entries[:k], entries[k:])), _path_lists(view, po, d, k)))
+        vo += k
+        po += 64 * k * d
+    return answers
 
 
 def query_codewords_raw(codewords, requests):
@@ -1373,6 +1409,35 @@ class DeviceCodeword(Sequence):
                                             out_vec.ptr, ctypes.byref(h), None))
         folded = DeviceCodeword(out_vec, self.field)
         folded._tree = MerkleTree(h, None, out_vec.n)
+        return folded
+
+    # -- pair leaves (Fri(pair_leaves=True)): the codeword under the row tree of its two halves
+    def _halves(self):
+        """the two halves as vectors over this codeword's memory: two pointers into the one vector, no copy"""
+        n = self.vec.n
+        assert n >= 2 and n & (n - 1) == 0, "a pair tree needs a power-of-two length of at least 2"
+        base = int(self.vec.ptr)
+        return [DeviceVector.wrap(base, n // 2, self.vec), DeviceVector.wrap(base + 8 * n, n // 2, self.vec)]
+
+    def pair_tree(self):
+        if getattr(self, "_pair_tree", None) is None:
+            self._pair_tree = RowTree.build(self._halves())
+        return self._pair_tree
+
+    def start_pair_tree(self):
+        """enqueue the build of the pair tree and return at once (`pair_tree().root` waits for it)"""
+        if getattr(self, "_pair_tree", None) is None:
+            self._pair_tree = RowTree.start(self._halves())
+        return self._pair_tree
+
+    def fold_pairs_commit(self, alpha, offset, omega, out_vec):
+        """fold_commit with pair leaves (sc_fri_fold_pairs_commit_dev): the folded DeviceCodeword, whose pair_tree().root waits for
+        the device"""
+        h = _vp()
+        _check(lib().sc_fri_fold_pairs_commit_dev(self.vec.ptr, self.vec.n, fe_bytes(alpha.value), fe_bytes(offset.value), fe_bytes(omega.value),
+                                                  out_vec.ptr, ctypes.byref(h), None))
+        folded = DeviceCodeword(out_vec, self.field)
+        folded._pair_tree = MerkleTree(h, None, out_vec.n // 2)
         return folded
 
     def query(self, indices):
