@@ -104,6 +104,53 @@ __device__ __forceinline__ uint32_t hi32(uint64_t x) { return (uint32_t)(x >> 32
 
 static constexpr uint32_t PH3 = 0xCB800000u;     // top 32-bit limb of p (p = [1, 0, 0, PH3])
 
+// ---- constants without VGPR moves (SC_SGPR_CONST, default on).  hipcc gives a "v" operand that holds a constant a v_mov_b32 of
+// its own, and under register pressure it makes them again in every block: PH3 for the four REDC v_mad_u64_u32, a zero pair for
+// the first v_mad of an accumulator, a zero for the counters and the p-correction of limb 0.  PH3 goes in as an SGPR operand (one
+// constant-bus read; the carry-out destination is no read) and the zeros as the inline constant.
+#ifndef SC_SGPR_CONST
+#define SC_SGPR_CONST 1
+#endif
+#if SC_SGPR_CONST
+#define SC_ZERO_OPND "0"
+#define SC_ZERO_ARG(z)
+#define SC_PH_CONSTRAINT "s"
+#else
+#define SC_ZERO_OPND "%[z]"
+#define SC_ZERO_ARG(value) , [z] "v"(value)
+#define SC_PH_CONSTRAINT "v"
+#endif
+// x * y + 0
+__device__ __forceinline__ uint64_t a_mad0(uint32_t a, uint32_t b) {
+    uint64_t d; smask_t cy;
+    asm("v_mad_u64_u32 %[d], %[cy], %[a], %[b], " SC_ZERO_OPND : [d] "=v"(d), [cy] "=s"(cy) : [a] "v"(a), [b] "v"(b) SC_ZERO_ARG((uint64_t)0));
+    return d;
+}
+// x * PH3 + c (c: a 64-bit VGPR addend)
+__device__ __forceinline__ uint64_t a_mad_ph(uint32_t a, uint64_t c) {
+    uint64_t d; smask_t cy;
+    asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(d), "=s"(cy) : "v"(a), SC_PH_CONSTRAINT(PH3), "v"(c));
+    return d;
+}
+// x * PH3 + 0
+__device__ __forceinline__ uint64_t a_mad_ph0(uint32_t a) {
+    uint64_t d; smask_t cy;
+    asm("v_mad_u64_u32 %[d], %[cy], %[a], %[ph], " SC_ZERO_OPND : [d] "=v"(d), [cy] "=s"(cy) : [a] "v"(a), [ph] SC_PH_CONSTRAINT(PH3) SC_ZERO_ARG((uint64_t)0));
+    return d;
+}
+// 0 + 0 + carry  (a carry counter's first event)
+__device__ __forceinline__ uint32_t a_inc0(smask_t ci) {
+    uint32_t s; smask_t co;
+    asm(SC_HAZ_NOP "v_addc_co_u32_e64 %[s], %[co], " SC_ZERO_OPND ", 0, %[ci]" : [s] "=v"(s), [co] "=s"(co) : [ci] "s"(ci) SC_ZERO_ARG(0u));
+    return s;
+}
+// x + 0 + carry, carry out
+__device__ __forceinline__ uint32_t a_addc0(uint32_t x, smask_t ci, smask_t& co) {
+    uint32_t s;
+    asm(SC_HAZ_NOP "v_addc_co_u32_e64 %[s], %[co], %[x], " SC_ZERO_OPND ", %[ci]" : [s] "=v"(s), [co] "=s"(co) : [x] "v"(x), [ci] "s"(ci) SC_ZERO_ARG(0u));
+    return s;
+}
+
 // R (4 limbs + carry) -> canonical: subtract p when carry | R >= p
 __device__ __forceinline__ Fe a_cond_sub_p(uint32_t r0, uint32_t r1, uint32_t r2, uint32_t r3, smask_t cf) {
     smask_t b;
@@ -121,7 +168,7 @@ __device__ __forceinline__ Fe a_cond_sub_p(uint32_t r0, uint32_t r1, uint32_t r2
 __device__ __forceinline__ Fe a_fixup_fast(uint32_t d0, uint32_t d1, uint32_t d2, uint32_t d3, smask_t bw, smask_t& rare) {
     smask_t c;
     const uint32_t d3p = d3 + PH3;
-    uint32_t o0 = a_addc(d0, 0u, bw, c);
+    uint32_t o0 = a_addc0(d0, bw, c);
     uint32_t o3 = a_cnd(d3, d3p, bw);
     rare_or(rare, c);
     return Fe{((uint64_t)d1 << 32) | o0, ((uint64_t)o3 << 32) | d2};
@@ -157,7 +204,7 @@ __device__ __forceinline__ Fe a_fixup_fast(uint32_t d0, uint32_t d1, uint32_t d2
 __device__ __forceinline__ Fe a_fixup_fix(uint32_t d0, uint32_t d1, uint32_t d2, uint32_t d3, smask_t bw) {
     smask_t c, t;
     const uint32_t d3p = d3 + PH3;
-    uint32_t o0 = a_addc(d0, 0u, bw, c);
+    uint32_t o0 = a_addc0(d0, bw, c);
     uint32_t o3 = a_cnd(d3, d3p, bw);
     asm("s_cmp_eq_u64 %[c], 0\n\t"
         "s_cbranch_scc1 1f\n\t"
@@ -176,30 +223,30 @@ __device__ __forceinline__ Fe mont_mul_core(Fe a, Fe b, smask_t& rare) {
     const uint32_t b0 = lo32(b.lo), b1 = hi32(b.lo), b2 = lo32(b.hi), b3 = hi32(b.hi);
     smask_t c;
     // ---- product, even/odd accumulators
-    uint64_t E0 = a_mad(a0, b0, 0);
-    uint64_t O0 = a_mad(a0, b1, 0);
+    uint64_t E0 = a_mad0(a0, b0);
+    uint64_t O0 = a_mad0(a0, b1);
     O0 = a_madc(a1, b0, O0, c);
-    uint32_t nO0 = a_inc(0u, c);
-    uint64_t E1 = a_mad(a0, b2, 0);
+    uint32_t nO0 = a_inc0(c);
+    uint64_t E1 = a_mad0(a0, b2);
     E1 = a_madc(a1, b1, E1, c);
-    uint32_t nE1 = a_inc(0u, c);
+    uint32_t nE1 = a_inc0(c);
     E1 = a_madc(a2, b0, E1, c);
     nE1 = a_inc(nE1, c);
     uint64_t O1 = a_mad(a0, b3, (uint64_t)nO0);
     O1 = a_madc(a1, b2, O1, c);
-    uint32_t nO1 = a_inc(0u, c);
+    uint32_t nO1 = a_inc0(c);
     O1 = a_madc(a2, b1, O1, c);
     nO1 = a_inc(nO1, c);
     O1 = a_madc(a3, b0, O1, c);
     nO1 = a_inc(nO1, c);
     uint64_t E2 = a_mad(a1, b3, (uint64_t)nE1);
     E2 = a_madc(a2, b2, E2, c);
-    uint32_t nE2 = a_inc(0u, c);
+    uint32_t nE2 = a_inc0(c);
     E2 = a_madc(a3, b1, E2, c);
     nE2 = a_inc(nE2, c);
     uint64_t O2 = a_mad(a2, b3, (uint64_t)nO1);
     O2 = a_madc(a3, b2, O2, c);
-    uint32_t nO2 = a_inc(0u, c);
+    uint32_t nO2 = a_inc0(c);
     uint64_t E3 = a_mad(a3, b3, (uint64_t)nE2);
     // ---- merge T = E + (O << 32)
     const uint32_t t0 = lo32(E0);
@@ -213,13 +260,12 @@ __device__ __forceinline__ Fe mont_mul_core(Fe a, Fe b, smask_t& rare) {
     // ---- reduction (subtractive form): m' = T_lo * p^-1 mod 2^128 = T_lo - x*2^119 (mod 2^128) -- only the top limb of
     // T_lo changes -- and  T * 2^-128 = T_hi - (floor(m' * PH / 2^32) + delta)  in (-p, p),  PH = 407 * 2^23,
     // delta = borrow of the top-limb subtraction; the low word of t0 * PH IS x * 2^23, so x costs nothing.
-    const uint32_t PHc = PH3;                       // 407 * 2^23
-    uint64_t s0 = a_mad(t0, PHc, 0);
+    uint64_t s0 = a_mad_ph0(t0);                    // PH = PH3 = 407 * 2^23
     smask_t bw;
     uint32_t m3 = a_sub_co(t3, lo32(s0), bw);      // bw = delta
-    uint64_t s1 = a_mad(t1, PHc, (uint64_t)hi32(s0));
-    uint64_t s2 = a_mad(t2, PHc, (uint64_t)hi32(s1));
-    uint64_t s3 = a_mad(m3, PHc, (uint64_t)hi32(s2));
+    uint64_t s1 = a_mad_ph(t1, (uint64_t)hi32(s0));
+    uint64_t s2 = a_mad_ph(t2, (uint64_t)hi32(s1));
+    uint64_t s3 = a_mad_ph(m3, (uint64_t)hi32(s2));
     // R = T_hi - Q - delta; negative -> add p back (same tail as fe_sub)
     uint32_t r0 = a_subb(t4, lo32(s1), bw, bw);
     uint32_t r1 = a_subb(t5, lo32(s2), bw, bw);
@@ -228,9 +274,9 @@ __device__ __forceinline__ Fe mont_mul_core(Fe a, Fe b, smask_t& rare) {
     if constexpr (MODE == 1) return a_fixup_fast(r0, r1, r2, r3, bw, rare);
     if constexpr (MODE == 2) return a_fixup_fix(r0, r1, r2, r3, bw);
     uint32_t ph = a_cnd(0u, PH3, bw);
-    uint32_t o0 = a_addc(r0, 0u, bw, c);
-    uint32_t o1 = a_addc(r1, 0u, c, c);
-    uint32_t o2 = a_addc(r2, 0u, c, c);
+    uint32_t o0 = a_addc0(r0, bw, c);
+    uint32_t o1 = a_addc0(r1, c, c);
+    uint32_t o2 = a_addc0(r2, c, c);
     uint32_t o3 = a_addc_last(r3, ph, c);
     return Fe{((uint64_t)o1 << 32) | o0, ((uint64_t)o3 << 32) | o2};
 }
@@ -278,13 +324,33 @@ template <int W> __device__ __forceinline__ void v_addc_dump(uint32_t& d, uint32
 #define SC_V_MADD(d, x, y, c)      v_mad_dump<W>(d, x, y, c)
 #define SC_V_INCD(d, x, ci)        v_inc_dump<W>(d, x, ci)
 #define SC_V_ADDCD(d, x, y, ci)    v_addc_dump<W>(d, x, y, ci)
-
+// the same with the constants of SC_SGPR_CONST: x * y + 0, x * PH3 + c, x * PH3 + 0, 0 + 0 + carry, x + 0 + carry
+template <int W> __device__ __forceinline__ void v_mad0_dump(uint64_t& d, uint32_t x, uint32_t y) {
+    if constexpr (W == 0) asm volatile("v_mad_u64_u32 %[d], vcc, %[x], %[y], " SC_ZERO_OPND : [d] "=v"(d) : [x] "v"(x), [y] "v"(y) SC_ZERO_ARG((uint64_t)0) : "vcc");
+    else asm volatile("v_mad_u64_u32 %[d], s[100:101], %[x], %[y], " SC_ZERO_OPND : [d] "=v"(d) : [x] "v"(x), [y] "v"(y) SC_ZERO_ARG((uint64_t)0) : "s100", "s101");
+}
+template <int W> __device__ __forceinline__ void v_madp_dump(uint64_t& d, uint32_t x, uint64_t c) {
+    if constexpr (W == 0) asm volatile("v_mad_u64_u32 %0, vcc, %1, %2, %3" : "=v"(d) : "v"(x), SC_PH_CONSTRAINT(PH3), "v"(c) : "vcc");
+    else asm volatile("v_mad_u64_u32 %0, s[100:101], %1, %2, %3" : "=v"(d) : "v"(x), SC_PH_CONSTRAINT(PH3), "v"(c) : "s100", "s101");
+}
+template <int W> __device__ __forceinline__ void v_madp0_dump(uint64_t& d, uint32_t x) {
+    if constexpr (W == 0) asm volatile("v_mad_u64_u32 %[d], vcc, %[x], %[ph], " SC_ZERO_OPND : [d] "=v"(d) : [x] "v"(x), [ph] SC_PH_CONSTRAINT(PH3) SC_ZERO_ARG((uint64_t)0) : "vcc");
+    else asm volatile("v_mad_u64_u32 %[d], s[100:101], %[x], %[ph], " SC_ZERO_OPND : [d] "=v"(d) : [x] "v"(x), [ph] SC_PH_CONSTRAINT(PH3) SC_ZERO_ARG((uint64_t)0) : "s100", "s101");
+}
+template <int W> __device__ __forceinline__ void v_inc0_dump(uint32_t& d, smask_t ci) {
+    if constexpr (W == 0) asm volatile("v_addc_co_u32_e64 %[d], vcc, " SC_ZERO_OPND ", 0, %[ci]" : [d] "=v"(d) : [ci] "s"(ci) SC_ZERO_ARG(0u) : "vcc");
+    else asm volatile("v_addc_co_u32_e64 %[d], s[100:101], " SC_ZERO_OPND ", 0, %[ci]" : [d] "=v"(d) : [ci] "s"(ci) SC_ZERO_ARG(0u) : "s100", "s101");
+}
+#define SC_V_MADD0(d, x, y)        v_mad0_dump<W>(d, x, y)
+#define SC_V_MADDP(d, x, c)        v_madp_dump<W>(d, x, c)
+#define SC_V_MADDP0(d, x)          v_madp0_dump<W>(d, x)
+#define SC_V_INCD0(d, ci)          v_inc0_dump<W>(d, ci)
+#define SC_V_ADDC0(d, co, x, ci)   asm volatile("v_addc_co_u32_e64 %[s], %[c], %[a], " SC_ZERO_OPND ", %[i]" : [s] "=v"(d), [c] "=s"(co) : [a] "v"(x), [i] "s"(ci) SC_ZERO_ARG(0u))
 struct MulState {       // registers of one product in flight
     uint32_t a0, a1, a2, a3, b0, b1, b2, b3;
     uint64_t E0, O0, E1, O1, E2, O2, E3, s0, s1, s2, s3;
     uint32_t nO0, nE1, nO1, nE2, nO2, t1, t2, t3, t4, t5, t6, t7, m3, r0, r1, r2, r3, ph, o0, o1, o2, o3;
-    smask_t c1, c2, c3, c4, c5, c6, c7, c8, c9, ct, bw, cx;
-};
+    smask_t c1, c2, c3, c4, c5, c6, c7, c8, c9, ct, bw, cx;};
 
 // FAST: the top-limb correction (field.cuh, fe_fixup_fast_c) instead of the four-limb one: limb 0 takes the borrow as its carry-in,
 // limb 3 gets PH3 by a plain add and a select, limbs 1 and 2 stay, and limb 0's carry-out -- the carry they would have passed on --
@@ -298,51 +364,50 @@ __device__ __forceinline__ void mont_mul2_core(Fe xa, Fe wa, Fe xb, Fe wb, Fe& r
     A.b0 = lo32(wa.lo); A.b1 = hi32(wa.lo); A.b2 = lo32(wa.hi); A.b3 = hi32(wa.hi);
     B.a0 = lo32(xb.lo); B.a1 = hi32(xb.lo); B.a2 = lo32(xb.hi); B.a3 = hi32(xb.hi);
     B.b0 = lo32(wb.lo); B.b1 = hi32(wb.lo); B.b2 = lo32(wb.hi); B.b3 = hi32(wb.hi);
-    const uint64_t zero64 = 0;
-    const uint32_t zero32 = 0, PHc = PH3;
+    [[maybe_unused]] const uint32_t zero32 = 0, PHc = PH3;
 #define SC_BOTH(STEP) { MulState& M = A; [[maybe_unused]] constexpr int W = 0; STEP } { MulState& M = B; [[maybe_unused]] constexpr int W = 1; STEP }
     // ---- product.  Carry counters travel in PAIRS: the odd accumulator O_k covers columns (2k+1, 2k+2), and the overflow counts
     // of O_{k-1} (weight: column 2k+1) and of E_k (weight: column 2k+2) are exactly the low and the high word of the 64-bit addend
     // of O_k's first v_mad -- {nO0, nE1} for O1, {nO1, nE2} for O2 -- so no counter is ever zero-extended into a register pair
-    // of its own (4 v_mov per product before), and the even accumulators start from the shared zero.  That first v_mad cannot
+    // of its own (4 v_mov per product before), and the even accumulators start from the inline zero.  That first v_mad cannot
     // overflow: its product has the twiddle's top limb b3 <= 0xCB800000 as a factor (a * b3 <= 0.8 * 2^64) and the addend is
     // below 2^34.  The schedule keeps every carry consumer >= 2 instructions behind its producer (4 with the interleave).
-    SC_BOTH(SC_V_MADD(M.E0, M.a0, M.b0, zero64);)
-    SC_BOTH(SC_V_MADD(M.O0, M.a0, M.b1, zero64);)
-    SC_BOTH(SC_V_MADD(M.E1, M.a0, M.b2, zero64);)
+    SC_BOTH(SC_V_MADD0(M.E0, M.a0, M.b0);)
+    SC_BOTH(SC_V_MADD0(M.O0, M.a0, M.b1);)
+    SC_BOTH(SC_V_MADD0(M.E1, M.a0, M.b2);)
     SC_BOTH(SC_V_MAD(M.O0, M.c1, M.a1, M.b0, M.O0);)
     SC_BOTH(SC_V_MAD(M.E1, M.c2, M.a1, M.b1, M.E1);)
     SC_BOTH(SC_V_MAD(M.E1, M.c3, M.a2, M.b0, M.E1);)
-    SC_BOTH(SC_V_INCD(M.nO0, zero32, M.c1);)
-    SC_BOTH(SC_V_INCD(M.nE1, zero32, M.c2);)
+    SC_BOTH(SC_V_INCD0(M.nO0, M.c1);)
+    SC_BOTH(SC_V_INCD0(M.nE1, M.c2);)
     SC_BOTH(SC_V_INCD(M.nE1, M.nE1, M.c3);)
     SC_BOTH(SC_V_MADD(M.O1, M.a0, M.b3, (uint64_t)M.nO0 | ((uint64_t)M.nE1 << 32));)
     SC_BOTH(SC_V_MAD(M.O1, M.c4, M.a1, M.b2, M.O1);)
     SC_BOTH(SC_V_MAD(M.O1, M.c5, M.a2, M.b1, M.O1);)
-    SC_BOTH(SC_V_INCD(M.nO1, zero32, M.c4);)
+    SC_BOTH(SC_V_INCD0(M.nO1, M.c4);)
     SC_BOTH(SC_V_MAD(M.O1, M.c6, M.a3, M.b0, M.O1);)
-    SC_BOTH(SC_V_MADD(M.E2, M.a1, M.b3, zero64);)
+    SC_BOTH(SC_V_MADD0(M.E2, M.a1, M.b3);)
     SC_BOTH(SC_V_INCD(M.nO1, M.nO1, M.c5);)
     SC_BOTH(SC_V_MAD(M.E2, M.c7, M.a2, M.b2, M.E2);)
     SC_BOTH(SC_V_INCD(M.nO1, M.nO1, M.c6);)
     SC_BOTH(SC_V_MAD(M.E2, M.c8, M.a3, M.b1, M.E2);)
-    SC_BOTH(SC_V_INCD(M.nE2, zero32, M.c7);)
-    SC_BOTH(SC_V_MADD(M.E3, M.a3, M.b3, zero64);)
+    SC_BOTH(SC_V_INCD0(M.nE2, M.c7);)
+    SC_BOTH(SC_V_MADD0(M.E3, M.a3, M.b3);)
     SC_BOTH(SC_V_INCD(M.nE2, M.nE2, M.c8);)
     SC_BOTH(SC_V_MADD(M.O2, M.a2, M.b3, (uint64_t)M.nO1 | ((uint64_t)M.nE2 << 32));)
     SC_BOTH(SC_V_MAD(M.O2, M.c9, M.a3, M.b2, M.O2);)
     // ---- merge T = E + (O << 32), interleaved with the reduction chain s0..s3 (t0 = lo32(E0)); its first two steps stand
     // between the last v_mad of the product and the counter that reads its carry
     SC_BOTH(SC_V_ADDCO(M.t1, M.ct, hi32(M.E0), lo32(M.O0));)
-    SC_BOTH(SC_V_MADD(M.s0, lo32(M.E0), PHc, zero64);)
-    SC_BOTH(SC_V_INCD(M.nO2, zero32, M.c9);)
+    SC_BOTH(SC_V_MADDP0(M.s0, lo32(M.E0));)
+    SC_BOTH(SC_V_INCD0(M.nO2, M.c9);)
     SC_BOTH(SC_V_ADDC(M.t2, M.ct, lo32(M.E1), hi32(M.O0), M.ct);)
-    SC_BOTH(SC_V_MADD(M.s1, M.t1, PHc, (uint64_t)hi32(M.s0));)
+    SC_BOTH(SC_V_MADDP(M.s1, M.t1, (uint64_t)hi32(M.s0));)
     SC_BOTH(SC_V_ADDC(M.t3, M.ct, hi32(M.E1), lo32(M.O1), M.ct);)
-    SC_BOTH(SC_V_MADD(M.s2, M.t2, PHc, (uint64_t)hi32(M.s1));)
+    SC_BOTH(SC_V_MADDP(M.s2, M.t2, (uint64_t)hi32(M.s1));)
     SC_BOTH(SC_V_SUBCO(M.m3, M.bw, M.t3, lo32(M.s0));)
     SC_BOTH(SC_V_ADDC(M.t4, M.ct, lo32(M.E2), hi32(M.O1), M.ct);)
-    SC_BOTH(SC_V_MADD(M.s3, M.m3, PHc, (uint64_t)hi32(M.s2));)
+    SC_BOTH(SC_V_MADDP(M.s3, M.m3, (uint64_t)hi32(M.s2));)
     SC_BOTH(SC_V_ADDC(M.t5, M.ct, hi32(M.E2), lo32(M.O2), M.ct);)
     SC_BOTH(SC_V_SUBB(M.r0, M.bw, M.t4, lo32(M.s1), M.bw);)
     SC_BOTH(SC_V_ADDC(M.t6, M.ct, lo32(M.E3), hi32(M.O2), M.ct);)
@@ -356,7 +421,7 @@ __device__ __forceinline__ void mont_mul2_core(Fe xa, Fe wa, Fe xb, Fe wb, Fe& r
     if constexpr (MODE == 2) {
         A.ph = A.r3 + PHc;
         B.ph = B.r3 + PHc;
-        SC_BOTH(SC_V_ADDC(M.o0, M.cx, M.r0, zero32, M.bw);)
+        SC_BOTH(SC_V_ADDC0(M.o0, M.cx, M.r0, M.bw);)
         SC_BOTH(SC_V_CND(M.o3, M.r3, M.ph, M.bw);)
         smask_t t;
         asm volatile("s_or_b64 %[t], %[ca], %[cb]\n\t"
@@ -374,7 +439,7 @@ __device__ __forceinline__ void mont_mul2_core(Fe xa, Fe wa, Fe xb, Fe wb, Fe& r
     if constexpr (MODE == 1) {
         A.ph = A.r3 + PHc;
         B.ph = B.r3 + PHc;
-        SC_BOTH(SC_V_ADDC(M.o0, M.cx, M.r0, zero32, M.bw);)
+        SC_BOTH(SC_V_ADDC0(M.o0, M.cx, M.r0, M.bw);)
         SC_BOTH(SC_V_CND(M.o3, M.r3, M.ph, M.bw);)
         rare_or(rare, A.cx);
         rare_or(rare, B.cx);
@@ -383,11 +448,11 @@ __device__ __forceinline__ void mont_mul2_core(Fe xa, Fe wa, Fe xb, Fe wb, Fe& r
         return;
     }
     SC_BOTH(SC_V_CND(M.ph, zero32, PHc, M.bw);)
-    SC_BOTH(SC_V_ADDC(M.o0, M.cx, M.r0, zero32, M.bw);)
+    SC_BOTH(SC_V_ADDC0(M.o0, M.cx, M.r0, M.bw);)
     SC_V_NOP0();
-    SC_BOTH(SC_V_ADDC(M.o1, M.cx, M.r1, zero32, M.cx);)
+    SC_BOTH(SC_V_ADDC0(M.o1, M.cx, M.r1, M.cx);)
     SC_V_NOP0();
-    SC_BOTH(SC_V_ADDC(M.o2, M.cx, M.r2, zero32, M.cx);)
+    SC_BOTH(SC_V_ADDC0(M.o2, M.cx, M.r2, M.cx);)
     SC_V_NOP0();
     SC_BOTH(SC_V_ADDCD(M.o3, M.r3, M.ph, M.cx);)
 #undef SC_BOTH

@@ -439,6 +439,55 @@ struct Round {
 #pragma unroll
         for (int i = 0; i < E; ++i) lds[lds_index(row(i, sh), cc[i >> S], logC)] = x[i];
     }
+    // The LDS exchanges of the geometry-specialised eight-element rounds (SPLIT_ADDR; FixedRounds::run, SC_LDS_SPLIT): element i's
+    // row and column are the disjoint OR of a lane part (r_l, c_l: this thread's rr[0], cc[0]) and a compile-time part (r_u, c_u:
+    // the element's place in its butterfly group and the group's share of the thread index), so with cm = C - 1
+    //     lds_index(r, c) = (r << logC) | ((c ^ r) & cm) = (lds_index(r_l, c_l) ^ ((c_u ^ r_u) & cm)) + (r_u << logC):
+    // ONE lane address per exchange side, a v_xor per distinct value of the swizzle's compile-time bits (none where sh >= logC, where
+    // r_u has no bit below logC; four bases at logC = 2 for the gather at sh = 0), and the rest in the 16-bit offset field of
+    // ds_read_b128 / ds_write_b128 (a tile is at most 64 KiB) -- instead of an index built per element.
+    // RFAST: setup()'s split of the thread index for the first round of a transposing pass.
+    template <bool RFAST> SC_HD static Uc uniform_part(int g) {          // group_part(g) for a compile-time geometry and split
+        const uint32_t rem = (uint32_t)g << (GLR + GLC - LOGE);
+        if (RFAST) return Uc{rem & ((1u << (GLR - S)) - 1u), rem >> (GLR - S)};
+        return Uc{rem >> GLC, rem & ((1u << GLC) - 1u)};
+    }
+    template <bool RFAST> SC_HD static uint32_t lds_low(int i, int sh) {
+        const Uc u = uniform_part<RFAST>(i >> S);
+        return (u.c ^ row_of(u.rrem, (uint32_t)(i & (F - 1)), sh)) & ((1u << GLC) - 1u);
+    }
+    template <bool RFAST> SC_HD static uint32_t lds_off(int i, int sh) {
+        return row_of(uniform_part<RFAST>(i >> S).rrem, (uint32_t)(i & (F - 1)), sh) << GLC;
+    }
+    SC_HD uint32_t lds_lane(int sh) const { return lds_index(row_of(rr[0], 0, sh), cc[0], logC); }
+    // tile index of element i from the lane index
+    template <bool RFAST> SC_HD static uint32_t lds_index_split(uint32_t lane, int i, int sh) {
+        return (lane ^ lds_low<RFAST>(i, sh)) + lds_off<RFAST>(i, sh);
+    }
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef __attribute__((address_space(3))) char lchar;
+    typedef __attribute__((address_space(3))) Fe lfe;
+    // (the lane's byte offset is pinned: what the compiler may not look through it cannot fold back into per-element indices)
+    template <bool RFAST> SC_HD void gather_lds_split(int sh, Fe* x, const Fe* lds) const {
+        const lchar* base = (const lchar*)lds;
+        const uint32_t lane = vgpr_pin(lds_lane(sh) << 4);
+#pragma unroll
+        for (int i = 0; i < E; ++i) x[i] = *reinterpret_cast<const lfe*>(base + ((lane ^ (lds_low<RFAST>(i, sh) << 4)) + (lds_off<RFAST>(i, sh) << 4)));
+    }
+    template <bool RFAST> SC_HD void scatter_lds_split(int sh, const Fe* x, Fe* lds) const {
+        lchar* base = (lchar*)lds;
+        const uint32_t lane = vgpr_pin(lds_lane(sh) << 4);
+#pragma unroll
+        for (int i = 0; i < E; ++i) *reinterpret_cast<lfe*>(base + ((lane ^ (lds_low<RFAST>(i, sh) << 4)) + (lds_off<RFAST>(i, sh) << 4))) = x[i];
+    }
+#else
+    template <bool RFAST> void gather_lds_split(int sh, Fe* x, const Fe* lds) const {
+        for (int i = 0; i < E; ++i) x[i] = lds[lds_index_split<RFAST>(lds_lane(sh), i, sh)];
+    }
+    template <bool RFAST> void scatter_lds_split(int sh, const Fe* x, Fe* lds) const {
+        for (int i = 0; i < E; ++i) lds[lds_index_split<RFAST>(lds_lane(sh), i, sh)] = x[i];
+    }
+#endif
     // last round (sh == 0): four-step twiddle (unless the next pass applies it on load), final scale, store
     // the direct four-step twiddles of this thread's E output elements (PassParams::twd): issued early by the fixed-shape kernel,
     // at the top of the last round, so that their latency hides behind that round's butterflies
@@ -600,6 +649,10 @@ SC_HD void tile_twiddles_to_lds(const PassParams& P, int logR, uint32_t tid, uin
 // (ntt_pass_kernel_fixed) and eight (ntt_pass_kernel_fixed8).  core.hip's launch_pass and the emulator dispatch over these lists.
 #define SC_FIXED4_SHAPES(X) X(8, 3) X(7, 4) X(10, 2) X(6, 5) X(9, 3) X(8, 4)
 #define SC_FIXED8_SHAPES(X) X(10, 2) X(9, 3) X(8, 4)
+// A/B switch of the eight-element kernels' LDS addressing (FixedRounds::LDS_SPLIT): 0 = an index per element (scatter_lds / gather_lds)
+#ifndef SC_LDS_SPLIT
+#define SC_LDS_SPLIT 1
+#endif
 // FAST = ARITH_FIX: the rounds use the self-repairing top-limb forms; no accumulator, nothing to redo (ntt_pass_kernel_fixed8).
 // FAST = ARITH_FAST: the rounds use the top-limb field corrections and accumulate their flags in `rare` (one accumulator through all rounds
 // of the tile); where it ends up non-zero the tile's outputs may be wrong -- also those of other waves, which got this wave's
@@ -613,6 +666,8 @@ struct FixedRounds {
     static constexpr int SH = GLR - DONE - S;
     static constexpr bool NEXT_WAVE_LOCAL = (ROUND >= 1) && (SH + GLC <= 6);
     static constexpr uint32_t TW_COUNT = 1u << (GLR - 1);     // tile twiddles; <= threads per workgroup for GLC >= 1
+    // the LDS exchanges as lane address + immediate offset (Round::gather_lds_split): the eight-element kernels only, like SPLIT_ADDR
+    static constexpr bool LDS_SPLIT = SC_LDS_SPLIT && Round<LOGE, S, GLR, GLC>::SPLIT_ADDR;
 
     // sync(): workgroup barrier; wsync(): wave-level fence; stamp(i): diagnostics hook (no-op in production)
     template <class Sync, class WSync, class Stamp>
@@ -638,7 +693,9 @@ struct FixedRounds {
             stamp(2);
             R.template finish_global<FAST>(P, SH, x, tin, &rare);
         } else {
-            R.gather_lds(SH, x, lds);
+            // (a later round never has the first round's split of the thread index)
+            if constexpr (LDS_SPLIT) R.template gather_lds_split<false>(SH, x, lds);
+            else R.gather_lds(SH, x, lds);
         }
         Fe tpre[E];
         bool prefetched = false;
@@ -653,7 +710,12 @@ struct FixedRounds {
         R.template butterflies<FAST>(SH, x, tw, 0, prune, ROUND + 1 == NR ? 1 : 0, P.prio_balance == 1 ? 1 : 0, &rare);
         stamp(3 + 2 * ROUND);
         if constexpr (ROUND + 1 < NR) {
-            R.scatter_lds(SH, x, lds);
+            if constexpr (LDS_SPLIT) {
+                if (ROUND == 0 && R.rfast) R.template scatter_lds_split<true>(SH, x, lds);
+                else R.template scatter_lds_split<false>(SH, x, lds);
+            } else {
+                R.scatter_lds(SH, x, lds);
+            }
             if (NEXT_WAVE_LOCAL && wave_local) wsync(); else sync();
             stamp(4 + 2 * ROUND);
             FixedRounds<LOGE, GLR, GLC, ROUND + 1, ALT, FAST>::run(P, tile, tid, lds, tw, sync, wsync, stamp, wave_local, rare);
