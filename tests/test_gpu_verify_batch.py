@@ -8,6 +8,7 @@ from hashlib import blake2b, shake_256
 import numpy as np
 import pytest
 
+from verify_spies import host_verdict, row_counts           # noqa: F401  (row_counts: a fixture)
 from workload_rescue_prime import RescuePrime
 
 pytestmark = pytest.mark.gpu
@@ -46,13 +47,6 @@ def seeded_urandom():
     genuine = fast_stark.os.urandom
     yield _seed_urandom
     fast_stark.os.urandom = genuine
-
-
-def host_verdict(fn, *args):
-    try:
-        return fn(*args) == True          # noqa: E712  (the verifiers return bools; anything else is not an acceptance)
-    except Exception:
-        return False
 
 
 def flipped(digest, at=0):
@@ -420,38 +414,7 @@ def test_stark_verify_batch_configs4_size(seeded_urandom):
 
 # ---- what goes to the device -----------------------------------------------------------------------------------------------------
 
-@pytest.fixture
-def row_counts(monkeypatch):
-    """rows each device entry received, UNDECIDED colinearity verdicts, and calls of the host functions rows fall back to"""
-    import fri
-    counts = {"merkle": 0, "colinearity": 0, "undecided": 0, "host_merkle": 0, "host_colinearity": 0}
-    merkle_batch, colinearity_batch = sc.merkle_verify_batch, sc.colinearity_batch
-    host_merkle, host_colinearity = fri.Merkle.verify, fri.test_colinearity
-
-    def spy_merkle(rows, *a):
-        counts["merkle"] += len(rows)
-        return merkle_batch(rows, *a)
-
-    def spy_colinearity(rows, *a):
-        counts["colinearity"] += len(rows)
-        out = colinearity_batch(rows, *a)
-        counts["undecided"] += int((out == sc.UNDECIDED).sum())
-        return out
-
-    def spy_host_merkle(*a):
-        counts["host_merkle"] += 1
-        return host_merkle(*a)
-
-    def spy_host_colinearity(*a):
-        counts["host_colinearity"] += 1
-        return host_colinearity(*a)
-
-    monkeypatch.setattr(sc, "merkle_verify_batch", spy_merkle)
-    monkeypatch.setattr(sc, "colinearity_batch", spy_colinearity)
-    monkeypatch.setattr(fri.Merkle, "verify", staticmethod(spy_host_merkle))
-    monkeypatch.setattr(fri, "test_colinearity", spy_host_colinearity)
-    return counts
-
+# (the `row_counts` spies: tests/verify_spies.py, imported above)
 
 def test_honest_fri_proofs_check_every_row_on_the_device(row_counts):
     field = Field.main()
