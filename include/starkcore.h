@@ -851,6 +851,37 @@ int sc_fri_fold_pairs_commit_dev(const void* d_in, uint64_t N, const uint64_t al
                                  sc_merkle_t** tree, void* stream);
 int sc_fri_pairs_query_dev(uint64_t n, const sc_merkle_t* const* trees, const void* const* d_codewords, const uint64_t* indices, const uint64_t* counts,
                            void* pairs_out, uint8_t* paths_out);
+/* Fri.prove with pair leaves in ONE call: the arguments of sc_fri_prove_grind_dev (grinding_bits = 0: no proof of work, nonce_out may be
+ * NULL), the same steps, over pair trees.
+ * Commit phase: codeword r (n_r = N >> r elements) under the row tree of {cw, cw + n_r/2} (n_r/2 leaves); round 0's tree is started
+ *             asynchronously, the rounds whose output has more than 2^16 elements use the launches of sc_fri_fold_pairs_commit_dev, each root
+ *             is polled from its pinned slot and the challenge computed in the library as in sc_fri_commit_dev; from 2^16 elements down the
+ *             rounds run in the pair form of the persistent tail kernel (csrc/fri_tail.cuh: a lane folds both members of a pair and hashes
+ *             the 32-byte row leaf out of registers), with the per-round launches as the fall-back when the kernel is switched off
+ *             (sc_set_tuning("fri_tail", 0), STARKCORE_FRI_TAIL=0), not taken or gave up (counted in sc_fri_tail_stats).
+ * Between commit and query: as in sc_fri_prove_dev -- the last codeword in the clear, the challenge over [prior..., roots..., last
+ *             codeword], the proof of work (grinding_bits > 0), Fri.sample_indices.
+ * Openings:   one launch.  Codeword j < rounds - 1: the num_tests pairs {cw_j[a], cw_j[a + n_j/2]} and the paths of leaf a = index mod
+ *             n_j/2 over the top-level indices; nothing of the last codeword.  The `extra_count` further (ordinary tree, device vector)
+ *             pairs: as in sc_fri_prove_dev, at the four-fold sorted positions written to extra_indices_out.
+ * `answers`:  four sections, each contiguous and starting at a multiple of 256 bytes, each codeword after codeword:
+ *               [pairs            32 bytes per opening: num_tests per codeword j < rounds - 1]
+ *               [extra elements   16 bytes per opening: 4 num_tests per further pair]
+ *               [paths            64 * log2(n_j/2) bytes per pair opening, then 64 * log2 N per opening of a further pair]
+ *               [positions        u64: the leaf numbers a (num_tests per codeword), then the sorted positions of each further pair]
+ *             answers_bytes >= the four section lengths, the first three rounded up to multiples of 256.  A buffer of sc_host_alloc is
+ *             written by the kernel itself; any other host pointer is served through the staging copy.
+ * Outputs:    as sc_fri_prove_dev's.  With vecs_out = trees_out = NULL the folded codewords and their trees go back to the pools before the
+ *             call returns; given, trees_out[r] is an ordinary sc_merkle_t of n_r/2 leaves (sc_fri_pairs_query_dev, sc_merkle_open_batch).
+ * Refused with nothing enqueued and nothing written -- SC_ERR_NOT_POW2: N no power of two, or N >> (rounds - 1) < 2; SC_ERR_BAD_ARG: a NULL
+ * that is needed, num_tests == 0 or > N >> (rounds - 1), rounds < 2, answers_bytes too small, grinding_bits outside 0 .. 63;
+ * SC_ERR_UNSUPPORTED: a transcript outside the fixed layout, or rounds + extra_count > 32 (the caller runs the phases one by one). */
+int sc_fri_prove_pairs_dev(const void* d_codeword, uint64_t N, const uint64_t offset[2], const uint64_t omega[2], uint32_t rounds, uint32_t num_tests,
+                           const void* prior_data, const uint32_t* prior_lens, uint64_t prior_count,
+                           uint64_t extra_count, const sc_merkle_t* const* extra_trees, const void* const* extra_vecs, uint64_t extra_shift,
+                           sc_vec_t** vecs_out, sc_merkle_t** trees_out, uint8_t* roots_out, uint64_t* alphas_out,
+                           void* last_codeword_out, uint64_t* top_indices_out, uint64_t* extra_indices_out,
+                           void* answers, uint64_t answers_bytes, void* stream, int grinding_bits, uint64_t* nonce_out);
 
 /* ---- Merkle forests: Merkle.commit (merkle.py:13-14) of `count` arrays of N leaves each in one set of launches ------------------ */
 /* d_elems: a device matrix [count][N] of residues, row t = the leaves of tree t; N a power of two >= 2, count >= 1.  All levels of all

@@ -282,6 +282,12 @@ int host_pool_put(void* p);
 bool host_pool_holds(const void* p, size_t bytes);
 int verify_stage_buffer(size_t bytes, uint8_t** out);   // the batched verifier's pinned staging buffer, grown to `bytes` (one per process; callers hold g_mu)
 
+// ---- merkle_rows.hip: pair leaves for FRI (csrc/fri_pairs.cuh) for a caller that holds g_mu -- the commit phase of sc_fri_prove_pairs_dev
+// pair_tree_start: the pair tree of a codeword of n >= 2 elements (n / 2 leaves), enqueued, the root on its way to a pinned slot;
+// fold_pairs_and_build: what sc_fri_fold_pairs_commit_dev enqueues (N >= 4)
+int pair_tree_start(const Fe* d_codeword, uint64_t n, sc_merkle** tree, hipStream_t st);
+int fold_pairs_and_build(const Fe* d_in, uint64_t N, Fe alpha, Fe offset, Fe omega, Fe* d_out, sc_merkle** tree, hipStream_t st);
+
 // ---- grind.hip
 // sc_grind_batch for a caller that holds g_mu (and keeps it: sc_fri_prove_grind_dev searches in the middle of its own call)
 int grind_seeds_locked(const std::string& what, const void* seeds, uint64_t count, int bits, uint64_t start, uint64_t max_nonces, uint64_t* nonces_out,

@@ -84,6 +84,7 @@ struct PairTrees {
     uint64_t total_threads;
     int count;
 };
+#ifndef SC_ROWS_NO_KERNELS      // (merkle_rows.cuh: the plain kernels of the row stages have one home, merkle_rows.hip)
 __global__ void __launch_bounds__(256) fri_pairs_query_kernel(const PairTrees Q, const uint64_t* __restrict__ indices, Fe* __restrict__ pairs_out,
                                                               uint64_t* __restrict__ paths_out) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -106,6 +107,68 @@ __global__ void __launch_bounds__(256) fri_pairs_query_kernel(const PairTrees Q,
         o[quarter] = s[quarter];
     }
 }
+#endif  // SC_ROWS_NO_KERNELS
+
+#ifndef SC_MERKLE_NO_KERNELS    // (merkle.cuh: QueryDone and the kernels around it belong to merkle_fri.hip)
+// Its sibling for sc_fri_prove_pairs_dev: the pair openings AND the caller's further (ordinary tree, vector) pairs in one launch, the
+// answers possibly straight into pinned host memory.  The first Q.pair_trees entries are pair trees as above; the entries behind them
+// are ordinary trees of L = N leaves over N elements (per_query = 1 + 4 logL: the opened element, then the path), whose openings are
+// numbered behind all pair openings: element idx_off + q - Q.pair_openings of elems_out.  `indices` may live in host memory: the first
+// lane of every run of lanes that serve one opening loads it and hands it on (the scheme of merkle_query_multi_kernel, as is `done`).
+struct ProveOpenings {
+    PairTrees Q;
+    int pair_trees;
+    uint64_t pair_openings;
+};
+__global__ void __launch_bounds__(256) fri_pairs_prove_query_kernel(const ProveOpenings O, const uint64_t* __restrict__ indices, Fe* __restrict__ pairs_out,
+                                                                    Fe* __restrict__ elems_out, uint64_t* __restrict__ paths_out, const QueryDone done) {
+    const PairTrees& Q = O.Q;
+    const uint64_t t_raw = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = t_raw < Q.total_threads;
+    const uint64_t t = live ? t_raw : Q.total_threads - 1;
+    int w = 0;
+    for (int i = 1; i < Q.count; ++i) if (t >= Q.t[i].thread_off) w = i;
+    const PairTree& T = Q.t[w];
+    const bool pair = w < O.pair_trees;
+    const uint64_t local = t - T.thread_off;
+    const uint64_t q = local / T.per_query;
+    const uint32_t r = (uint32_t)(local % T.per_query);
+    const uint64_t qn = T.idx_off + q;                        // the opening's number: non-decreasing along the lanes
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t below = __shfl_up(qn, 1);
+    const bool leader = lane == 0 || below != qn;
+    const uint64_t leaders = __ballot(leader);
+    const uint64_t mine = leader ? indices[qn] : 0ull;
+    const int src = 63 - __builtin_clzll(leaders & (lane == 63 ? ~0ull : ((2ull << lane) - 1ull)));
+    const uint64_t idx = __shfl(mine, src);
+    const uint32_t values = pair ? 2u : 1u;                   // threads of an opening that copy a value; the others a quarter of a digest
+    if (live) {
+        if (r < values) {
+            if (pair) pairs_out[2 * qn + r] = T.elems[idx + (r ? T.L : 0ull)];
+            else elems_out[qn - O.pair_openings] = T.elems[idx];
+        } else {
+            const uint32_t quarter = (r - values) & 3u, l = (r - values) >> 2;
+            const uint64_t off = (l == 0) ? 0 : (2 * T.L - (T.L >> (l - 1)));
+            const uint64_t node = (idx >> l) ^ 1ull;
+            const ulonglong2* s = reinterpret_cast<const ulonglong2*>(T.levels + 8 * (off + node));
+            ulonglong2* o = reinterpret_cast<ulonglong2*>(paths_out + 8 * (T.path_off + q * T.logL + l));
+            o[quarter] = s[quarter];
+        }
+    }
+    if (done.host_flag) {
+        __threadfence_system();
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const unsigned arrived = atomicAdd(done.ticket, 1u);
+            if (arrived == gridDim.x - 1) {
+                *done.ticket = 0;
+                __threadfence_system();
+                done.host_flag[0] = done.seq;
+            }
+        }
+    }
+}
+#endif  // SC_MERKLE_NO_KERNELS
 
 #endif  // __HIPCC__
 

@@ -18,8 +18,14 @@
 // 25 lanes and 8.9 us in one lane (tools/microbench/keccak_wave.hip, profiles/r05/keccak_wave_ubench.txt) -- and no launch separates
 // the rounds any more.  Nothing spins for ever:
 // every wait gives up after TAIL_SPIN_LIMIT polls and raises the abort flag, and the host then finishes the rounds the classic way.
+//
+// PAIRS (fri_tail_kernel<true>, Fri(pair_leaves=True), csrc/fri_pairs.cuh): a round's codeword of n elements is committed under the tree
+// of its n/2 PAIRS.  Leaf i's lane (or quad) folds both members -- out[i] and out[i + n/2], pair_fold_lane -- stores them and hashes
+// the personalised 32-byte row leaf (merkle_rows.cuh: row_leaf_walk) out of registers; the tree has n - 1 digests.  Everything above
+// the leaf stage -- subtree levels, barrier, root out, challenge back, every bounded wait -- is the one code below.
 #pragma once
 #include "merkle.cuh"
+#include "fri_pairs.cuh"
 
 namespace sc {
 
@@ -31,7 +37,7 @@ constexpr uint32_t TAIL_SPIN_LIMIT = 1u << 21;      // polls before a wait gives
 
 struct TailRoundDesc {
     Fe* out;              // this round's folded codeword
-    uint64_t* levels;     // its tree, (2 n - 1) digests
+    uint64_t* levels;     // its tree, (2 n - 1) digests (pair form: n / 2 leaves, n - 1 digests)
     Fe i2o_m;             // 1 / (2 offset) of the codeword being folded, Montgomery form
 };
 // pinned host memory, one block per call; every flag carries the call's sequence number
@@ -112,6 +118,32 @@ __host__ __device__ __forceinline__ uint32_t tail_workgroups(uint32_t logn) {
     return n > per_wg ? n / per_wg : 1u;
 }
 
+// row_leaf_walk's compression by the four lanes of a quad, for rows of ONE block (a pair: 32 bytes): lane 0 lays the block out in the
+// quad's 17 words of LDS, the quad runs the compression of blake2b_block_4lane on the walk's own initial state, counter and final flag,
+// and lane j leaves digest words j and 4 + j in h[0] and h[1]
+struct QuadCompress {
+    uint64_t* msg;
+    uint32_t j;
+    __device__ __forceinline__ void operator()(uint64_t h[8], const uint64_t m[16], uint64_t t, bool last) const {
+        if (j == 0) {
+#pragma unroll
+            for (int w = 0; w < 16; ++w) msg[w] = m[w];
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const uint32_t sh = 8u * j;
+        const uint64_t h_a = j == 0 ? h[0] : (j == 1 ? h[1] : (j == 2 ? h[2] : h[3])), h_b = j == 0 ? h[4] : (j == 1 ? h[5] : (j == 2 ? h[6] : h[7]));
+        const uint64_t iv_a = B2_IV[j], iv_b = B2_IV[4 + j];
+        uint64_t a = h_a, b = h_b, c = iv_a, d = iv_b;
+        if (j == 0) d ^= t;
+        if (j == 2 && last) d = ~d;
+        B2_ROUNDS4();
+        h[0] = h_a ^ a ^ c;
+        h[1] = h_b ^ b ^ d;
+    }
+};
+
+// PAIRS: the pair form (see the head of this file); false: the decimal leaves of merkle.cuh
+template <bool PAIRS>
 __global__ void __launch_bounds__(256) fri_tail_kernel(const TailParams P) {
     __shared__ uint64_t linA[128 * 17], linB[64 * 17];     // up to 256 resp. 128 digests in the lin layout (linB: also the leaf messages)
     __shared__ Fe s_alpha;
@@ -123,12 +155,13 @@ __global__ void __launch_bounds__(256) fri_tail_kernel(const TailParams P) {
     const Fe* prev = P.in0;
     for (uint32_t r = 0; r < P.rounds; ++r) {
         const uint32_t logn = P.log_n0 - r, n = 1u << logn;
-        const bool quad = logn <= TAIL_QUAD_LOG;
+        const uint32_t leaves = PAIRS ? n >> 1 : n;                  // of this round's tree
+        const bool quad = (PAIRS ? logn - 1u : logn) <= TAIL_QUAD_LOG;
         const uint32_t per_wg = quad ? 64u : 256u;
-        const uint32_t nwg = n > per_wg ? n / per_wg : 1u;           // workgroups at work in this round
-        const uint32_t here = n < per_wg ? n : per_wg;               // leaves of each of them
+        const uint32_t nwg = leaves > per_wg ? leaves / per_wg : 1u; // workgroups at work in this round
+        const uint32_t here = leaves < per_wg ? leaves : per_wg;     // leaves of each of them
         uint64_t* const levels = P.rd[r].levels;
-        auto level_off = [n](uint32_t l) -> uint64_t { return l == 0 ? 0 : 2ull * n - ((uint64_t)n >> (l - 1)); };
+        auto level_off = [leaves](uint32_t l) -> uint64_t { return l == 0 ? 0 : 2ull * leaves - ((uint64_t)leaves >> (l - 1)); };
         const bool last_round = r + 1 == P.rounds;
         uint32_t l = 0;                                               // level held in LDS
         uint64_t* src = linA;
@@ -143,7 +176,48 @@ __global__ void __launch_bounds__(256) fri_tail_kernel(const TailParams P) {
                 const Fe w = mont_mul(mont_mul(P.pw_lo[e & 4095u], P.pw_hi[e >> 12]), c_m);
                 return fe_add(fe_half(fe_add(a, b)), mont_mul(fe_sub(a, b), w));
             };
-            if (quad) {
+            // pair form: a pair's two members (pair_fold_lane), folded one after the other and stored by the `storing` lanes -- to the
+            // pinned block as well when they are the last codeword's
+            auto fold_pair = [&](uint32_t i, bool storing) -> PairSource {
+                const PairFoldLane F = pair_fold_lane(i, leaves);
+                PairSource pair;
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    const Fe a = ld_fe_agent(prev + F.in[2 * k]), b = ld_fe_agent(prev + F.in[2 * k + 1]);
+                    const uint64_t e = F.exp[k] << r;                  // the existing two-level table: (1/omega_r)^x = (1/omega_0)^(x 2^r)
+                    const Fe w = mont_mul(mont_mul(P.pw_lo[e & 4095u], P.pw_hi[e >> 12]), c_m);
+                    pair.v[k] = fe_add(fe_half(fe_add(a, b)), mont_mul(fe_sub(a, b), w));
+                    if (storing) {
+                        st_fe_agent(P.rd[r].out + F.out[k], pair.v[k]);
+                        if (last_round && n <= TAIL_LAST_MAX) { P.host->last[F.out[k]].lo = pair.v[k].lo; P.host->last[F.out[k]].hi = pair.v[k].hi; }
+                    }
+                }
+                return pair;
+            };
+            if constexpr (PAIRS) {
+                if (quad) {
+                    const uint32_t q = t >> 2, j = t & 3u, i = wg * 64u + q;
+                    if (q < here) {
+                        const PairSource pair = fold_pair(i, j == 0);  // (all four lanes: the same loads, the same arithmetic)
+                        uint64_t h[8];
+                        row_leaf_walk(2u, pair, QuadCompress{linB + 17u * q, j}, h);
+                        linA[lin_off(q) + j] = h[0];
+                        linA[lin_off(q) + 4u + j] = h[1];
+                        levels[8ull * i + j] = h[0];
+                        levels[8ull * i + 4u + j] = h[1];
+                    }
+                } else {
+                    const uint32_t i = wg * 256u + t;
+                    const PairSource pair = fold_pair(i, true);
+                    uint64_t h[8];
+                    row_leaf_walk(2u, pair, RowColumns::Compress{}, h);
+                    ulonglong2* o = reinterpret_cast<ulonglong2*>(levels + 8ull * i);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) o[k] = make_ulonglong2(h[2 * k], h[2 * k + 1]);
+#pragma unroll
+                    for (int w = 0; w < 8; ++w) linA[lin_off(t) + w] = h[w];
+                }
+            } else if (quad) {
                 const uint32_t q = t >> 2, j = t & 3u, i = wg * 64u + q;
                 uint32_t len = 0;
                 if (q < here) {
@@ -213,7 +287,7 @@ __global__ void __launch_bounds__(256) fri_tail_kernel(const TailParams P) {
         }
         // workgroups any LATER round needs (not monotone: 2^15 leaves are 128 workgroups of 256, 2^14 leaves 256 workgroups of 64)
         uint32_t nwg_next = 0;
-        for (uint32_t k = r + 1; k < P.rounds; ++k) { const uint32_t w = tail_workgroups(P.log_n0 - k); nwg_next = w > nwg_next ? w : nwg_next; }
+        for (uint32_t k = r + 1; k < P.rounds; ++k) { const uint32_t w = tail_workgroups(P.log_n0 - k - (PAIRS ? 1u : 0u)); nwg_next = w > nwg_next ? w : nwg_next; }
         if (wg == 0) {
             if (nwg > 1) {
                 if (t == 0) {

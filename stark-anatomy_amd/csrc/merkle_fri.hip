@@ -1,5 +1,6 @@
 // merkle_fri.hip -- Merkle trees (code/merkle.py), the split-and-fold of code/fri.py:85, the commit loop of Fri.commit with the
 // Fiat-Shamir step of code/ip.py:18-25 on the host side of the library, and the openings of the query phase.
+#define SC_ROWS_NO_KERNELS      // merkle_rows.cuh / fri_pairs.cuh: their leaf stages only (the pair form of the tail kernel)
 #include "core.h"
 #include "merkle.cuh"
 #include "merkle_forest.cuh"
@@ -504,13 +505,15 @@ constexpr int TAIL_GAVE_UP = 2;           // a launch whose wait timed out: the 
 // it polls the root's pinned slot, hashes the transcript and writes the next challenge to the pinned word the kernel polls.
 // SC_OK: trees_out / vecs_out / roots_out / alphas_out filled to the end (and *last_there set when `last_host` got the last codeword);
 // TAIL_NOT_TAKEN: the shape is not the kernel's; TAIL_GAVE_UP: a wait inside it timed out -- either way nothing the caller holds has changed.
+// pairs: the pair form (fri_tail_kernel<true>): codeword k of nk elements under a tree of nk / 2 leaves and nk - 1 digests.
 static int fri_tail_rounds(std::unique_lock<std::mutex>& lk, const Fe* cur, uint64_t n, Fe alpha0, Fe off, Fe om, uint32_t first, uint32_t rounds,
                            std::vector<uint8_t>& items, uint64_t prior_count, sc_vec_t** vecs_out, sc_merkle_t** trees_out, uint8_t* roots_out,
-                           uint64_t* alphas_out, hipStream_t st, Fe* last_host, bool* last_there, const std::function<void()>* on_last) {
+                           uint64_t* alphas_out, hipStream_t st, Fe* last_host, bool* last_there, const std::function<void()>* on_last, bool pairs = false) {
     if (g.fri_tail < 0) { const char* e = getenv("STARKCORE_FRI_TAIL"); g.fri_tail = (e && atoi(e) == 0) ? 0 : 1; }      // (sc_set_tuning("fri_tail") overrides)
     const uint32_t R = rounds - first;
     const uint64_t n0 = n / 2;
-    if (!g.fri_tail || R < 1 || R >= (uint32_t)TAIL_MAX_ROUNDS || n0 > (1ull << TAIL_MAX_LOG) || (n0 >> (R - 1)) < 1) return TAIL_NOT_TAKEN;
+    if (!g.fri_tail || R < 1 || R >= (uint32_t)TAIL_MAX_ROUNDS || n0 > (1ull << TAIL_MAX_LOG) || (n0 >> (R - 1)) < (pairs ? 2u : 1u)) return TAIL_NOT_TAKEN;
+    const auto tree_leaves = [pairs](uint64_t nk) -> uint64_t { return pairs ? nk / 2 : nk; };
     PowTables* pw;
     Fe i2o;
     SCCHK(fold_constants(n, off, om, st, &pw, &i2o));
@@ -534,7 +537,7 @@ static int fri_tail_rounds(std::unique_lock<std::mutex>& lk, const Fe* cur, uint
     const size_t items_before = items.size();
     auto give_back = [&](bool clean) {
         for (size_t k = 0; k < new_vecs.size(); ++k) pool_free(new_vecs[k], ((n0 >> (k + 1)) ? (n0 >> (k + 1)) : 1) * sizeof(Fe));
-        for (size_t k = 0; k < new_levels.size(); ++k) pool_free(new_levels[k], (2 * (n0 >> k) - 1) * 64);
+        for (size_t k = 0; k < new_levels.size(); ++k) pool_free(new_levels[k], (2 * tree_leaves(n0 >> k) - 1) * 64);
         items.resize(items_before);
         if (clean) g_tail_ctl_free.push_back(ctl);
         else if (hipMemset(ctl, 0, sizeof(TailCtl)) == hipSuccess) g_tail_ctl_free.push_back(ctl);      // counters of an aborted call
@@ -550,15 +553,16 @@ static int fri_tail_rounds(std::unique_lock<std::mutex>& lk, const Fe* cur, uint
             new_vecs.push_back(out);
         }
         uint64_t* levels = nullptr;
-        if (pool_alloc((void**)&levels, (2 * nk - 1) * 64) != hipSuccess) { give_back(true); return fail(SC_ERR_HIP, "out of device memory"); }
+        if (pool_alloc((void**)&levels, (2 * tree_leaves(nk) - 1) * 64) != hipSuccess) { give_back(true); return fail(SC_ERR_HIP, "out of device memory"); }
         new_levels.push_back(levels);
         P.rd[k].out = out; P.rd[k].levels = levels; P.rd[k].i2o_m = i2o_k;
         const Fe sq = mont_mul(i2o_k, i2o_k);          // the next codeword's offset is this one's squared (fri.py:87): 1/(2 o^2) = 2 (1/(2 o))^2
         i2o_k = fe_add(sq, sq);
     }
     uint32_t nwg = 1;                                          // the widest round's workgroups (a workgroup leaves when no later round needs it)
-    for (uint32_t k = 0; k < R; ++k) nwg = std::max(nwg, tail_workgroups(P.log_n0 - k));
-    hipLaunchKernelGGL(fri_tail_kernel, dim3(nwg), dim3(256), 0, st, P);
+    for (uint32_t k = 0; k < R; ++k) nwg = std::max(nwg, tail_workgroups(P.log_n0 - k - (pairs ? 1u : 0u)));
+    if (pairs) hipLaunchKernelGGL(fri_tail_kernel<true>, dim3(nwg), dim3(256), 0, st, P);
+    else hipLaunchKernelGGL(fri_tail_kernel<false>, dim3(nwg), dim3(256), 0, st, P);
     if (hipGetLastError() != hipSuccess) { give_back(true); return TAIL_NOT_TAKEN; }
     ++g_tail_launches;
     bool aborted = false;
@@ -629,11 +633,11 @@ static int fri_tail_rounds(std::unique_lock<std::mutex>& lk, const Fe* cur, uint
     }
     if (tracing) {
         // device stamps are a 100 MHz counter: 10 ns each
-        fprintf(stderr, "fri_tail_kernel n0=2^%u, %u rounds (%u workgroups); per round, us: leaves | subtree | barrier | top levels + root out | challenge back || host: root seen, challenge written (since launch)\n", P.log_n0, R, nwg);
+        fprintf(stderr, "fri_tail_kernel%s n0=2^%u, %u rounds (%u workgroups); per round, us: leaves | subtree | barrier | top levels + root out | challenge back || host: root seen, challenge written (since launch)\n", pairs ? " (pair leaves)" : "", P.log_n0, R, nwg);
         for (uint32_t k = 0; k < R; ++k) {
             const volatile uint64_t* sp = host->stamps[k];
             auto d = [&](int a, int b) { return (double)(sp[b] - sp[a]) / 100.0; };
-            const bool multi = tail_workgroups(P.log_n0 - k) > 1;
+            const bool multi = tail_workgroups(P.log_n0 - k - (pairs ? 1u : 0u)) > 1;
             fprintf(stderr, "  2^%-2u  %6.1f | %6.1f | %6.1f | %6.1f | %6.1f || %8.1f %8.1f   (round start at %.1f)\n", P.log_n0 - k, d(0, 1), d(1, 2), multi ? d(2, 3) : 0.0, multi ? d(3, 4) : d(2, 4),
                     k + 1 < R ? d(4, 5) : 0.0, host_us.size() > 2 * k ? host_us[2 * k] : 0.0, host_us.size() > 2 * k + 1 ? host_us[2 * k + 1] : 0.0, (double)(sp[0] - host->stamps[0][0]) / 100.0);
         }
@@ -641,7 +645,7 @@ static int fri_tail_rounds(std::unique_lock<std::mutex>& lk, const Fe* cur, uint
     for (uint32_t k = 0; k < R; ++k) {
         const uint64_t nk = n0 >> k;
         if (k > 0) vecs_out[first + k - 1] = new sc_vec{new_vecs[k - 1], nk};
-        sc_merkle* t = new sc_merkle{new_levels[k], nk, ilog2(nk)};
+        sc_merkle* t = new sc_merkle{new_levels[k], tree_leaves(nk), ilog2(tree_leaves(nk))};
         memcpy(t->root, roots_out + 64 * (first + k), 64);
         t->have_root = true;
         t->st = st;
@@ -655,10 +659,12 @@ static int fri_tail_rounds(std::unique_lock<std::mutex>& lk, const Fe* cur, uint
 static int fri_commit_locked(std::unique_lock<std::mutex>& lk, const void* d_codeword, uint64_t N, const uint64_t offset[2], const uint64_t omega[2], uint32_t rounds,
                              const void* prior_data, const uint32_t* prior_lens, uint64_t prior_count,
                              sc_vec_t** vecs_out, sc_merkle_t** trees_out, uint8_t* roots_out, uint64_t* alphas_out, void* stream,
-                             Fe* last_host = nullptr, bool* last_there = nullptr, const std::function<void()>* on_last = nullptr) {
+                             Fe* last_host = nullptr, bool* last_there = nullptr, const std::function<void()>* on_last = nullptr, bool pairs = false) {
+    // pairs (sc_fri_prove_pairs_dev): every codeword under the tree of its pairs (csrc/fri_pairs.cuh) -- the launches of
+    // sc_merkle_rows_build_async_dev and sc_fri_fold_pairs_commit_dev above the tail's range, fri_tail_kernel<true> from there down
     SCCHK(ensure_init());
     if (!d_codeword || !trees_out || !roots_out || (rounds > 1 && (!vecs_out || !alphas_out)) || rounds < 1) return fail(SC_ERR_BAD_ARG, "null argument");
-    if (N < 2 || !is_pow2(N) || rounds > 60 || (N >> (rounds - 1)) < 1) return fail(SC_ERR_NOT_POW2, "codeword length must be a power of two >= 2 that survives the folds");
+    if (N < 2 || !is_pow2(N) || rounds > 60 || (N >> (rounds - 1)) < (pairs ? 2u : 1u)) return fail(SC_ERR_NOT_POW2, "codeword length must be a power of two >= 2 that survives the folds");
     if (prior_count + rounds > TRANSCRIPT_MAX_ITEMS) return fail(SC_ERR_UNSUPPORTED, "transcript too long for the fixed layout");
     std::vector<uint8_t> items;
     {
@@ -682,7 +688,7 @@ static int fri_commit_locked(std::unique_lock<std::mutex>& lk, const void* d_cod
         for (uint32_t i = 0; i < made_vecs; ++i) { pool_free(vecs_out[i]->d, (vecs_out[i]->n ? vecs_out[i]->n : 1) * sizeof(Fe)); delete vecs_out[i]; vecs_out[i] = nullptr; }
         return rc;
     };
-    int rc = merkle_build_device(cur, n, nullptr, &trees_out[0], st, BUILD_ASYNC);
+    int rc = pairs ? pair_tree_start(cur, n, &trees_out[0], st) : merkle_build_device(cur, n, nullptr, &trees_out[0], st, BUILD_ASYNC);
     if (rc != SC_OK) return rc;
     made_trees = 1;
     for (uint32_t r = 0; r < rounds; ++r) {
@@ -710,12 +716,12 @@ static int fri_commit_locked(std::unique_lock<std::mutex>& lk, const void* d_cod
         alphas_out[2 * r] = alpha.lo; alphas_out[2 * r + 1] = alpha.hi;
         if (!tail_gave_up && n / 2 <= (1ull << TAIL_MAX_LOG)) {
             // from here on every round is latency: the rest of the commit phase is one persistent launch (csrc/fri_tail.cuh)
-            rc = fri_tail_rounds(lk, cur, n, alpha, off, om, r + 1, rounds, items, prior_count, vecs_out, trees_out, roots_out, alphas_out, st, last_host, last_there, on_last);
+            rc = fri_tail_rounds(lk, cur, n, alpha, off, om, r + 1, rounds, items, prior_count, vecs_out, trees_out, roots_out, alphas_out, st, last_host, last_there, on_last, pairs);
             if (rc == SC_OK) return SC_OK;
             if (rc == TAIL_GAVE_UP) tail_gave_up = true;
             else if (rc != TAIL_NOT_TAKEN) return undo(rc);
         }
-        rc = fold_and_build(cur, n, alpha, off, om, nxt->d, &trees_out[r + 1], st);
+        rc = pairs ? fold_pairs_and_build(cur, n, alpha, off, om, nxt->d, &trees_out[r + 1], st) : fold_and_build(cur, n, alpha, off, om, nxt->d, &trees_out[r + 1], st);
         if (rc != SC_OK) return undo(rc);
         ++made_trees;
         cur = nxt->d;
@@ -807,13 +813,29 @@ static inline uint64_t fri_openings_of_codeword(uint32_t j, uint32_t rounds, uin
 // grinding_bits > 0 (sc_fri_prove_grind_dev; Fri(grinding_bits), grinding.py): between the seed over the transcript with the last
 // codeword and the sampling, the smallest nonce accepted with that seed is searched on the call's stream (csrc/grind.hip), appended
 // to the transcript as the plain integer the prover pushes, and the indices are sampled from the hash of THAT transcript.
+//
+// pairs (sc_fri_prove_pairs_dev; Fri(pair_leaves=True), csrc/fri_pairs.cuh): the commit phase over pair trees, the same steps between
+// commit and query, and the openings of the proof with pair leaves -- per codeword j < rounds - 1 the s pairs {cw_j[a], cw_j[a + n_j/2]}
+// and the s paths of leaf a = index mod n_j/2, nothing of the last codeword -- written by fri_pairs_prove_query_kernel together with the
+// caller's further pairs.  `answers`: [pairs, 32 B each][the further pairs' elements, 16 B each][paths][positions u64], each section
+// padded to 256 bytes.
 static int fri_prove(const void* d_codeword, uint64_t N, const uint64_t offset[2], const uint64_t omega[2], uint32_t rounds, uint32_t num_tests,
                      const void* prior_data, const uint32_t* prior_lens, uint64_t prior_count,
                      uint64_t extra_count, const sc_merkle_t* const* extra_trees, const void* const* extra_vecs, uint64_t extra_shift,
                      sc_vec_t** vecs_out, sc_merkle_t** trees_out, uint8_t* roots_out, uint64_t* alphas_out,
                      void* last_codeword_out, uint64_t* top_indices_out, uint64_t* extra_indices_out,
-                     void* answers, uint64_t answers_bytes, void* stream, int grinding_bits, uint64_t* nonce_out) {
+                     void* answers, uint64_t answers_bytes, void* stream, int grinding_bits, uint64_t* nonce_out, bool pairs = false) {
     std::unique_lock<std::mutex> lk(g_mu);
+    if (pairs) {
+        // The pair entry's refusal codes are its header's (include/starkcore.h): BAD_ARG for fewer than two rounds or more tests than the
+        // last codeword holds, NOT_POW2 for a last codeword below two elements -- where the shared checks below, written for the
+        // option-off entries, answer UNSUPPORTED or accept.  This block only gives those codes first; every condition the two forms
+        // share (NULLs, grinding bits, the table's size, the answers' size) is tested once, below.
+        if (!d_codeword || !offset || !omega || !roots_out || rounds < 2 || (prior_count && (!prior_data || !prior_lens)))
+            return fail(SC_ERR_BAD_ARG, "sc_fri_prove_pairs_dev: null argument, or fewer than two rounds");
+        if (rounds > 60 || !is_pow2(N) || (N >> (rounds - 1)) < 2) return fail(SC_ERR_NOT_POW2, "sc_fri_prove_pairs_dev: codeword length must be a power of two with at least two elements in every round");
+        if (num_tests > (N >> (rounds - 1))) return fail(SC_ERR_BAD_ARG, "sc_fri_prove_pairs_dev: more tests than the last codeword has elements");
+    }
     if (grinding_bits < 0 || grinding_bits > 63 || (grinding_bits && !nonce_out)) return fail(SC_ERR_BAD_ARG, "fri prove: 0 .. 63 grinding bits and a place for the nonce expected");
     if (!last_codeword_out || !top_indices_out || !answers || (extra_count && (!extra_trees || !extra_vecs || !extra_indices_out)) || !num_tests)
         return fail(SC_ERR_BAD_ARG, "null argument");
@@ -840,17 +862,20 @@ static int fri_prove(const void* d_codeword, uint64_t N, const uint64_t offset[2
     uint64_t total = 0;
     size_t path_bytes = 0;
     for (uint32_t j = 0; j < rounds; ++j) {
-        const uint64_t k = fri_openings_of_codeword(j, rounds, s);
+        const uint64_t k = pairs ? (j + 1 < rounds ? (uint64_t)s : 0ull) : fri_openings_of_codeword(j, rounds, s);
         total += k;
-        path_bytes += k * 64 * (size_t)ilog2(N >> j);
+        path_bytes += k * 64 * (size_t)ilog2(pairs ? (N >> j) / 2 : N >> j);
     }
+    const uint64_t pair_openings = pairs ? total : 0;          // (pairs: 32 bytes each, a section of their own in front of the further pairs' elements)
     total += extra_count * 4ull * s;
     path_bytes += extra_count * 4ull * s * 64 * (size_t)ilog2(N);
-    const size_t el_bytes = (total * sizeof(Fe) + 255) & ~(size_t)255;
-    if (answers_bytes < el_bytes + path_bytes + total * 8) return fail(SC_ERR_BAD_ARG, "answer buffer too small");
+    const size_t pair_bytes = (pair_openings * 2 * sizeof(Fe) + 255) & ~(size_t)255;
+    const size_t el_bytes = pair_bytes + (((total - pair_openings) * sizeof(Fe) + 255) & ~(size_t)255);      // everything in front of the paths
+    const size_t path_span = pairs ? (path_bytes + 255) & ~(size_t)255 : path_bytes;                          // the paths' section
+    if (answers_bytes < el_bytes + path_span + total * 8) return fail(SC_ERR_BAD_ARG, "answer buffer too small");
     {
         const auto live = g_host_live.find(answers);           // a buffer of sc_host_alloc is written by the kernel: its real size counts, not the caller's word
-        if (live != g_host_live.end() && live->second < el_bytes + path_bytes + total * 8) return fail(SC_ERR_BAD_ARG, "answer buffer too small");
+        if (live != g_host_live.end() && live->second < el_bytes + path_span + total * 8) return fail(SC_ERR_BAD_ARG, "answer buffer too small");
     }
     // STARKCORE_FRI_TIMING=1: the call's phases on stderr (host clock, microseconds) -- tools/fri_prove_timing.py
     static const bool timing = getenv("STARKCORE_FRI_TIMING") != nullptr;
@@ -897,7 +922,7 @@ static int fri_prove(const void* d_codeword, uint64_t N, const uint64_t offset[2
     const std::function<void()> on_last = pickle_transcript;
     bool last_there = false;       // the persistent tail kernel hands the last codeword over with its roots
     int rc = fri_commit_locked(lk, d_codeword, N, offset, omega, rounds, prior_data, prior_lens, prior_count, vecs_out, trees_out, roots_out, alphas_out, stream,
-                               (Fe*)last_codeword_out, &last_there, &on_last);
+                               (Fe*)last_codeword_out, &last_there, &on_last, pairs);
     if (rc != SC_OK) return rc;
     stamp(1);
     hipStream_t st = pick_stream(stream);
@@ -942,12 +967,15 @@ static int fri_prove(const void* d_codeword, uint64_t N, const uint64_t offset[2
     stamp(7);
     // positions: written where the kernel reads them (behind the answers)
     uint8_t* const base = (uint8_t*)answers;
-    uint64_t* idx = (uint64_t*)(base + el_bytes + path_bytes);
+    uint64_t* idx = (uint64_t*)(base + el_bytes + path_span);
     std::vector<uint64_t> cur(top_indices_out, top_indices_out + s), prev;
     uint64_t at = 0;
     for (uint32_t j = 0; j < rounds; ++j) {
         const uint64_t half = (N >> j) / 2;
-        if (j + 1 < rounds) {
+        if (pairs) {
+            // leaf a = index mod n_j / 2 of codeword j's pair tree; nothing of the last codeword is opened
+            if (j + 1 < rounds) for (uint32_t t = 0; t < s; ++t) idx[at++] = top_indices_out[t] % half;
+        } else if (j + 1 < rounds) {
             for (uint32_t t = 0; t < s; ++t) cur[t] %= half;
             for (uint32_t t = 0; t < s; ++t) idx[at++] = cur[t];
             for (uint32_t t = 0; t < s; ++t) idx[at++] = cur[t] + half;
@@ -982,37 +1010,66 @@ static int fri_prove(const void* d_codeword, uint64_t N, const uint64_t offset[2
         }
     } else {
         void* buf;
-        rc = scratch(5, el_bytes + path_bytes + total * 8 + 256, &buf);
+        rc = scratch(5, el_bytes + path_span + total * 8 + 256, &buf);
         if (rc != SC_OK) return undo(rc);
-        d_el = (Fe*)buf; d_paths = (uint64_t*)((char*)buf + el_bytes); d_idx = (const uint64_t*)((char*)buf + el_bytes + path_bytes);
+        d_el = (Fe*)buf; d_paths = (uint64_t*)((char*)buf + el_bytes); d_idx = (const uint64_t*)((char*)buf + el_bytes + path_span);
         if (hipMemcpyAsync((void*)d_idx, idx, total * 8, hipMemcpyHostToDevice, st) != hipSuccess) return undo(fail(SC_ERR_HIP, "index upload"));
-    }
-    QueryTrees Q;
-    Q.count = 0;
-    Q.total_threads = 0;
-    uint64_t off = 0, poff = 0;
-    for (uint64_t t = 0; t < rounds + extra_count; ++t) {
-        const bool own = t < rounds;
-        const sc_merkle* tree = own ? trees_out[t] : extra_trees[t - rounds];
-        const uint64_t k = own ? fri_openings_of_codeword((uint32_t)t, rounds, s) : 4ull * s;
-        if (!k) continue;
-        QueryTree& T = Q.t[Q.count++];
-        T.levels = tree->d_levels;
-        T.elems = own ? (t == 0 ? (const Fe*)d_codeword : vecs_out[t - 1]->d) : (const Fe*)extra_vecs[t - rounds];
-        T.N = tree->N;
-        T.logN = (uint32_t)tree->logN;
-        T.per_query = 4 * T.logN + 1;
-        T.thread_off = Q.total_threads;
-        T.idx_off = off;
-        T.path_off = poff;
-        Q.total_threads += k * T.per_query;
-        off += k;
-        poff += k * (uint64_t)tree->logN;
     }
     QueryDone done;
     const uint64_t seq = ++g_query_seq;
     if (direct) { done.ticket = g_query_ticket; done.host_flag = g_query_flag; done.seq = seq; }
-    hipLaunchKernelGGL(merkle_query_multi_kernel, dim3((unsigned)((Q.total_threads + 255) / 256)), dim3(256), 0, st, Q, d_idx, d_el, d_paths, done);
+    if (pairs) {
+        // codeword j < rounds - 1 under its pair tree, then the caller's ordinary trees: one table, one launch
+        ProveOpenings O;
+        PairTrees& Q = O.Q;
+        Q.count = 0;
+        Q.total_threads = 0;
+        O.pair_trees = (int)rounds - 1;
+        O.pair_openings = pair_openings;
+        uint64_t off = 0, poff = 0;
+        for (uint64_t t = 0; t + 1 < rounds + extra_count; ++t) {
+            const bool own = t + 1 < rounds;
+            const sc_merkle* tree = own ? trees_out[t] : extra_trees[t - (rounds - 1)];
+            const uint64_t k = own ? (uint64_t)s : 4ull * s;
+            PairTree& T = Q.t[Q.count++];
+            T.levels = tree->d_levels;
+            T.elems = own ? (t == 0 ? (const Fe*)d_codeword : vecs_out[t - 1]->d) : (const Fe*)extra_vecs[t - (rounds - 1)];
+            T.L = tree->N;
+            T.logL = (uint32_t)tree->logN;
+            T.per_query = own ? (uint32_t)pair_query_threads(T.logL) : 4 * T.logL + 1;
+            T.thread_off = Q.total_threads;
+            T.idx_off = off;
+            T.path_off = poff;
+            Q.total_threads += k * T.per_query;
+            off += k;
+            poff += k * (uint64_t)tree->logN;
+        }
+        hipLaunchKernelGGL(fri_pairs_prove_query_kernel, dim3((unsigned)((Q.total_threads + 255) / 256)), dim3(256), 0, st, O, d_idx, d_el, (Fe*)((char*)d_el + pair_bytes), d_paths, done);
+    } else {
+        QueryTrees Q;
+        Q.count = 0;
+        Q.total_threads = 0;
+        uint64_t off = 0, poff = 0;
+        for (uint64_t t = 0; t < rounds + extra_count; ++t) {
+            const bool own = t < rounds;
+            const sc_merkle* tree = own ? trees_out[t] : extra_trees[t - rounds];
+            const uint64_t k = own ? fri_openings_of_codeword((uint32_t)t, rounds, s) : 4ull * s;
+            if (!k) continue;
+            QueryTree& T = Q.t[Q.count++];
+            T.levels = tree->d_levels;
+            T.elems = own ? (t == 0 ? (const Fe*)d_codeword : vecs_out[t - 1]->d) : (const Fe*)extra_vecs[t - rounds];
+            T.N = tree->N;
+            T.logN = (uint32_t)tree->logN;
+            T.per_query = 4 * T.logN + 1;
+            T.thread_off = Q.total_threads;
+            T.idx_off = off;
+            T.path_off = poff;
+            Q.total_threads += k * T.per_query;
+            off += k;
+            poff += k * (uint64_t)tree->logN;
+        }
+        hipLaunchKernelGGL(merkle_query_multi_kernel, dim3((unsigned)((Q.total_threads + 255) / 256)), dim3(256), 0, st, Q, d_idx, d_el, d_paths, done);
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return undo(fail(SC_ERR_HIP, hipGetErrorString(e)));
     stamp(5);
@@ -1033,7 +1090,8 @@ static int fri_prove(const void* d_codeword, uint64_t N, const uint64_t offset[2
             if (e != hipSuccess || __atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq) return undo(fail(SC_ERR_HIP, "the query kernel did not complete"));
         }
     } else {
-        if (hipMemcpyAsync(base, d_el, total * sizeof(Fe), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        // (pairs: both sections in front of the paths lie in the staging buffer as they do in the answers)
+        if (hipMemcpyAsync(base, d_el, pairs ? pair_bytes + (total - pair_openings) * sizeof(Fe) : total * sizeof(Fe), hipMemcpyDeviceToHost, st) != hipSuccess ||
             (path_bytes && hipMemcpyAsync(base + el_bytes, d_paths, path_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) ||
             hipStreamSynchronize(st) != hipSuccess)
             return undo(fail(SC_ERR_HIP, "copy of the openings failed"));
@@ -1042,8 +1100,8 @@ static int fri_prove(const void* d_codeword, uint64_t N, const uint64_t offset[2
     if (timing) {
         stamp(6);
         auto us = [&](int a, int b) { return std::chrono::duration<double, std::micro>(tp[b] - tp[a]).count(); };
-        fprintf(stderr, "sc_fri_prove_dev N=2^%d: commit %.1f | last codeword to host %.1f | pickle + shake %.1f | sample indices %.1f | positions %.1f | launch %.1f | "
-                        "wait for the openings (%s) %.1f | total %.1f us\n", ilog2(N), us(0, 1), us(1, 2), us(2, 3), us(3, 7), us(7, 4), us(4, 5), direct ? "pinned" : "staged", us(5, 6), us(0, 6));
+        fprintf(stderr, "%s N=2^%d: commit %.1f | last codeword to host %.1f | pickle + shake %.1f | sample indices %.1f | positions %.1f | launch %.1f | "
+                        "wait for the openings (%s) %.1f | total %.1f us\n", pairs ? "sc_fri_prove_pairs_dev" : "sc_fri_prove_dev", ilog2(N), us(0, 1), us(1, 2), us(2, 3), us(3, 7), us(7, 4), us(4, 5), direct ? "pinned" : "staged", us(5, 6), us(0, 6));
     }
     return SC_OK;
 }
@@ -1066,6 +1124,18 @@ int sc_fri_prove_grind_dev(const void* d_codeword, uint64_t N, const uint64_t of
     return fri_prove(d_codeword, N, offset, omega, rounds, num_tests, prior_data, prior_lens, prior_count, extra_count, extra_trees, extra_vecs, extra_shift,
                      vecs_out, trees_out, roots_out, alphas_out, last_codeword_out, top_indices_out, extra_indices_out, answers, answers_bytes, stream,
                      grinding_bits, nonce_out);
+}
+
+// Fri.prove with pair leaves in one call (include/starkcore.h): fri_prove's pair form
+int sc_fri_prove_pairs_dev(const void* d_codeword, uint64_t N, const uint64_t offset[2], const uint64_t omega[2], uint32_t rounds, uint32_t num_tests,
+                           const void* prior_data, const uint32_t* prior_lens, uint64_t prior_count,
+                           uint64_t extra_count, const sc_merkle_t* const* extra_trees, const void* const* extra_vecs, uint64_t extra_shift,
+                           sc_vec_t** vecs_out, sc_merkle_t** trees_out, uint8_t* roots_out, uint64_t* alphas_out,
+                           void* last_codeword_out, uint64_t* top_indices_out, uint64_t* extra_indices_out,
+                           void* answers, uint64_t answers_bytes, void* stream, int grinding_bits, uint64_t* nonce_out) {
+    return fri_prove(d_codeword, N, offset, omega, rounds, num_tests, prior_data, prior_lens, prior_count, extra_count, extra_trees, extra_vecs, extra_shift,
+                     vecs_out, trees_out, roots_out, alphas_out, last_codeword_out, top_indices_out, extra_indices_out, answers, answers_bytes, stream,
+                     grinding_bits, nonce_out, true);
 }
 
 int sc_merkle_build(const void* elems, uint64_t N, uint8_t root_out[64], sc_merkle_t** tree) {

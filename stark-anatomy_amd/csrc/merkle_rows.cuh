@@ -111,6 +111,9 @@ struct RowColumns {
     __device__ __forceinline__ void leaf(uint64_t row, uint64_t h[8]) const { row_leaf_walk(w, Source{*this, row}, Compress{}, h); }
 };
 
+// SC_ROWS_NO_KERNELS: a translation unit that wants the leaf stages of this header only (merkle_fri.hip: the pair form of the persistent
+// tail kernel hashes pair leaves) defines it; the plain kernels have one home, merkle_rows.hip.
+#ifndef SC_ROWS_NO_KERNELS
 // level 0 of a tree of fewer than 256 leaves (from 256 up the row stage is the entry of merkle_subtree_kernel<true, *, false, RowColumns>)
 __global__ void __launch_bounds__(256) merkle_rows_leaf_kernel(const RowColumns C, uint64_t* __restrict__ digests, uint64_t N) {
     __shared__ uint4 sm[256 * 4];
@@ -144,6 +147,8 @@ __global__ void __launch_bounds__(256) merkle_rows_query_kernel(const RowColumns
     }
 }
 
+#endif  // SC_ROWS_NO_KERNELS
+
 // The segments of a row forest as a kernel argument (forest_climb_kernel's Rows parameter): the table is wave-uniform and read by
 // scalar loads from the kernel-argument segment, the SEGMENT of a column is wave-uniform (columns are walked in step), the TREE is the
 // lane's own -- trees of fewer than 256 rows share a workgroup -- so the address is computed per lane.  Lane (tree, row) reads 16
@@ -164,6 +169,7 @@ struct RowForestColumns {
     }
 };
 
+#ifndef SC_ROWS_NO_KERNELS
 // k opened rows of a row forest in one launch: per position (trees[q], indices[q]) its w values (rows_out [k][w], 16 bytes each) and its
 // authentication path (paths_out, 64 * logN bytes per position, digest l at forest_path_digest).  One thread per value and per 16-byte
 // quarter of a digest.
@@ -186,6 +192,8 @@ __global__ void __launch_bounds__(256) row_forest_query_kernel(const RowSegments
         o[quarter] = s[quarter];
     }
 }
+
+#endif  // SC_ROWS_NO_KERNELS
 
 #endif  // __HIPCC__
 

@@ -182,15 +182,23 @@ int sc_fri_fold_pairs_commit_dev(const void* d_in, uint64_t N, const uint64_t al
     SCCHK(ensure_init());
     if (!tree || !d_in || !d_out || !alpha || !offset || !omega) return fail(SC_ERR_BAD_ARG, "sc_fri_fold_pairs_commit_dev: null argument");
     if (N < 4 || !is_pow2(N)) return fail(SC_ERR_NOT_POW2, "sc_fri_fold_pairs_commit_dev: codeword length must be a power of two >= 4");
-    hipStream_t st = pick_stream(stream);
+    return fold_pairs_and_build((const Fe*)d_in, N, fe_from(alpha), fe_from(offset), fe_from(omega), (Fe*)d_out, tree, pick_stream(stream));
+}
+}  // extern "C"
+
+namespace sci {
+int pair_tree_start(const Fe* d_codeword, uint64_t n, sc_merkle** tree, hipStream_t st) {
+    const void* halves[2] = {d_codeword, d_codeword + n / 2};
+    return rows_build(halves, 2, n / 2, nullptr, tree, st, BUILD_ASYNC);
+}
+int fold_pairs_and_build(const Fe* d_in, uint64_t N, Fe alpha, Fe offset, Fe omega, Fe* d_out, sc_merkle** tree, hipStream_t st) {
     const uint64_t q = N / 4;
     if (q < 256) {
-        SCCHK(fold_device((const Fe*)d_in, N, fe_from(alpha), fe_from(offset), fe_from(omega), (Fe*)d_out, st));
-        const void* halves[2] = {d_out, (const Fe*)d_out + q};
-        return rows_build(halves, 2, q, nullptr, tree, st, BUILD_ASYNC);
+        SCCHK(fold_device(d_in, N, alpha, offset, omega, d_out, st));
+        return pair_tree_start(d_out, N / 2, tree, st);
     }
     PairFold P;
-    SCCHK(fold_prepare((const Fe*)d_in, N, fe_from(alpha), fe_from(offset), fe_from(omega), (Fe*)d_out, st, &P.f));
+    SCCHK(fold_prepare(d_in, N, alpha, offset, omega, d_out, st, &P.f));
     P.q = q;
     // the launch plan of the row stage (rows_build): nlev levels of every 256-leaf subtree behind the leaves, four lanes per hash on
     // the narrow levels of a latency-bound launch
@@ -200,6 +208,9 @@ int sc_fri_fold_pairs_commit_dev(const void* d_in, uint64_t N, const uint64_t al
     };
     return merkle_build_device(nullptr, q, nullptr, tree, st, BUILD_ASYNC, nullptr, &leaves);
 }
+}  // namespace sci
+
+extern "C" {
 
 // every opening of a proof's query phase in one launch: codeword j = 2 L_j elements at d_codewords[j] under the pair tree trees[j] of
 // L_j leaves; counts[j] of the concatenated `indices` belong to it; per opening the pair (32 bytes) and the path (64 * log2 L_j bytes),

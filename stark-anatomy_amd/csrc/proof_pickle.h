@@ -10,6 +10,7 @@
 //   list (top level and nested)      ]  MEMOIZE  [ item APPEND | ( MARK items... APPENDS, in batches of 1000 ) ]
 //   bytes, fresh object              SHORT_BINBYTES / BINBYTES  MEMOIZE   (>= 64 KiB: outside any frame, as _Pickler_write_bytes does)
 //   tuple of three                   items  TUPLE3  MEMOIZE
+//   tuple of two                     items  TUPLE2  MEMOIZE
 //   algebra.FieldElement, first use  global (module and name strings memoized, STACK_GLOBAL, MEMOIZE)  )  NEWOBJ  MEMOIZE
 //                                    }  MEMOIZE  (  'value' int  'field' <Field object>  SETITEMS  BUILD
 //     the same OBJECT again          BINGET / LONG_BINGET of its memo index -- identity is part of the description (`key`)
@@ -44,6 +45,12 @@
 //                            codeword's a or b (the same position, opened once); 4 s (k - 1) items, as k - 1 'R' ops would produce
 //   'P' u32 k  u32 field  u64 key_base  u32 depth  u64 positions  u64 values  u64 paths
 //                            as 'O', positions u64
+//   'X' u32 s  u32 field  u32 k  | k x (u64 key_base, u32 depth) | u64 pairs  u64 paths  u64 positions
+//                            the query phase of a proof with pair leaves (Fri(pair_leaves=True), the pinned answers of
+//                            sc_fri_prove_pairs_dev) over k opened codewords: codeword j has 2^depth_j pair leaves; its s openings lie in
+//                            the three arrays codeword after codeword -- pairs 32 bytes each (cw[a], cw[a + 2^depth_j]), paths 64 depth_j
+//                            bytes each, positions (the leaf numbers a) u64 each; per codeword s tuples of TWO elements (items  TUPLE2
+//                            MEMOIZE; keys key_base_j | a and key_base_j | (a + 2^depth_j)), then the s paths: 2 s k items
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -249,10 +256,41 @@ struct ProofPickler {
         const uint8_t op = *p++;
         auto u32 = [&](uint32_t* v) { if (end - p < 4) return false; memcpy(v, p, 4); p += 4; return true; };
         auto u64 = [&](uint64_t* v) { if (end - p < 8) return false; memcpy(v, p, 8); p += 8; return true; };
-        if (op == 'Q' || op == 'P') {                      // several items of the enclosing list, payload by address
+        if (op == 'Q' || op == 'P' || op == 'X') {         // several items of the enclosing list, payload by address
             if (!L) return nullptr;
             uint32_t k, f;
             if (!u32(&k) || !u32(&f) || f >= nfields) return nullptr;
+            if (op == 'X') {
+                // 'X': k = s here, then the number of opened codewords; per codeword s pairs, then s paths
+                const uint32_t s_ = k;
+                uint32_t nk;
+                if (!u32(&nk) || nk < 1 || nk > 64 || (size_t)(end - p) < (size_t)nk * 12 + 24) return nullptr;
+                uint64_t base[64]; uint32_t depth[64];
+                for (uint32_t j = 0; j < nk; ++j) { memcpy(&base[j], p, 8); memcpy(&depth[j], p + 8, 4); p += 12; if (depth[j] > 31) return nullptr; }
+                uint64_t p_pair, p_path, p_pos;
+                if (!u64(&p_pair) || !u64(&p_path) || !u64(&p_pos) || (s_ && (!p_pair || !p_pos))) return nullptr;
+                if (L->done + 2ull * s_ * nk > L->count) return nullptr;
+                const uint8_t *pairs = (const uint8_t*)(uintptr_t)p_pair, *paths = (const uint8_t*)(uintptr_t)p_path;
+                const uint64_t* pos = (const uint64_t*)(uintptr_t)p_pos;
+                size_t po = 0;
+                for (uint32_t j = 0; j < nk; ++j) {
+                    if (s_ && depth[j] && !paths) return nullptr;
+                    const uint64_t leaves = 1ull << depth[j];
+                    const size_t o = (size_t)s_ * j;
+                    for (uint32_t t = 0; t < s_; ++t) {
+                        const uint64_t a = pos[o + t];
+                        item_begin(*L);
+                        boundary();                                // save(tuple)
+                        save_element(f, base[j] | (uint32_t)a, pairs + 32 * (o + t));
+                        save_element(f, base[j] | (uint32_t)(a + leaves), pairs + 32 * (o + t) + 16);
+                        put(0x86); memoize();                      // TUPLE2 MEMOIZE
+                        item_end(*L);
+                    }
+                    for (uint32_t t = 0; t < s_; ++t) { item_begin(*L); save_path(paths + po + (size_t)t * 64 * depth[j], depth[j]); item_end(*L); }
+                    po += (size_t)s_ * 64 * depth[j];
+                }
+                return p;
+            }
             if (op == 'P') {
                 uint64_t base, p_pos, p_val, p_path; uint32_t depth;
                 if (!u64(&base) || !u32(&depth) || !u64(&p_pos) || !u64(&p_val) || !u64(&p_path)) return nullptr;

@@ -505,6 +505,9 @@ class Fri:
         FastStark's committed codewords (fast_stark.py:154-175) -- fetched in the SAME device round trip as the query phase"""
         assert(self.domain_length == len(codeword)), "initial codeword length does not match length of initial codeword"
         if self.pair_leaves:
+            top_level_indices = self._prove_pairs_in_library(codeword, proof_stream, also_open) if Fri.PAIRS_IN_LIBRARY else None
+            if top_level_indices is not None:
+                return top_level_indices
             return self._prove_pairs(codeword, proof_stream, also_open)
         top_level_indices = self._prove_in_library(codeword, proof_stream, also_open)
         if top_level_indices is not None:
@@ -802,6 +805,83 @@ class Fri:
                     proof_stream.push(obj)
 
     # -- pair leaves --------------------------------------------------------------------
+    PAIRS_IN_LIBRARY = True          # False: `prove` with pair_leaves always takes the round-by-round route (_prove_pairs); tests and tools compare the two
+
+    def _prove_pairs_in_library(self, codeword, proof_stream, also_open):
+        """`prove` with pair_leaves as ONE library call (sc_fri_prove_pairs_dev): commit phase over pair trees (the persistent tail
+        kernel's pair form from 2^16 elements down), last codeword, proof of work, indices, and one kernel that writes every pair,
+        every path and also_open's openings into pinned host memory.  What comes back is pushed as _prove_pairs pushes it -- roots,
+        the last codeword, the nonce, per round s pairs and s paths -- in described form (proof_objects.FriPairsQueryPhase).  Served
+        under the conditions of _prove_in_library; None otherwise, and _prove_pairs then runs with the same bytes."""
+        import ctypes
+        import numpy as np
+        rounds, s = self.num_rounds(), self.num_colinearity_tests
+        N = self.domain_length
+        if not (isinstance(codeword, DeviceCodeword) and _po.eligible(codeword) and codeword._tree is None and N >= 2 and N & (N - 1) == 0):
+            return None
+        if rounds < 2 or (N >> (rounds - 1)) < 2:
+            return None
+        if self.field.p != Field.P_MAIN or s > (N >> (rounds - 1)) or s < 1 or library_transcript(proof_stream, rounds) is None:
+            return None
+        extra = []
+        if also_open is not None:
+            extra = also_open.codewords
+            if extra is None or also_open.shift is None or not all(isinstance(cw, DeviceCodeword) and _po.eligible(cw) and len(cw) == N for cw in extra):
+                return None
+        if rounds + len(extra) > 32:
+            return None
+        self._check_omega_order(N)
+        prior = list(proof_stream.objects)
+        k, ne = len(prior), len(extra)
+        roots = ctypes.create_string_buffer(64 * rounds)
+        last_raw = ctypes.create_string_buffer(16 * (N >> (rounds - 1)))
+        top = (ctypes.c_uint64 * s)()
+        quad = (ctypes.c_uint64 * (4 * s))()
+        # the four sections of `answers` (include/starkcore.h): pairs, also_open's elements, paths, positions
+        opened = rounds - 1
+        depths = [(N >> (j + 1)).bit_length() - 1 for j in range(opened)]                  # log2 of codeword j's n_j / 2 pair leaves
+        depth0 = N.bit_length() - 1
+        pair_bytes = (32 * s * opened + 255) & ~255
+        element_bytes = (16 * 4 * s * ne + 255) & ~255
+        own_paths = 64 * s * sum(depths)
+        path_bytes = (own_paths + 64 * 4 * s * depth0 * ne + 255) & ~255
+        total = s * opened + 4 * s * ne
+        # (lifetime of the pinned buffer: see _prove_in_library -- the segments and also_open.answers are views of it)
+        answers = _sc.HostBuffer(pair_bytes + element_bytes + path_bytes + 8 * total)
+        extra_trees = [cw.tree() for cw in extra]
+        nonce = ctypes.c_uint64(0)
+        rc = _sc.lib().sc_fri_prove_pairs_dev(codeword.vec.ptr, N, _sc.fe_bytes(self.offset.value), _sc.fe_bytes(self.omega.value), rounds, s,
+                                              b"".join(prior), (ctypes.c_uint32 * max(1, k))(*map(len, prior)), k,
+                                              ne, (ctypes.c_void_p * max(1, ne))(*[t._h for t in extra_trees]),
+                                              (ctypes.c_void_p * max(1, ne))(*[cw.vec.ptr for cw in extra]), int(also_open.shift) if ne else 0,
+                                              None, None, roots, None, last_raw, top, quad, answers.ptr, answers.nbytes, None,
+                                              self.grinding_bits, ctypes.byref(nonce))
+        if rc == _sc.SC_ERR_UNSUPPORTED:
+            return None
+        _sc._check(rc)
+        raw = roots.raw
+        for r in range(rounds):
+            proof_stream.push(raw[64 * r:64 * r + 64])
+        # (the folded codewords' entries carry the FIELD OBJECT of the codeword they were folded from, as DeviceCodeword.fold_pairs_commit's
+        # do: a proof is pickled by identity)
+        holders = [_po.entries_of(codeword)] + [_po.DetachedEntries(codeword.field) for _ in range(rounds - 1)]
+        lazy = _po.lazy_objects(proof_stream)
+        lazy.add(_po.ElementList(holders[-1], last_raw.raw))
+        if self.grinding_bits:
+            lazy.append(int(nonce.value))
+        data = answers.array
+        paths_at, where_at = pair_bytes + element_bytes, pair_bytes + element_bytes + path_bytes
+        where = data[where_at:where_at + 8 * total].view(np.uint64)
+        lazy.add(_po.FriPairsQueryPhase(holders[:opened], s, depths, data[:32 * s * opened], data[paths_at:paths_at + own_paths], where[:s * opened]))
+        if also_open is not None:
+            fetched, c, stride = [], 4 * s, 64 * depth0
+            for e in range(ne):
+                po = paths_at + own_paths + e * c * stride
+                fetched.append((data[pair_bytes + 16 * c * e:pair_bytes + 16 * c * (e + 1)], data[po:po + c * stride].reshape(c, stride)))
+            also_open.answers = fetched
+            also_open.position_arrays = [where[s * opened + c * e:s * opened + c * (e + 1)] for e in range(ne)]
+        return list(top)
+
     def _prove_pairs(self, codeword, proof_stream, also_open=None):
         """`prove` with pair_leaves: the round-by-round route of _commit_rounds over pair trees (round 0's tree is started first, then
         per round one sc_fri_fold_pairs_commit_dev with the Fiat-Shamir step in Python, so any ProofStream subclass is served), the

@@ -41,6 +41,7 @@ class _Context:
         self.fields = []
         self.seen = set()                                  # ids of the real objects described so far
         self.uids = {}                                     # process-wide codeword id -> small id of this serialization
+        self.keep = []                                     # arrays a description refers to by address that nobody else holds
 
     def uid(self, holder):
         """The codeword's id inside THIS serialization (1, 2, ...).  The pickler's memo key of an element is
@@ -257,6 +258,63 @@ class FriQueryPhase:
 
     def materialize(self):
         return [obj for r in self.rounds() for obj in r.materialize()]
+
+
+class FriPairsQueryPhase:
+    """the query phase of a proof with pair leaves (Fri(pair_leaves=True)), as sc_fri_prove_pairs_dev answered it: views
+    of one pinned buffer.  holders[j]: the entry holder of opened codeword j (every codeword but the last); depths[j]: log2 of its pair
+    tree's leaves; pairs: uint8 view, 32 bytes per opening (cw_j[a], cw_j[a + half]); paths: uint8 view, 64 depths[j] bytes per opening;
+    positions: the leaf numbers a (uint64 view) -- each codeword after codeword, s openings per codeword.  The objects are
+    Fri._prove_pairs': per codeword s tuples of two identity-preserving entries, then s path lists."""
+
+    def __init__(self, holders, s, depths, pairs, paths, positions):
+        self.holders, self.s, self.depths = list(holders), s, list(depths)
+        self.pairs, self.paths, self.positions = pairs, paths, positions
+        self.count = 2 * s * len(self.holders)
+
+    payload_bytes = property(lambda self: int(self.pairs.nbytes + self.paths.nbytes))
+
+    def _round(self, j):
+        """(pairs, paths, positions) of codeword j as views"""
+        s = self.s
+        po = 64 * s * sum(self.depths[:j])
+        return self.pairs[32 * s * j:32 * s * (j + 1)], self.paths[po:po + 64 * s * self.depths[j]], self.positions[s * j:s * (j + 1)]
+
+    def _head(self, ctx, f, holders, depths, pairs, paths, positions):
+        head = _struct.pack("<cIII", b"X", self.s, f, len(holders))
+        per = b"".join(_struct.pack("<QI", ctx.uid(h) << 32, d) for h, d in zip(holders, depths))
+        return head + per + _struct.pack("<QQQ", pairs.ctypes.data, paths.ctypes.data if paths.nbytes else 0, positions.ctypes.data)
+
+    def ops(self, ctx):
+        """the 'X' op of csrc/proof_pickle.h: the three arrays stay where the device wrote them, the description carries their
+        addresses (this segment keeps them alive); arrays that are not contiguous: one 'X' op per codeword over contiguous copies,
+        which the serialization's context keeps until the bytes are written"""
+        if not self.holders or self.s == 0:
+            return b""
+        f = ctx.field_index(self.holders[0].field)
+        if any(ctx.field_index(h.field) != f for h in self.holders):
+            raise _Unsupported("two fields in one query phase")
+        if (self.pairs.flags["C_CONTIGUOUS"] and self.paths.flags["C_CONTIGUOUS"] and self.positions.flags["C_CONTIGUOUS"]
+                and self.positions.dtype == np.uint64 and self.pairs.dtype == np.uint8 and self.paths.dtype == np.uint8):
+            return self._head(ctx, f, self.holders, self.depths, self.pairs, self.paths, self.positions)
+        out = []
+        for j, (holder, depth) in enumerate(zip(self.holders, self.depths)):
+            pairs, paths, positions = self._round(j)
+            copies = (np.ascontiguousarray(pairs, dtype=np.uint8), np.ascontiguousarray(paths, dtype=np.uint8), np.ascontiguousarray(positions, dtype=np.uint64))
+            ctx.keep.append(copies)
+            out.append(self._head(ctx, f, [holder], [depth], *copies))
+        return b"".join(out)
+
+    def materialize(self):
+        s, out = self.s, []
+        for j, (holder, depth) in enumerate(zip(self.holders, self.depths)):
+            pairs, paths, positions = self._round(j)
+            a = [int(i) for i in positions]
+            values = _sc.unpack(np.ascontiguousarray(pairs).tobytes(), 2 * s)
+            entries = holder._entries(a + [i + (1 << depth) for i in a], values[0::2] + values[1::2])
+            out.extend(zip(entries[:s], entries[s:]))
+            out.extend(_sc._path_lists(memoryview(np.ascontiguousarray(paths).tobytes()), 0, depth, s))
+        return out
 
 
 class Openings:

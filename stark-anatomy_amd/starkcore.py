@@ -168,6 +168,8 @@ SIGNATURES = {
     "sc_merkle_row_leaf": (_int, [_vp, _u64, _vp]),
     "sc_fri_fold_pairs_commit_dev": (_int, [_vp, _u64, _vp, _vp, _vp, _vp, ctypes.POINTER(_vp), _vp]),
     "sc_fri_pairs_query_dev": (_int, [_u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sc_fri_prove_pairs_dev": (_int, [_vp, _u64, _vp, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp,
+                                      _vp, _vp, _vp, _vp, _u64, _vp, _int, ctypes.POINTER(_u64)]),
     "sc_merkle_forest_build_dev": (_int, [_vp, _u64, _u64, ctypes.POINTER(_vp), _vp]),
     "sc_fri_fold_forest_dev": (_int, [_vp, _u64, _u64, _vp, _vp, _vp, _vp, ctypes.POINTER(_vp), _vp]),
     "sc_merkle_forest_roots": (_int, [_vp, _vp]),
