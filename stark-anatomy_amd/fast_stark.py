@@ -1148,92 +1148,29 @@ class FastStark:
 
     # -- verifier (fast_stark.py:180-286) -----------------------------------------------------------
     def verify(self, proof, transition_constraints, boundary, transition_zerofier_root, proof_stream=None):
-        stream = (ProofStream() if proof_stream == None else proof_stream).deserialize(proof)
-        registers = range(self.num_registers)
-        trace_rows = 1 + max(cycle for cycle, _, _ in boundary) + self.num_randomizers
-
-        # the commitments, and the combination weights they determine
-        if self.row_commitments:
-            row_root = stream.pull()                     # one tree over the rows of [boundary quotients ..., randomizer]
-        else:
-            quotient_roots = [stream.pull() for _ in registers]
-            randomizer_root = stream.pull()
-        weights = self.sample_weights(1 + 2 * len(transition_constraints) + 2 * self.num_registers, stream.verifier_fiat_shamir())
-
-        # low-degree test of the combination; it reports the combination's values at the points it opened
-        opened = []
-        accepted = self.fri.verify(stream, opened)
-        opened.sort(key=lambda index_value: index_value[0])
-        if not accepted:
-            return False
-
-        # every committed codeword opened at those points and at their successors on the trace domain
-        N, step = self.fri.domain_length, self.expansion_factor
-        positions = sorted([i for i, _ in opened] + [(i + step) % N for i, _ in opened])
-        if self.row_commitments:
-            opened_rows = self._pull_row_openings(stream, row_root, positions)
-            if opened_rows is None:
-                return False
-            quotient_leaves = [{position: row[s] for position, row in opened_rows.items()} for s in registers]
-            randomizer = {position: row[-1] for position, row in opened_rows.items()}
-        else:
-            quotient_leaves = []
-            for root in quotient_roots:
-                quotient_leaves.append(self._pull_openings(stream, root, positions))
-                if quotient_leaves[-1] is None:
-                    return False
-            randomizer = self._pull_openings(stream, randomizer_root, positions)
-            if randomizer is None:
-                return False
-        zerofier_values = self._pull_openings(stream, transition_zerofier_root, positions)
-        if zerofier_values is None:
-            return False
-
-        # the combination recomputed from the openings must agree with FRI's view of it at every queried point
-        zerofiers, interpolants = self.boundary_zerofiers(boundary), self.boundary_interpolants(boundary)
-        max_degree = self.max_degree(transition_constraints)
-        transition_shifts = [max_degree - bound for bound in self.transition_quotient_degree_bounds(transition_constraints)]
-        boundary_shifts = [max_degree - bound for bound in self.boundary_quotient_degree_bounds(trace_rows, boundary)]
-        constraint_at = [constraint.evaluator() for constraint in transition_constraints]      # term lists extracted once, not per point
-
-        def trace_row(index, x):
-            # undo the boundary quotient: trace = quotient * zerofier + interpolant
-            return [quotient_leaves[s][index] * zerofiers[s].evaluate(x) + interpolants[s].evaluate(x) for s in registers]
-
-        for index, claimed in opened:
-            successor = (index + step) % N
-            x = self.generator * (self.omega ^ index)
-            point = [x] + trace_row(index, x) + trace_row(successor, self.generator * (self.omega ^ successor))
-            weight = iter(weights)
-            total = randomizer[index] * next(weight)
-            for evaluate, shift in zip(constraint_at, transition_shifts):
-                quotient = evaluate(point) / zerofier_values[index]
-                total = total + quotient * next(weight) + quotient * (x ^ shift) * next(weight)
-            for s, shift in zip(registers, boundary_shifts):
-                quotient = quotient_leaves[s][index]
-                total = total + quotient * next(weight) + quotient * (x ^ shift) * next(weight)
-            if not (total == claimed):
-                return False
-        return True
+        return self._walk(proof, transition_constraints, boundary, transition_zerofier_root, proof_stream, HostChecks(), None)
 
     def verify_batch(self, proofs, transition_constraints, boundaries, transition_zerofier_root, proof_streams=None):
         """[self.verify(proofs[i], transition_constraints, boundaries[i], transition_zerofier_root, proof_streams[i]) for i ...] with
         every Merkle path and FRI colinearity test of the whole batch checked in one device call per kind (csrc/merkle_verify.cuh).
-        The walk over each proof is `verify`'s, pull for pull; the checks that are cheap on the host (the last codeword, its degree)
-        run here, the rest become rows -- the combination at the opened points too (COMBINATION_ON_DEVICE; one more device call for
-        the batch).  A proof on which `verify` raises is reported False."""
+        The walk over each proof is `verify`'s (_walk); the checks that are cheap on the host (the last codeword, its degree) run in
+        it, the rest become rows -- the combination at the opened points too (COMBINATION_ON_DEVICE; one more device call for the
+        batch).  A proof on which `verify` raises is reported False."""
         if proof_streams is None:
             proof_streams = [None] * len(proofs)
         checks = BatchChecks(len(proofs))
         for owner, (proof, boundary, proof_stream) in enumerate(zip(proofs, boundaries, proof_streams)):
             try:
-                if not self._collect_checks(proof, transition_constraints, boundary, transition_zerofier_root, proof_stream, checks, owner):
+                if not self._walk(proof, transition_constraints, boundary, transition_zerofier_root, proof_stream, checks, owner):
                     checks.reject(owner)
             except Exception:
                 checks.reject(owner)
         return checks.run()
 
-    def _collect_checks(self, proof, transition_constraints, boundary, transition_zerofier_root, proof_stream, checks, owner):
+    def _walk(self, proof, transition_constraints, boundary, transition_zerofier_root, proof_stream, checks, owner):
+        """THE verifier: one walk over a proof whose checks go to `checks` (fri.HostChecks: decided at once, the first failure ends
+        the walk; fri.BatchChecks: rows of proof `owner` for the batch's device calls, the walk goes on), as Fri._walk's do.  False:
+        rejected on the way."""
         stream = (ProofStream() if proof_stream == None else proof_stream).deserialize(proof)
         registers = range(self.num_registers)
         trace_rows = 1 + max(cycle for cycle, _, _ in boundary) + self.num_randomizers
@@ -1248,7 +1185,7 @@ class FastStark:
 
         # low-degree test of the combination; it reports the combination's values at the points it opened
         opened = []
-        accepted = self.fri._collect_checks(stream, opened, checks, owner)
+        accepted = self.fri._walk(stream, opened, checks, owner)
         opened.sort(key=lambda index_value: index_value[0])
         if not accepted:
             return False
@@ -1264,10 +1201,14 @@ class FastStark:
             randomizer = {position: row[-1] for position, row in opened_rows.items()}
         else:
             quotient_leaves = []
-            for root in quotient_roots:
-                quotient_leaves.append(self._collect_openings(stream, root, positions, checks, owner))
-            randomizer = self._collect_openings(stream, randomizer_root, positions, checks, owner)
-        zerofier_values = self._collect_openings(stream, transition_zerofier_root, positions, checks, owner)
+            for root in quotient_roots + [randomizer_root]:
+                quotient_leaves.append(self._pull_openings(stream, root, positions, checks, owner))
+                if quotient_leaves[-1] is None:
+                    return False
+            randomizer = quotient_leaves.pop()
+        zerofier_values = self._pull_openings(stream, transition_zerofier_root, positions, checks, owner)
+        if zerofier_values is None:
+            return False
 
         # the combination recomputed from the openings must agree with FRI's view of it at every queried point
         zerofiers, interpolants = self.boundary_zerofiers(boundary), self.boundary_interpolants(boundary)
@@ -1294,14 +1235,12 @@ class FastStark:
                 total = total + quotient * next(weight) + quotient * (x ^ shift) * next(weight)
             return bool(total == claimed)
 
-        # the opened points become rows of one device call for the whole batch (csrc/combination.cuh); `holds` decides what the rows
-        # cannot hold or the device leaves undecided, and every point when the check stays on the host
+        # in a batch the opened points become rows of one device call for the whole batch (csrc/combination.cuh), and `holds` decides
+        # what the rows cannot hold or the device leaves undecided; without a group of rows -- host checks, or a batch whose
+        # combination stays on the host -- `holds` decides every point here, in order, and the first that fails ends the walk
         group = self._combination_group(checks, transition_constraints, transition_shifts, boundary_shifts) if FastStark.COMBINATION_ON_DEVICE else None
         if group is None:
-            for index, claimed in opened:
-                if not holds(index, claimed):
-                    return False
-            return True
+            return all(holds(index, claimed) for index, claimed in opened)
         member = group.member(weights, zerofiers, interpolants)
         for index, claimed in opened:
             successor = (index + step) % N
@@ -1356,21 +1295,11 @@ class FastStark:
                                    FastStark.COMBINATION_DEVICE_MIN_ROWS, keep=transition_constraints)
         return checks.combination_group(key, make) or None
 
-    @staticmethod
-    def _collect_openings(stream, root, positions, checks, owner):
-        """_pull_openings with the paths recorded in `checks` instead of verified"""
-        leaves = {}
-        for position in positions:
-            leaf, path = stream.pull(), stream.pull()
-            checks.merkle(owner, root, position, path, leaf)
-            leaves[position] = leaf
-        return leaves
-
-    def _pull_row_openings(self, stream, root, positions, checks=None, owner=None):
+    def _pull_row_openings(self, stream, root, positions, checks, owner):
         """{position: row} from the (row, authentication path) pairs of a row commitment, in the order of `positions`; None as soon as
         a row is not a list of num_registers + 1 elements of this field with values below p, a path is not log2 N digests of 64
-        bytes, or the path does not lead from the row's leaf to `root`.  checks: the path is recorded there (a row whose leaf digest
-        the host computed) instead of verified here."""
+        bytes, the root is not a byte string, or `checks` says that the path does not lead from the row's leaf (Merkle.row_leaf,
+        computed here) to `root`"""
         p, width, depth = self.field.p, self.num_registers + 1, self.fri.domain_length.bit_length() - 1
         rows = {}
         for position in positions:
@@ -1380,21 +1309,19 @@ class FastStark:
                 return None
             if type(path) is not list or len(path) != depth or not all(type(d) is bytes and len(d) == 64 for d in path):
                 return None
-            if checks is not None:
-                checks.merkle(owner, root, position, path, None, leaf_digest=Merkle.row_leaf(row))
-            elif not (type(root) is bytes and Merkle.verify_rows(root, position, path, row)):
+            if type(root) is not bytes or not checks.merkle(owner, root, position, path, None, leaf_digest=Merkle.row_leaf(row)):
                 return None
             rows[position] = row
         return rows
 
     @staticmethod
-    def _pull_openings(stream, root, positions):
+    def _pull_openings(stream, root, positions, checks, owner):
         """{position: leaf} from the (leaf, authentication path) pairs the prover pushed for one commitment, in the order of
-        `positions`; None as soon as a path does not lead to `root`"""
+        `positions`; None as soon as `checks` says that a path does not lead to `root`"""
         leaves = {}
         for position in positions:
             leaf, path = stream.pull(), stream.pull()
-            if not Merkle.verify(root, position, path, leaf):
+            if not checks.merkle(owner, root, position, path, leaf):
                 return None
             leaves[position] = leaf
         return leaves

@@ -177,11 +177,15 @@ class BatchChecks:
         self.c_a, self.c_b, self.c_round, self.c_y, self.c_owner, self.rounds = [], [], [], [], [], []
         self.col_points = []                     # per colinearity row: its points, for test_colinearity if the device leaves it undecided
         self.truncations = []                    # (values list, its length before round 0, round 0's colinearity references)
+        self._refs = []                          # the current round's colinearity references: ("row", row index) or ("host", verdict)
         self.combinations = {}                   # key of an (AIR, domain) group -> its CombinationRows
         self.combination_device_rows = 0         # rows sent to sc_stark_combination_batch by `run`
 
-    def reject(self, owner):
+    # Every check answers "go on" (True): a batch walk never stops at a failed check, the verdicts come from `run`.
+    def reject(self, owner, *lines):
+        """the walk gives up on proof `owner`; lines: what HostChecks.reject prints"""
         self.ok[owner] = False
+        return False
 
     def root(self, root):
         """index of a 64-byte root in the root table, or None when the device cannot compare with it"""
@@ -216,7 +220,7 @@ class BatchChecks:
                     digest = Merkle.H(bytes(data_element)).digest()
                 except Exception:
                     self.ok[owner] = False
-                    return
+                    return True
                 kind, leaf = _sc.LEAF_DIGEST, self.n_digests.to_bytes(16, "little")
                 self.digests.append(digest)
                 self.n_digests += 1
@@ -229,16 +233,18 @@ class BatchChecks:
             self.m_owner.append(owner)
             self.digests.append(joined)
             self.n_digests += depth
-            return
+            return True
         try:
             accepted = Merkle.verify(root, index, path, data_element) if leaf_digest is None else Merkle.verify_(root, index, path, leaf_digest)
         except Exception:
             accepted = False
         if not accepted:
             self.ok[owner] = False
+        return True
 
     def round(self, offset, omega, alpha):
-        """a round-table entry (offset_r, omega_r, alpha_r); None when they are not residues of the main field"""
+        """a round begins: its round-table entry (offset_r, omega_r, alpha_r); None when they are not residues of the main field"""
+        self._refs = []
         if not all(type(e) is FieldElement and type(e.value) is int and 0 <= e.value < Field.P_MAIN and e.field.p == Field.P_MAIN
                    for e in (offset, omega, alpha)):
             return None
@@ -246,8 +252,8 @@ class BatchChecks:
         return len(self.rounds) - 1
 
     def colinearity(self, owner, round_index, offset, omega, a, b, alpha, ya, yb, yc):
-        """test_colinearity([(offset * omega^a, ya), (offset * omega^b, yb), (alpha, yc)]) as a row; returns ("row", row index) or
-        ("host", verdict) for `truncate`"""
+        """test_colinearity([(offset * omega^a, ya), (offset * omega^b, yb), (alpha, yc)]) as a row; where its verdict will be found is
+        kept with the round's references, for `truncate`"""
         ys = (ya, yb, yc)
         if round_index is not None and all(type(y) is FieldElement and type(y.value) is int and 0 <= y.value < Field.P_MAIN
                                            and y.field.p == Field.P_MAIN for y in ys) and 0 <= a < (1 << 64) and 0 <= b < (1 << 64):
@@ -257,14 +263,16 @@ class BatchChecks:
             self.c_y.append(ya.value.to_bytes(16, "little") + yb.value.to_bytes(16, "little") + yc.value.to_bytes(16, "little"))
             self.c_owner.append(owner)
             self.col_points.append((offset, omega, a, b, alpha, ya, yb, yc))
-            return ("row", len(self.c_a) - 1)
+            self._refs.append(("row", len(self.c_a) - 1))
+            return True
         try:
             accepted = test_colinearity([(offset * (omega ^ a), ya), (offset * (omega ^ b), yb), (alpha, yc)])
         except Exception:
             accepted = False
         if not accepted:
             self.ok[owner] = False
-        return ("host", accepted)
+        self._refs.append(("host", accepted))
+        return True
 
     def combination_group(self, key, make):
         """the CombinationRows of the (AIR, domain) group `key`, made by make() when the batch meets the group for the first time"""
@@ -334,10 +342,36 @@ class BatchChecks:
                     break
         return [bool(v) for v in ok]
 
-    def truncate(self, values, base, refs):
-        """round 0 appends its pairs to `values` from position `base` on; refs: what `colinearity` returns for its tests, filled in
-        place as they are recorded (a walk that raises half-way leaves the tests recorded so far)"""
-        self.truncations.append((values, base, refs))
+    def truncate(self, values, base):
+        """round 0 (begun with `round`) appends its pairs to `values` from position `base` on: its tests' references, filled in place as
+        `colinearity` records them (a walk that raises half-way leaves the tests recorded so far)"""
+        self.truncations.append((values, base, self._refs))
+
+
+class HostChecks:
+    """BatchChecks' twin for one proof on the host: the same methods, every check decided at once by the function a row of BatchChecks
+    stands for.  A check answers whether the walk goes on: False ends it there, before the next pull.  What raises inside a check
+    propagates to the walk's caller."""
+
+    def reject(self, owner, *lines):
+        for line in lines:
+            print(line)
+        return False
+
+    def merkle(self, owner, root, index, path, data_element, leaf_digest=None):
+        return Merkle.verify(root, index, path, data_element) if leaf_digest is None else Merkle.verify_(root, index, path, leaf_digest)
+
+    def round(self, offset, omega, alpha):
+        return None
+
+    def colinearity(self, owner, round_index, offset, omega, a, b, alpha, ya, yb, yc):
+        return test_colinearity([(offset * (omega ^ a), ya), (offset * (omega ^ b), yb), (alpha, yc)])
+
+    def truncate(self, values, base):
+        pass
+
+    def combination_group(self, key, make):
+        return None                              # (no rows: the walk decides every opened point itself, in order, and stops at the first that fails)
 
 
 class Fri:
@@ -390,6 +424,11 @@ class Fri:
             residues.add(candidate % reduced_size)
             chosen.append(candidate)
         return chosen
+
+    def _round_positions(self, top_level_indices, r):
+        """the `a` positions of round r's colinearity tests: the top-level indices reduced to half of codeword r's length (fri.py:126)"""
+        half = self.domain_length >> (r + 1)
+        return [index % half for index in top_level_indices]
 
     def eval_domain(self):
         # offset * omega^i, i < domain_length, by running product
@@ -460,26 +499,24 @@ class Fri:
             codewords.append(cur)
         return codewords
 
-    def _commit_rounds(self, codeword, proof_stream, rounds):
+    def _commit_rounds(self, codeword, proof_stream, rounds, pairs=False):
         """the same loop with the Fiat-Shamir step in Python (any proof stream): a round's fold and tree are ENQUEUED in one library
-        call (sc_fri_fold_commit_dev) and everything the host can do without the root (the next output vector) happens while the
-        device hashes"""
+        call (sc_fri_fold_commit_dev; pairs: over pair trees, sc_fri_fold_pairs_commit_dev) and everything the host can do without
+        the root (the next output vector) happens while the device hashes"""
+        start_tree, tree, fold_commit = ("start_pair_tree", "pair_tree", "fold_pairs_commit") if pairs else ("start_tree", "tree", "fold_commit")
         omega, offset = self.omega, self.offset
         codewords = []
+        getattr(codeword, start_tree)()
         for r in range(rounds):
-            N = len(codeword)
-            if r == 0:
-                codeword.start_tree()
-            folded = DeviceVector(N // 2) if r < rounds - 1 else None
+            folded = DeviceVector(len(codeword) // 2) if r < rounds - 1 else None
             # Merkle root of this round's codeword (waits for the device); the tree stays in HBM for the query phase
-            proof_stream.push(codeword.tree().root)
+            proof_stream.push(getattr(codeword, tree)().root)
             if r == rounds - 1:
                 break
             alpha = self.field.sample(proof_stream.prover_fiat_shamir())
             codewords.append(codeword)
-            codeword = codeword.fold_commit(alpha, offset, omega, folded)
-            omega = omega ^ 2
-            offset = offset ^ 2
+            codeword = getattr(codeword, fold_commit)(alpha, offset, omega, folded)
+            omega, offset = omega ^ 2, offset ^ 2
         codewords.append(codeword)
         return codewords
 
@@ -616,14 +653,9 @@ class Fri:
         for stream in streams:
             top.append(self.sample_indices(stream.prover_fiat_shamir(), N // 2, n_last, s))
         # query phase (fri.py:124-128): codeword j opens its round's a and b positions and the c positions of the round before
-        per_round, requests = [], [[] for _ in range(rounds)]
+        requests = [[] for _ in range(rounds)]
         for m in range(K):
-            mine, current = [], top[m]
-            for j in range(rounds - 1):
-                half = N >> (j + 1)
-                current = [index % half for index in current]
-                mine.append(current)
-            per_round.append(mine)
+            mine = [self._round_positions(top[m], j) for j in range(rounds - 1)]
             for j in range(rounds):
                 request = []
                 if j < rounds - 1:
@@ -659,19 +691,19 @@ class Fri:
                         stream.push(path)
         return top
 
-    def _prove_in_library(self, codeword, proof_stream, also_open):
-        """fri.py:115-130 as ONE library call (sc_fri_prove_dev): commit phase, the challenge over the transcript with the last
-        codeword, the sampled indices, and one kernel that writes every opening of the proof into pinned host memory.  What comes
-        back is pushed as the reference pushes it -- roots, the last codeword, per round s triples and 3 s paths -- in described
-        form (proof_objects); None when the stream or the codewords are not of the kind the library serves (the phases then run
-        one by one, with the same bytes)."""
+    def _library_route(self, codeword, proof_stream, also_open, pairs=False):
+        """What the two one-call routes (_prove_in_library, _prove_pairs_in_library) share before the call: None when the stream or
+        the codewords are not of the kind the library serves -- the caller's phases then run one by one, with the same bytes -- else
+        (prior, extra, extra_trees, roots, last_raw, top, quad): the stream's byte strings so far, also_open's codewords and their
+        trees, and the buffers the call fills (the roots, the last codeword's residues, the top-level and the quadrupled indices)."""
         import ctypes
-        import numpy as np
         rounds, s = self.num_rounds(), self.num_colinearity_tests
         N = self.domain_length
         if not (isinstance(codeword, DeviceCodeword) and _po.eligible(codeword) and codeword._tree is None and N >= 2 and N & (N - 1) == 0):
             return None
         if rounds < 2:                  # (fri.py:122 reads codewords[1]: the reference itself has no proof with fewer than two codewords)
+            return None
+        if pairs and (N >> (rounds - 1)) < 2:                    # (a pair tree needs a last codeword of two elements)
             return None
         if self.field.p != Field.P_MAIN or s > (N >> (rounds - 1)) or s < 1 or library_transcript(proof_stream, rounds) is None:
             return None
@@ -683,13 +715,59 @@ class Fri:
         if rounds + len(extra) > 32:
             return None
         self._check_omega_order(N)
-        prior = list(proof_stream.objects)
+        return (list(proof_stream.objects), extra, [cw.tree() for cw in extra], ctypes.create_string_buffer(64 * rounds),
+                ctypes.create_string_buffer(16 * (N >> (rounds - 1))), (ctypes.c_uint64 * s)(), (ctypes.c_uint64 * (4 * s))())
+
+    def _library_arguments(self, codeword, also_open, route, answers):
+        """the arguments the two calls share (include/starkcore.h).  No handle of the commit phase comes back (vecs_out = trees_out =
+        NULL): nothing reads the folded codewords or their trees once the openings are on the host, and the library hands their
+        memory back before it returns"""
+        import ctypes
+        prior, extra, extra_trees, roots, last_raw, top, quad = route
         k, ne = len(prior), len(extra)
-        roots = ctypes.create_string_buffer(64 * rounds)
-        n_last = N >> (rounds - 1)
-        last_raw = ctypes.create_string_buffer(16 * n_last)
-        top = (ctypes.c_uint64 * s)()
-        quad = (ctypes.c_uint64 * (4 * s))()
+        return (codeword.vec.ptr, self.domain_length, _sc.fe_bytes(self.offset.value), _sc.fe_bytes(self.omega.value), self.num_rounds(),
+                self.num_colinearity_tests, b"".join(prior), (ctypes.c_uint32 * max(1, k))(*map(len, prior)), k,
+                ne, (ctypes.c_void_p * max(1, ne))(*[t._h for t in extra_trees]),
+                (ctypes.c_void_p * max(1, ne))(*[cw.vec.ptr for cw in extra]), int(also_open.shift) if ne else 0,
+                None, None, roots, None, last_raw, top, quad, answers.ptr, answers.nbytes, None)
+
+    def _push_library_commit(self, proof_stream, codeword, field, roots, last_raw, nonce):
+        """What comes back from either call, pushed as the reference pushes the commit phase (fri.py:71, :91): the roots, the last
+        codeword in the clear (described: proof_objects.ElementList), and the nonce the library found and hashed into the seed of
+        the indices.  field: the field object of the folded codewords' entries (a proof is pickled by identity).  Returns the entry
+        holders per codeword and the stream's described objects, for the query phase's description."""
+        raw = roots.raw
+        rounds = len(raw) // 64
+        for r in range(rounds):
+            proof_stream.push(raw[64 * r:64 * r + 64])
+        holders = [_po.entries_of(codeword)] + [_po.DetachedEntries(field) for _ in range(rounds - 1)]
+        lazy = _po.lazy_objects(proof_stream)
+        lazy.add(_po.ElementList(holders[-1], last_raw.raw))
+        if self.grinding_bits:
+            lazy.append(int(nonce.value))
+        return holders, lazy
+
+    def _take_library_openings(self, also_open, count, data, values_at, paths_at, where):
+        """also_open's answers as views of the pinned buffer `data`: per codeword 4 s residues from byte values_at on, 4 s paths of
+        log2 N digests from byte paths_at on, and the positions as the library wrote them (`where`)"""
+        c, stride = 4 * self.num_colinearity_tests, 64 * (self.domain_length.bit_length() - 1)
+        also_open.answers = [(data[values_at + 16 * c * e:values_at + 16 * c * (e + 1)],
+                              data[paths_at + c * stride * e:paths_at + c * stride * (e + 1)].reshape(c, stride)) for e in range(count)]
+        also_open.position_arrays = [where[c * e:c * (e + 1)] for e in range(count)]
+
+    def _prove_in_library(self, codeword, proof_stream, also_open):
+        """fri.py:115-130 as ONE library call (sc_fri_prove_dev): commit phase, the challenge over the transcript with the last
+        codeword, the sampled indices, and one kernel that writes every opening of the proof into pinned host memory.  What comes
+        back is pushed as the reference pushes it -- roots, the last codeword, per round s triples and 3 s paths -- in described
+        form (proof_objects); None when the stream or the codewords are not of the kind the library serves (_library_route)."""
+        import ctypes
+        import numpy as np
+        route = self._library_route(codeword, proof_stream, also_open)
+        if route is None:
+            return None
+        rounds, s, N = self.num_rounds(), self.num_colinearity_tests, self.domain_length
+        _, extra, _, roots, last_raw, top, _ = route
+        ne = len(extra)
         # openings per pair (see include/starkcore.h): codeword j: the 2 s of its own round (j < rounds - 1) -- the c positions of the round
         # before are among them -- and the last codeword the s of the round before
         counts = [2 * s if j + 1 < rounds else (s if j > 0 else 0) for j in range(rounds)] + [4 * s] * ne
@@ -702,15 +780,8 @@ class Fri:
         # back to the pool when the stream is dropped after serialize().  A caller that keeps streams calls
         # proof_stream.objects.detach() (proof_objects.LazyProofObjects.detach) to hold plain objects instead.
         answers = _sc.HostBuffer(el_bytes + path_bytes + 8 * total)
-        extra_trees = [cw.tree() for cw in extra]
         nonce = ctypes.c_uint64(0)
-        # no handle of the commit phase comes back (vecs_out = trees_out = NULL): nothing reads the folded codewords or their trees
-        # once the openings are on the host, and the library hands their memory back before it returns
-        arguments = (codeword.vec.ptr, N, _sc.fe_bytes(self.offset.value), _sc.fe_bytes(self.omega.value), rounds, s,
-                     b"".join(prior), (ctypes.c_uint32 * max(1, k))(*map(len, prior)), k,
-                     ne, (ctypes.c_void_p * max(1, ne))(*[t._h for t in extra_trees]),
-                     (ctypes.c_void_p * max(1, ne))(*[cw.vec.ptr for cw in extra]), int(also_open.shift) if ne else 0,
-                     None, None, roots, None, last_raw, top, quad, answers.ptr, answers.nbytes, None)
+        arguments = self._library_arguments(codeword, also_open, route, answers)
         if self.grinding_bits:                                   # the same call with the proof of work between the last codeword and the indices
             rc = _sc.lib().sc_fri_prove_grind_dev(*arguments, self.grinding_bits, ctypes.byref(nonce))
         else:
@@ -718,31 +789,15 @@ class Fri:
         if rc == _sc.SC_ERR_UNSUPPORTED:
             return None
         _sc._check(rc)
-        # the commit phase's objects (fri.py:71, :91): the roots, then the last codeword in the clear
-        raw = roots.raw
-        for r in range(rounds):
-            proof_stream.push(raw[64 * r:64 * r + 64])
-        holders = [_po.entries_of(codeword)] + [_po.DetachedEntries(self.field) for _ in range(rounds - 1)]
-        lazy = _po.lazy_objects(proof_stream)
-        lazy.add(_po.ElementList(holders[-1], last_raw.raw))
-        if self.grinding_bits:
-            lazy.append(int(nonce.value))                        # the nonce the library found and hashed into the seed of the indices
+        holders, lazy = self._push_library_commit(proof_stream, codeword, self.field, roots, last_raw, nonce)
         # the query phase's objects (fri.py:104-113): described by the answers as they lie in the pinned buffer
         data = answers.array
         own = sum(counts[:rounds])                               # openings of the commit phase's codewords; the caller's come behind them
         own_paths = sum(64 * c * d for c, d in zip(counts[:rounds], depths[:rounds]))
-        if rounds > 1:
-            positions = data[el_bytes + path_bytes:el_bytes + path_bytes + 8 * own].view(np.uint64)
-            lazy.add(_po.FriQueryPhase(holders, s, counts[:rounds], depths[:rounds], data[:16 * own], data[el_bytes:el_bytes + own_paths], positions))
+        where = data[el_bytes + path_bytes:el_bytes + path_bytes + 8 * total].view(np.uint64)
+        lazy.add(_po.FriQueryPhase(holders, s, counts[:rounds], depths[:rounds], data[:16 * own], data[el_bytes:el_bytes + own_paths], where[:own]))
         if also_open is not None:
-            vo, po, fetched = own, el_bytes + own_paths, []
-            where = data[el_bytes + path_bytes:el_bytes + path_bytes + 8 * total].view(np.uint64)
-            for c, d in zip(counts[rounds:], depths[rounds:]):
-                fetched.append((data[16 * vo:16 * (vo + c)], data[po:po + 64 * c * d].reshape(c, 64 * d)))
-                vo += c
-                po += 64 * c * d
-            also_open.answers = fetched
-            also_open.position_arrays = [where[own + 4 * s * e:own + 4 * s * (e + 1)] for e in range(ne)]      # the same, as the library wrote them
+            self._take_library_openings(also_open, ne, data, 16 * own, el_bytes + own_paths, where[own:])
         return list(top)
 
     def _query_all(self, codewords, top_level_indices, proof_stream, also_open=None):
@@ -752,11 +807,7 @@ class Fri:
         s = self.num_colinearity_tests
         rounds = len(codewords) - 1
         halves = [len(cw) // 2 for cw in codewords]           # (len() of a device codeword is a call into the binding: once each)
-        per_round, indices = [], [index for index in top_level_indices]
-        for i in range(rounds):
-            half = halves[i]
-            indices = [index % half for index in indices]
-            per_round.append(indices)
+        per_round = [self._round_positions(top_level_indices, i) for i in range(rounds)]
         requests = []
         for j in range(len(codewords)):
             request = []
@@ -812,74 +863,38 @@ class Fri:
         kernel's pair form from 2^16 elements down), last codeword, proof of work, indices, and one kernel that writes every pair,
         every path and also_open's openings into pinned host memory.  What comes back is pushed as _prove_pairs pushes it -- roots,
         the last codeword, the nonce, per round s pairs and s paths -- in described form (proof_objects.FriPairsQueryPhase).  Served
-        under the conditions of _prove_in_library; None otherwise, and _prove_pairs then runs with the same bytes."""
+        under the conditions of _prove_in_library (_library_route); None otherwise, and _prove_pairs then runs with the same bytes."""
         import ctypes
         import numpy as np
-        rounds, s = self.num_rounds(), self.num_colinearity_tests
-        N = self.domain_length
-        if not (isinstance(codeword, DeviceCodeword) and _po.eligible(codeword) and codeword._tree is None and N >= 2 and N & (N - 1) == 0):
+        route = self._library_route(codeword, proof_stream, also_open, pairs=True)
+        if route is None:
             return None
-        if rounds < 2 or (N >> (rounds - 1)) < 2:
-            return None
-        if self.field.p != Field.P_MAIN or s > (N >> (rounds - 1)) or s < 1 or library_transcript(proof_stream, rounds) is None:
-            return None
-        extra = []
-        if also_open is not None:
-            extra = also_open.codewords
-            if extra is None or also_open.shift is None or not all(isinstance(cw, DeviceCodeword) and _po.eligible(cw) and len(cw) == N for cw in extra):
-                return None
-        if rounds + len(extra) > 32:
-            return None
-        self._check_omega_order(N)
-        prior = list(proof_stream.objects)
-        k, ne = len(prior), len(extra)
-        roots = ctypes.create_string_buffer(64 * rounds)
-        last_raw = ctypes.create_string_buffer(16 * (N >> (rounds - 1)))
-        top = (ctypes.c_uint64 * s)()
-        quad = (ctypes.c_uint64 * (4 * s))()
+        rounds, s, N = self.num_rounds(), self.num_colinearity_tests, self.domain_length
+        _, extra, _, roots, last_raw, top, _ = route
+        ne = len(extra)
         # the four sections of `answers` (include/starkcore.h): pairs, also_open's elements, paths, positions
         opened = rounds - 1
         depths = [(N >> (j + 1)).bit_length() - 1 for j in range(opened)]                  # log2 of codeword j's n_j / 2 pair leaves
-        depth0 = N.bit_length() - 1
         pair_bytes = (32 * s * opened + 255) & ~255
         element_bytes = (16 * 4 * s * ne + 255) & ~255
         own_paths = 64 * s * sum(depths)
-        path_bytes = (own_paths + 64 * 4 * s * depth0 * ne + 255) & ~255
+        path_bytes = (own_paths + 64 * 4 * s * (N.bit_length() - 1) * ne + 255) & ~255
         total = s * opened + 4 * s * ne
         # (lifetime of the pinned buffer: see _prove_in_library -- the segments and also_open.answers are views of it)
         answers = _sc.HostBuffer(pair_bytes + element_bytes + path_bytes + 8 * total)
-        extra_trees = [cw.tree() for cw in extra]
         nonce = ctypes.c_uint64(0)
-        rc = _sc.lib().sc_fri_prove_pairs_dev(codeword.vec.ptr, N, _sc.fe_bytes(self.offset.value), _sc.fe_bytes(self.omega.value), rounds, s,
-                                              b"".join(prior), (ctypes.c_uint32 * max(1, k))(*map(len, prior)), k,
-                                              ne, (ctypes.c_void_p * max(1, ne))(*[t._h for t in extra_trees]),
-                                              (ctypes.c_void_p * max(1, ne))(*[cw.vec.ptr for cw in extra]), int(also_open.shift) if ne else 0,
-                                              None, None, roots, None, last_raw, top, quad, answers.ptr, answers.nbytes, None,
-                                              self.grinding_bits, ctypes.byref(nonce))
+        rc = _sc.lib().sc_fri_prove_pairs_dev(*self._library_arguments(codeword, also_open, route, answers), self.grinding_bits, ctypes.byref(nonce))
         if rc == _sc.SC_ERR_UNSUPPORTED:
             return None
         _sc._check(rc)
-        raw = roots.raw
-        for r in range(rounds):
-            proof_stream.push(raw[64 * r:64 * r + 64])
-        # (the folded codewords' entries carry the FIELD OBJECT of the codeword they were folded from, as DeviceCodeword.fold_pairs_commit's
-        # do: a proof is pickled by identity)
-        holders = [_po.entries_of(codeword)] + [_po.DetachedEntries(codeword.field) for _ in range(rounds - 1)]
-        lazy = _po.lazy_objects(proof_stream)
-        lazy.add(_po.ElementList(holders[-1], last_raw.raw))
-        if self.grinding_bits:
-            lazy.append(int(nonce.value))
+        # (the folded codewords' entries carry the FIELD OBJECT of the codeword they were folded from, as DeviceCodeword.fold_pairs_commit's do)
+        holders, lazy = self._push_library_commit(proof_stream, codeword, codeword.field, roots, last_raw, nonce)
         data = answers.array
         paths_at, where_at = pair_bytes + element_bytes, pair_bytes + element_bytes + path_bytes
         where = data[where_at:where_at + 8 * total].view(np.uint64)
         lazy.add(_po.FriPairsQueryPhase(holders[:opened], s, depths, data[:32 * s * opened], data[paths_at:paths_at + own_paths], where[:s * opened]))
         if also_open is not None:
-            fetched, c, stride = [], 4 * s, 64 * depth0
-            for e in range(ne):
-                po = paths_at + own_paths + e * c * stride
-                fetched.append((data[pair_bytes + 16 * c * e:pair_bytes + 16 * c * (e + 1)], data[po:po + c * stride].reshape(c, stride)))
-            also_open.answers = fetched
-            also_open.position_arrays = [where[s * opened + c * e:s * opened + c * (e + 1)] for e in range(ne)]
+            self._take_library_openings(also_open, ne, data, pair_bytes, paths_at + own_paths, where[s * opened:])
         return list(top)
 
     def _prove_pairs(self, codeword, proof_stream, also_open=None):
@@ -893,23 +908,11 @@ class Fri:
         N = len(codeword)
         assert(N & (N - 1) == 0 and (N >> (rounds - 1)) >= 2), "pair leaves need power-of-two codewords of at least two elements in every round"
         self._check_omega_order(N)                             # (before anything is enqueued)
-        omega, offset = self.omega, self.offset
-        codewords = []
-        codeword.start_pair_tree()
-        for r in range(rounds):
-            folded = DeviceVector(len(codeword) // 2) if r < rounds - 1 else None
-            proof_stream.push(codeword.pair_tree().root)       # (waits for the device; the tree stays in HBM for the query phase)
-            if r == rounds - 1:
-                break
-            alpha = self.field.sample(proof_stream.prover_fiat_shamir())
-            codewords.append(codeword)
-            codeword = codeword.fold_pairs_commit(alpha, offset, omega, folded)
-            omega, offset = omega ^ 2, offset ^ 2
-        codewords.append(codeword)
+        codewords = self._commit_rounds(codeword, proof_stream, rounds, pairs=True)
         proof_stream.push(codewords[-1].tolist())              # the last codeword in the clear
         self.grind(proof_stream)
         top_level_indices = self.sample_indices(proof_stream.prover_fiat_shamir(), N // 2, len(codewords[-1]), s)
-        requests = [[index % (N >> (r + 1)) for index in top_level_indices] for r in range(rounds - 1)]
+        requests = [self._round_positions(top_level_indices, r) for r in range(rounds - 1)]
         for pairs, paths in _sc.query_pairs(codewords[:-1], requests):
             for pair in pairs:
                 proof_stream.push(pair)
@@ -934,76 +937,6 @@ class Fri:
     def _path_shape(path, depth):
         return type(path) in (list, tuple) and len(path) == depth and all(type(d) is bytes and len(d) == 64 for d in path)
 
-    def _verify_pairs(self, proof_stream, polynomial_values, checks=None, owner=None):
-        """`verify` with pair_leaves; with `checks` (a BatchChecks) the same walk with every path and colinearity test recorded as a row
-        for the batch's device calls instead of evaluated (a pair's path: a LEAF_DIGEST row over Merkle.row_leaf computed here; a
-        test: the existing 80-byte row with the y_c looked up here).  y_c of round r is never in the proof: it is the member of the
-        next round's pair at a % (half / 2) that lies at position a, or last_codeword[a] in the last queried round -- so all pairs
-        are pulled before the first test.  A pair that is not two field elements below p, or a path that is not log2(half) digests of
-        64 bytes, returns False before anything is appended to polynomial_values."""
-        rounds, s = self.num_rounds(), self.num_colinearity_tests
-        roots, alphas = [], []
-        for _ in range(rounds):
-            roots.append(proof_stream.pull())
-            alphas.append(self.field.sample(proof_stream.verifier_fiat_shamir()))
-        last_codeword = proof_stream.pull()
-        try:
-            well_formed = Merkle.commit_pairs(last_codeword) == roots[-1]
-        except Exception:
-            well_formed = False
-        if not well_formed:
-            return Fri._reject("last codeword is not well formed") if checks is None else False
-        squarings = 1 << (rounds - 1)
-        last_omega, last_offset = self.omega ^ squarings, self.offset ^ squarings
-        assert(last_omega.inverse() == last_omega ^ (len(last_codeword) - 1)), "omega does not have right order"
-        allowed = len(last_codeword) // self.expansion_factor - 1
-        observed = self._last_codeword_degree(last_codeword, last_omega, last_offset)
-        if observed > allowed:
-            return Fri._reject("last codeword does not correspond to polynomial of low enough degree", "observed degree: %s" % observed,
-                               "but should be: %s" % allowed) if checks is None else False
-        if not self._check_grinding(proof_stream):
-            return Fri._reject("proof of work fails") if checks is None else False
-        top_level_indices = self.sample_indices(proof_stream.verifier_fiat_shamir(), self.domain_length >> 1, self.domain_length >> (rounds - 1), s)
-        # everything the query phase holds, and its shape
-        pairs, paths = [], []
-        for r in range(rounds - 1):
-            depth = (self.domain_length >> (r + 1)).bit_length() - 1
-            pairs.append([self._pair_shape(proof_stream.pull()) for _ in range(s)])
-            paths.append([proof_stream.pull() for _ in range(s)])
-            if None in pairs[r]:
-                return Fri._reject("a pair is not two field elements") if checks is None else False
-            if not all(Fri._path_shape(path, depth) for path in paths[r]):
-                return Fri._reject("an authentication path has the wrong shape") if checks is None else False
-        omega, offset = self.omega, self.offset
-        for r in range(rounds - 1):
-            half = self.domain_length >> (r + 1)
-            lower = [index % half for index in top_level_indices]
-            if r + 2 < rounds:
-                y_c = [pairs[r + 1][t][0 if a < half // 2 else 1] for t, a in enumerate(lower)]
-            else:
-                y_c = [last_codeword[a] for a in lower]
-            if checks is not None:
-                round_index = checks.round(offset, omega, alphas[r])
-                refs = []
-                if r == 0:
-                    checks.truncate(polynomial_values, len(polynomial_values), refs)
-            for a, (ya, yb), yc in zip(lower, pairs[r], y_c):
-                b = a + half
-                if r == 0:
-                    polynomial_values += [(a, ya), (b, yb)]
-                # (x_a, y_a), (x_b, y_b) and (alpha, y_c) lie on one line: that is the fold of fri.py:85 read backwards
-                if checks is not None:
-                    refs.append(checks.colinearity(owner, round_index, offset, omega, a, b, alphas[r], ya, yb, yc))
-                elif not test_colinearity([(offset * (omega ^ a), ya), (offset * (omega ^ b), yb), (alphas[r], yc)]):
-                    return Fri._reject("colinearity check failure")
-            for a, pair, path in zip(lower, pairs[r], paths[r]):
-                if checks is not None:
-                    checks.merkle(owner, roots[r], a, path, None, leaf_digest=Merkle.row_leaf(pair))
-                elif not Merkle.verify_pair(roots[r], a, path, pair):
-                    return Fri._reject("merkle authentication path verification fails for a pair")
-            omega, offset = omega ^ 2, offset ^ 2
-        return True
-
     def _last_codeword_degree(self, last_codeword, last_omega, last_offset):
         """Degree of the interpolant of the last codeword on its coset: intt + unscale (the route the
         reference's fri.py:165-166 / docs describe) -- same unique polynomial as Lagrange at fri.py:164."""
@@ -1012,75 +945,25 @@ class Fri:
         assert(fast_coset_evaluate(poly, last_offset, last_omega, len(last_codeword)) == last_codeword), "re-evaluated codeword does not match original!"
         return poly.degree()
 
-    @staticmethod
-    def _reject(*lines):
-        for line in lines:
-            print(line)
-        return False
-
     def verify(self, proof_stream, polynomial_values):
-        if self.pair_leaves:
-            return self._verify_pairs(proof_stream, polynomial_values)
-        rounds, s = self.num_rounds(), self.num_colinearity_tests
-        # the commit phase replayed: per round a root and the challenge it determines, then the last codeword in the clear
-        roots, alphas = [], []
-        for _ in range(rounds):
-            roots.append(proof_stream.pull())
-            alphas.append(self.field.sample(proof_stream.verifier_fiat_shamir()))
-        last_codeword = proof_stream.pull()
-        if Merkle.commit(last_codeword) != roots[-1]:
-            return Fri._reject("last codeword is not well formed")
-        # the last codeword lives on the coset after rounds - 1 squarings; it must be of low degree there
-        squarings = 1 << (rounds - 1)
-        last_omega, last_offset = self.omega ^ squarings, self.offset ^ squarings
-        assert(last_omega.inverse() == last_omega ^ (len(last_codeword) - 1)), "omega does not have right order"
-        allowed = len(last_codeword) // self.expansion_factor - 1
-        observed = self._last_codeword_degree(last_codeword, last_omega, last_offset)
-        if observed > allowed:
-            return Fri._reject("last codeword does not correspond to polynomial of low enough degree", "observed degree: %s" % observed,
-                               "but should be: %s" % allowed)
-        if not self._check_grinding(proof_stream):
-            return Fri._reject("proof of work fails")
-        # the query phase: consistency of consecutive codewords at the sampled positions
-        top_level_indices = self.sample_indices(proof_stream.verifier_fiat_shamir(), self.domain_length >> 1, self.domain_length >> (rounds - 1), s)
-        omega, offset = self.omega, self.offset
-        for r in range(rounds - 1):
-            half = self.domain_length >> (r + 1)
-            lower = [index % half for index in top_level_indices]
-            upper = [index + half for index in lower]
-            triples = [proof_stream.pull() for _ in range(s)]
-            for a, b, (ya, yb, yc) in zip(lower, upper, triples):
-                if r == 0:
-                    polynomial_values += [(a, ya), (b, yb)]
-                # (x_a, y_a), (x_b, y_b) and (alpha, y_c) lie on one line: that is the fold of fri.py:85 read backwards
-                if not test_colinearity([(offset * (omega ^ a), ya), (offset * (omega ^ b), yb), (alphas[r], yc)]):
-                    return Fri._reject("colinearity check failure")
-            for a, b, (ya, yb, yc) in zip(lower, upper, triples):
-                for root, position, leaf, label in ((roots[r], a, ya, "aa"), (roots[r], b, yb, "bb"), (roots[r + 1], a, yc, "cc")):
-                    if not Merkle.verify(root, position, proof_stream.pull(), leaf):
-                        return Fri._reject("merkle authentication path verification fails for " + label)
-            omega, offset = omega ^ 2, offset ^ 2
-        return True
+        return self._walk(proof_stream, polynomial_values, HostChecks(), None)
 
     def verify_batch(self, proof_streams, polynomial_values_lists):
         """[self.verify(stream, values) for ...] with every Merkle path and colinearity test of the batch checked in one device call
         per kind (csrc/merkle_verify.cuh); a proof on which `verify` raises is reported False, and never affects the others"""
         checks = BatchChecks(len(proof_streams))
         for owner, (proof_stream, polynomial_values) in enumerate(zip(proof_streams, polynomial_values_lists)):
-            self._collect(proof_stream, polynomial_values, checks, owner)
+            try:
+                if not self._walk(proof_stream, polynomial_values, checks, owner):
+                    checks.reject(owner)
+            except Exception:
+                checks.reject(owner)
         return checks.run()
 
-    def _collect(self, proof_stream, polynomial_values, checks, owner):
-        """`verify`'s walk over one proof (line by line the same pulls), its checks recorded in `checks` instead of evaluated"""
-        try:
-            if not self._collect_checks(proof_stream, polynomial_values, checks, owner):
-                checks.reject(owner)
-        except Exception:
-            checks.reject(owner)
-
-    def _collect_checks(self, proof_stream, polynomial_values, checks, owner):
-        if self.pair_leaves:
-            return self._verify_pairs(proof_stream, polynomial_values, checks, owner)
+    def _walk(self, proof_stream, polynomial_values, checks, owner):
+        """THE verifier (fri.py:132-231): one walk over a proof, pull by pull, whose checks go to `checks` -- a HostChecks decides each
+        at once and ends the walk at the first that fails (`verify`); a BatchChecks records it as a row for proof `owner` and always
+        goes on (`verify_batch`, FastStark.verify_batch).  False: rejected on the way; True: nothing failed so far."""
         rounds, s = self.num_rounds(), self.num_colinearity_tests
         # the commit phase replayed: per round a root and the challenge it determines, then the last codeword in the clear
         roots, alphas = [], []
@@ -1088,8 +971,15 @@ class Fri:
             roots.append(proof_stream.pull())
             alphas.append(self.field.sample(proof_stream.verifier_fiat_shamir()))
         last_codeword = proof_stream.pull()
-        if Merkle.commit(last_codeword) != roots[-1]:
-            return False
+        if self.pair_leaves:                                     # (a last codeword no pair tree can be built over is rejected ...
+            try:
+                well_formed = Merkle.commit_pairs(last_codeword) == roots[-1]
+            except Exception:
+                well_formed = False
+        else:                                                    # ... one no decimal tree can be built over raises, as in the reference)
+            well_formed = Merkle.commit(last_codeword) == roots[-1]
+        if not well_formed:
+            return checks.reject(owner, "last codeword is not well formed")
         # the last codeword lives on the coset after rounds - 1 squarings; it must be of low degree there
         squarings = 1 << (rounds - 1)
         last_omega, last_offset = self.omega ^ squarings, self.offset ^ squarings
@@ -1097,28 +987,72 @@ class Fri:
         allowed = len(last_codeword) // self.expansion_factor - 1
         observed = self._last_codeword_degree(last_codeword, last_omega, last_offset)
         if observed > allowed:
-            return False
+            return checks.reject(owner, "last codeword does not correspond to polynomial of low enough degree", "observed degree: %s" % observed,
+                                 "but should be: %s" % allowed)
         if not self._check_grinding(proof_stream):
-            return False
+            return checks.reject(owner, "proof of work fails")
         # the query phase: consistency of consecutive codewords at the sampled positions
         top_level_indices = self.sample_indices(proof_stream.verifier_fiat_shamir(), self.domain_length >> 1, self.domain_length >> (rounds - 1), s)
+        query_phase = self._walk_pairs if self.pair_leaves else self._walk_triples
+        return query_phase(proof_stream, polynomial_values, checks, owner, roots, alphas, last_codeword, top_level_indices)
+
+    def _walk_triples(self, proof_stream, polynomial_values, checks, owner, roots, alphas, last_codeword, top_level_indices):
+        """decimal leaves: per round the s triples (y_a, y_b, y_c), their tests, then 3 s paths, each pulled right before its check"""
+        omega, offset = self.omega, self.offset
+        for r in range(len(roots) - 1):
+            half = self.domain_length >> (r + 1)
+            lower = self._round_positions(top_level_indices, r)
+            triples = [proof_stream.pull() for _ in lower]
+            round_index = checks.round(offset, omega, alphas[r])
+            if r == 0:        # registered before the tests: a later triple that raises must not keep pairs `verify` would not have appended
+                checks.truncate(polynomial_values, len(polynomial_values))
+            for a, (ya, yb, yc) in zip(lower, triples):
+                if r == 0:
+                    polynomial_values += [(a, ya), (a + half, yb)]
+                # (x_a, y_a), (x_b, y_b) and (alpha, y_c) lie on one line: that is the fold of fri.py:85 read backwards
+                if not checks.colinearity(owner, round_index, offset, omega, a, a + half, alphas[r], ya, yb, yc):
+                    return checks.reject(owner, "colinearity check failure")
+            for a, (ya, yb, yc) in zip(lower, triples):
+                for root, position, leaf, label in ((roots[r], a, ya, "aa"), (roots[r], a + half, yb, "bb"), (roots[r + 1], a, yc, "cc")):
+                    if not checks.merkle(owner, root, position, proof_stream.pull(), leaf):
+                        return checks.reject(owner, "merkle authentication path verification fails for " + label)
+            omega, offset = omega ^ 2, offset ^ 2
+        return True
+
+    def _walk_pairs(self, proof_stream, polynomial_values, checks, owner, roots, alphas, last_codeword, top_level_indices):
+        """pair leaves: per round s pairs (y_a, y_b) and s paths, one per pair (a row whose leaf digest, Merkle.row_leaf, is computed
+        here).  y_c of round r is never in the proof: it is the member of the next round's pair at a % (half / 2) that lies at
+        position a, or last_codeword[a] in the last queried round -- so every round's pairs and paths are pulled before the first test.
+        A pair that is not two field elements below p, or a path that is not log2(half) digests of 64 bytes, rejects before anything is
+        appended to polynomial_values."""
+        rounds, s = len(roots), self.num_colinearity_tests
+        pairs, paths = [], []
+        for r in range(rounds - 1):
+            depth = (self.domain_length >> (r + 1)).bit_length() - 1
+            pairs.append([self._pair_shape(proof_stream.pull()) for _ in range(s)])
+            paths.append([proof_stream.pull() for _ in range(s)])
+            if None in pairs[r]:
+                return checks.reject(owner, "a pair is not two field elements")
+            if not all(Fri._path_shape(path, depth) for path in paths[r]):
+                return checks.reject(owner, "an authentication path has the wrong shape")
         omega, offset = self.omega, self.offset
         for r in range(rounds - 1):
             half = self.domain_length >> (r + 1)
-            lower = [index % half for index in top_level_indices]
-            upper = [index + half for index in lower]
-            triples = [proof_stream.pull() for _ in range(s)]
+            lower = self._round_positions(top_level_indices, r)
+            if r + 2 < rounds:
+                y_c = [pairs[r + 1][t][0 if a < half // 2 else 1] for t, a in enumerate(lower)]
+            else:
+                y_c = [last_codeword[a] for a in lower]
             round_index = checks.round(offset, omega, alphas[r])
-            refs = []
-            if r == 0:        # registered before the tests: a later triple that raises must not keep pairs verify would not have appended
-                checks.truncate(polynomial_values, len(polynomial_values), refs)
-            for a, b, (ya, yb, yc) in zip(lower, upper, triples):
+            if r == 0:
+                checks.truncate(polynomial_values, len(polynomial_values))
+            for a, (ya, yb), yc in zip(lower, pairs[r], y_c):
                 if r == 0:
-                    polynomial_values += [(a, ya), (b, yb)]
-                # (x_a, y_a), (x_b, y_b) and (alpha, y_c) lie on one line: that is the fold of fri.py:85 read backwards
-                refs.append(checks.colinearity(owner, round_index, offset, omega, a, b, alphas[r], ya, yb, yc))
-            for a, b, (ya, yb, yc) in zip(lower, upper, triples):
-                for root, position, leaf in ((roots[r], a, ya), (roots[r], b, yb), (roots[r + 1], a, yc)):
-                    checks.merkle(owner, root, position, proof_stream.pull(), leaf)
+                    polynomial_values += [(a, ya), (a + half, yb)]
+                if not checks.colinearity(owner, round_index, offset, omega, a, a + half, alphas[r], ya, yb, yc):
+                    return checks.reject(owner, "colinearity check failure")
+            for a, pair, path in zip(lower, pairs[r], paths[r]):
+                if not checks.merkle(owner, roots[r], a, path, None, leaf_digest=Merkle.row_leaf(pair)):
+                    return checks.reject(owner, "merkle authentication path verification fails for a pair")
             omega, offset = omega ^ 2, offset ^ 2
         return True

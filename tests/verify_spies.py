@@ -48,7 +48,7 @@ def row_counts(monkeypatch):
 @pytest.fixture
 def combination_hosts(monkeypatch):
     """the BatchChecks of every FastStark.verify_batch call, and the owners (members of the batch) for which the host decided an opened
-    point of the combination (the `holds` of FastStark._collect_checks, which every row carries for the case that the device cannot
+    point of the combination (the `holds` of FastStark._walk, which every row carries for the case that the device cannot
     hold or decide it), one entry per call"""
     import fast_stark
     import fri
